@@ -15,14 +15,24 @@ torchrun WORLD_SIZE must equal --gpus.  RCCL is used only either side of the pat
 next to the headline value: `gather` (every rank's PCM of one step to rank 0) and, for configs[2], `broadcast` (the
 shared wide-band streams from rank 0).
 
-Extra legs on rank 0 at N = 1 (reported as extra keys; the headline `value` stays the HBM-resident run):
+A plain run does what the headline needs and nothing else: it sets up, warms up, times K steps, writes the last timed step's
+PCM if --dump-outputs DIR is given, and prints the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, the configuration).  Everything else it measures or checks runs with --full:
+  kernels_ms_per_step, roofline, pilot_pll   a separate untimed, profiled pass (HIP events per stage), the streaming-bandwidth
+                 probe, and on rank 0 at N = 1 roofline.control (the f32 stage-A kernel on fresh handles)
+  rds_check      configs[4]: the decoded RDS bits against the generator's
+  gather         N > 1: one step's PCM of every rank to rank 0 over RCCL
+and, on rank 0 at N = 1, the extra legs (extra keys; the headline `value` stays the HBM-resident run):
   sustained      the same step loop for >= --sustain seconds
   host_ingest    raw uint8 / float32 IQ from PINNED host memory, double-buffered: the copy of step k+1 overlaps the
                  processing of step k (PCIe-inclusive rates)
   host_call      latency of the single-receiver drop-in call: 1 channel, 16384 samples, fmx_process_host (in a process of its own)
   cpu_baseline   the oracle (a port) on the host cores; with oracle/_ref present also the reference's own leaf classes
+  other_workloads, strong_scaling_projection   the other BASELINE configs and the shard sizes, each a `--full --quick` run of its own
+--full --quick keeps the profiled pass, the probe and the checks and drops the extra legs and the control.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config4|shard512|config1|config2|config3|config5]
+                    [--dump-outputs DIR] [--full [--quick]]
 """
 import argparse
 import importlib
@@ -59,6 +69,8 @@ WORKLOADS = {
                         "per channel, cyclically (four blocks of 0.1 s); the decoded bits are checked behind the timed region"),
 }
 
+
+DUMP_BYTES = 60 * 10 ** 6                 # --dump-outputs: at most this many bytes of PCM (a fixed sample of the channels beyond it)
 
 RDS_BLOCKS = 4            # 4 blocks of 0.1 s = 475 RDS bits (1187.5 bit/s): the shortest run of blocks that is periodic in the bit clock
 RDS_CYCLE_BITS = 475
@@ -266,9 +278,20 @@ def cpu_baseline(seconds_budget=12.0, ref_budget=6.0, config0_budget=5.0):
     return out
 
 
+def dump_outputs(d, torch, pcm, channels, frames):
+    """--dump-outputs: the PCM the last timed step returned, [channels, frames, 2] float32, as d/pcm.npy -- all channels, or a fixed
+    sample of them (seed 0, ascending, indices in d/pcm_channels.npy) when all would exceed DUMP_BYTES."""
+    os.makedirs(d, exist_ok=True)
+    k = min(channels, max(1, DUMP_BYTES // (frames * 2 * 4)))
+    idx = np.arange(channels) if k == channels else np.sort(np.random.default_rng(0).choice(channels, k, replace=False))
+    sel = torch.as_tensor(idx, dtype=torch.long, device=pcm.device)
+    np.save(os.path.join(d, "pcm.npy"), pcm.index_select(0, sel)[:, :frames].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "pcm_channels.npy"), idx.astype(np.float64))
+
+
 def sub_bench(extra):
     """One short run of this script in a process of its own (another workload / shard size); returns the compact result."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--quick"] + extra
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--quick"] + extra
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ))
         j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -347,7 +370,13 @@ def main():
     ap.add_argument("--sustain", type=float, default=5.0, help="seconds of the sustained leg (0 = skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ingest", action="store_true", help="skip the host-ingest and host-call legs")
-    ap.add_argument("--quick", action="store_true", help="headline line only: no sustained / ingest / latency / CPU legs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the profiled pass (kernels_ms_per_step, roofline), the bandwidth probe, the checks, "
+                         "and the extra legs (sustained / ingest / latency / CPU / control / other workloads)")
+    ap.add_argument("--quick", action="store_true", help="with --full: no sustained / ingest / latency / CPU / control / other-workload legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the PCM of the last timed step as DIR/pcm.npy (float32 [channels, frames, 2]; a fixed sample of the channels "
+                         "when all would exceed %d MB, their indices in DIR/pcm_channels.npy)" % (DUMP_BYTES // 10 ** 6))
     ap.add_argument("--stride-pad", type=int, default=0,
                     help="complex samples of padding between consecutive streams in the IQ buffer (even)")
     ap.add_argument("--selftest-spawn", action="store_true", help=argparse.SUPPRESS)
@@ -358,6 +387,10 @@ def main():
         return
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if not args.full:                            # a plain run: the headline only
+        args.quick = True
     if args.quick:
         args.sustain = 0.0; args.no_ingest = True; args.no_cpu_baseline = True; args.no_extra_workloads = True
 
@@ -501,11 +534,14 @@ def main():
     t0 = time.perf_counter()
     frames = 0
     for _ in range(args.steps):
-        frames += step()
+        last_frames = step()
+        frames += last_frames
     torch.cuda.synchronize()
     barrier()
     dt_local = time.perf_counter() - t0
     f.synchronize()                     # raises if a stage-B wait gave up during the run (the figures would be void)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, pcm, channels, last_frames)
     dt = dt_local
     per_rank = [dt_local]
     if world > 1:
@@ -515,36 +551,38 @@ def main():
         per_rank = [float(x.item()) for x in allt]
         dt = max(per_rank)
 
-    # ---- per-kernel times from a separate, untimed pass (HIP events on the call's stream, recorded by the library) ----
+    # ---- --full: per-kernel times from a separate, untimed pass (HIP events on the call's stream, recorded by the library) ----
     # Every profiled step is enqueued while a spin kernel holds the stream (~1 ms), so that the GPU meets the step's kernels and
     # events back to back: the intervals then hold kernel time only, not the host's enqueue gaps (which made the stage times of
     # the small workloads add up to more than ms_per_step).
-    f.profile_enable(True)
-    f.profile_read(reset=True)
-    prof = {"launches": [0, 0, 0, 0], "ms": [0.0, 0.0, 0.0, 0.0]}
-    per_step = [[], [], []]                 # stage times of every profiled step (the populations in which they differ from step to step)
-    rep0, ex0 = f.pll_replays(), f.pll_exact_segments()
-    nprof = min(args.steps, 10) if nblk == 1 else max(min(args.steps, 10), nblk)     # (a whole cycle of the input blocks)
-    for _ in range(nprof):
-        with torch.cuda.stream(call_stream):
-            torch.cuda._sleep(2000000)
-        step()
+    pieces = f.last_call_pieces()
+    if args.full:
+        f.profile_enable(True)
+        f.profile_read(reset=True)
+        prof = {"launches": [0, 0, 0, 0], "ms": [0.0, 0.0, 0.0, 0.0]}
+        per_step = [[], [], []]                 # stage times of every profiled step (the populations in which they differ from step to step)
+        rep0, ex0 = f.pll_replays(), f.pll_exact_segments()
+        nprof = min(args.steps, 10) if nblk == 1 else max(min(args.steps, 10), nblk)     # (a whole cycle of the input blocks)
+        for _ in range(nprof):
+            with torch.cuda.stream(call_stream):
+                torch.cuda._sleep(2000000)
+            step()
+            torch.cuda.synchronize()
+            one = f.profile_read(reset=True)
+            # (a call made in overlapping pieces -- FMX_P_CALL_PIECES: pre-pass batches -- records one set of events per piece: a step's stage time is their sum)
+            pieces = f.last_call_pieces()
+            for k in range(3):
+                prof["launches"][k] += one["launches"][k] if pieces <= 1 else 1; prof["ms"][k] += one["ms"][k]
+                per_step[k].append(one["ms"][k] / (max(one["launches"][k], 1) if pieces <= 1 else 1))
         torch.cuda.synchronize()
-        one = f.profile_read(reset=True)
-        # (a call made in overlapping pieces -- FMX_P_CALL_PIECES: pre-pass batches -- records one set of events per piece: a step's stage time is their sum)
-        pieces = f.last_call_pieces()
-        for k in range(3):
-            prof["launches"][k] += one["launches"][k] if pieces <= 1 else 1; prof["ms"][k] += one["ms"][k]
-            per_step[k].append(one["ms"][k] / (max(one["launches"][k], 1) if pieces <= 1 else 1))
-    torch.cuda.synchronize()
-    pll_counts = {"steps": nprof, "fail_safe_replays_per_step": round((f.pll_replays() - rep0) / nprof, 2),
-                  "guard_sequential_segments_per_step": round((f.pll_exact_segments() - ex0) / nprof, 1),
-                  "segments_per_step": channels * -(-(n // 12) // 1536)}
-    f.profile_enable(False)
+        pll_counts = {"steps": nprof, "fail_safe_replays_per_step": round((f.pll_replays() - rep0) / nprof, 2),
+                      "guard_sequential_segments_per_step": round((f.pll_exact_segments() - ex0) / nprof, 1),
+                      "segments_per_step": channels * -(-(n // 12) // 1536)}
+        f.profile_enable(False)
 
     # ---- gather leg: one step's PCM of every rank to rank 0 over RCCL, timed on its own ------------------
     gather = None
-    if world > 1:
+    if world > 1 and args.full:
         fr = frames // max(args.steps, 1)
         loc = pcm[:, :fr].contiguous()
         shard.gather_pcm(loc, total_channels, dst=0)                # communicator / buffer warm-up
@@ -588,7 +626,7 @@ def main():
                      "unit": "MS/s", "ms_per_step": round(el / k * 1e3, 4)}
 
     rds_check = None
-    if args.workload == "config5":
+    if args.full and args.workload == "config5":
         # the decoded bit string of a few channels against what the generator sent (cyclic, 475 bits)
         torch.cuda.synchronize()
         worst, checked, nb = 0, 0, 0
@@ -610,45 +648,9 @@ def main():
     if rank == 0:
         total = float(total_channels) * n * args.steps
         value = total / dt / 1e6
-        launches = max(prof["launches"][0], 1)
-        ms_a = prof["ms"][0] / launches
         front_kernel_used = f.last_front_kernel()       # which of the three stage-A kernels the handle ran (include/fmx.h: FMX_P_FRONT_KERNEL)
         # algorithmic bytes of ONE front-end launch: every channel reads its n samples (8 B) and writes n/12 (8 B)
         alg_bytes = ALG_BYTES_STAGE_A * channels * n
-        achieved = alg_bytes / (ms_a * 1e-3) / 1e9 if ms_a > 0 else 0.0
-        # HBM bytes per launch from the rocprofv3 PMC passes (FETCH_SIZE doubled per MI355X_MICROARCH.md + WRITE_SIZE),
-        # committed under profiles/; only valid for the configuration it was collected on.
-        traffic = None
-        try:
-            pmcs = sorted(x for x in os.listdir(os.path.join(ROOT, "profiles")) if x.endswith("_front_pmc.json"))
-            pmc = json.load(open(os.path.join(ROOT, "profiles", pmcs[-1])))
-            if pmc.get("channels") == channels and pmc.get("block") == n:
-                traffic = pmc["front_kernel_hbm_bytes_per_launch"]
-        except Exception:
-            traffic = None
-        # practical ceiling next to the nominal peak: this box's streaming bandwidth, measured after the timed
-        # region with the library's probe kernels (float2 copy; and stage A's own shape: read 12, write 1)
-        measured = {}
-        try:
-            import ctypes as C
-            L = fmx_amd.load_library()
-            L.fmx_debug_stream_bandwidth.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_double)]
-            for mode, key in ((0, "copy_GBps"), (1, "read12_write1_GBps"), (2, "read_only_GBps")):
-                g = C.c_double()
-                # (over 7.5 GiB, the size of a step's input: a 1 GiB probe, rounds 2-5, re-read a buffer of which the 256 MB memory-side cache
-                # keeps a quarter from one pass to the next and reported 6.3 TB/s for a traffic mix that streams at 5.4-5.5,
-                # tools/ubench/stream_shape.hip)
-                if L.fmx_debug_stream_bandwidth(local_rank, mode, 15 << 29, 3, C.byref(g)) == 0:
-                    measured[key] = round(g.value, 1)
-        except Exception as e:      # the probe is a diagnostic; the bench line does not depend on it
-            measured = {"error": str(e)}
-        # the stage table as a decomposition of the timed step: the event intervals of the profiled pass, scaled so that they add up to
-        # ms_per_step (the raw intervals stay beside it)
-        raw = [prof["ms"][k] / max(prof["launches"][k], 1) for k in range(3)]
-        ms_step = dt / args.steps * 1e3
-        scale = ms_step / sum(raw) if sum(raw) > 0 else 1.0
-        kernels_ms = {"front_fir": round(raw[0] * scale, 4), "demod_pilot_pss": round(raw[1] * scale, 4), "audio_fir_resample": round(raw[2] * scale, 4),
-                      "scale": round(scale, 4), "note": "raw event intervals x scale = a decomposition of ms_per_step"}
         out = {
             "metric": "IQ MSamples/s demodulated to 48 kHz stereo",
             "value": round(value, 3), "unit": "MS/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -666,28 +668,69 @@ def main():
                        "streams_per_gpu": nstreams, "block_samples_per_channel": n,
                        "realtime_channels_equiv": round(value / 2.304, 1),
                        "pcm_frames_per_channel_per_step": frames // max(args.steps, 1), "parallelism": "channels sharded, 1 rank/GPU"},
-            "roofline": {"bound": "hbm", "kernel": {1: "fmx::front_kernel", 3: "fmx::f4::front4_kernel"}.get(front_kernel_used, "?") + " (input FIR stage)",
-                         "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                         "frac_read_only": round(achieved * (8.0 / ALG_BYTES_STAGE_A) / HBM_PEAK_GBPS, 4),
-                         "traffic": traffic, "avg_launch_ms": round(ms_a, 4),
-                         # both byte counts: what the channels consume (every channel reads its stream) and what is unique in HBM
-                         # (a stream several channels listen to is read once from HBM, then from the caches)
-                         "front_fir_bytes": {"per_channel_sample": alg_bytes, "unique_stream": 8.0 * nstreams * n + (8.0 / 12.0) * channels * n,
-                                             "frac_unique_stream": round((8.0 * nstreams * n + (8.0 / 12.0) * channels * n) / (ms_a * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if ms_a > 0 else None},
-                         "algorithmic_bytes_per_launch": alg_bytes, "measured_stream_bandwidth": measured,
-                         "frac_of_measured": (round(achieved / measured["read12_write1_GBps"], 4)
-                                              if measured.get("read12_write1_GBps") else None),
-                         # (the read-12-write-1 probe is a kernel of its own shape, not a ceiling -- stage A beats it by 2-15 % --; what nothing beats is this
-                         # GPU's read-only stream: the stage's READ rate against it)
-                         "frac_read_only_of_measured_reads": (round(achieved * (8.0 / ALG_BYTES_STAGE_A) / measured["read_only_GBps"], 4)
-                                                              if measured.get("read_only_GBps") else None)},
-            "kernels_ms_per_step": kernels_ms,
-            "kernels_ms_per_step_raw": {"front_fir": round(raw[0], 4), "demod_pilot_pss": round(raw[1], 4), "audio_fir_resample": round(raw[2], 4),
-                                        "stage_b_min_median_max": [round(float(v), 4) for v in (np.min(per_step[1]), np.median(per_step[1]), np.max(per_step[1]))],
-                                        "note": "HIP-event intervals of a separate untimed pass of %d steps, each enqueued behind a spin kernel; their sum "
-                                                "exceeds the timed step by the events' own cost" % launches},
-            "pilot_pll": pll_counts,
+        }
+        if args.full:
+            launches = max(prof["launches"][0], 1)
+            ms_a = prof["ms"][0] / launches
+            achieved = alg_bytes / (ms_a * 1e-3) / 1e9 if ms_a > 0 else 0.0
+            # HBM bytes per launch from the rocprofv3 PMC passes (FETCH_SIZE doubled: gfx950 counts half the bytes of wide streaming reads; + WRITE_SIZE),
+            # committed under profiles/; only valid for the configuration it was collected on.
+            traffic = None
+            try:
+                pmcs = sorted(x for x in os.listdir(os.path.join(ROOT, "profiles")) if x.endswith("_front_pmc.json"))
+                pmc = json.load(open(os.path.join(ROOT, "profiles", pmcs[-1])))
+                if pmc.get("channels") == channels and pmc.get("block") == n:
+                    traffic = pmc["front_kernel_hbm_bytes_per_launch"]
+            except Exception:
+                traffic = None
+            # practical ceiling next to the nominal peak: this box's streaming bandwidth, measured after the timed
+            # region with the library's probe kernels (float2 copy; and stage A's own shape: read 12, write 1)
+            measured = {}
+            try:
+                import ctypes as C
+                L = fmx_amd.load_library()
+                L.fmx_debug_stream_bandwidth.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_double)]
+                for mode, key in ((0, "copy_GBps"), (1, "read12_write1_GBps"), (2, "read_only_GBps")):
+                    g = C.c_double()
+                    # (over 7.5 GiB, the size of a step's input: a 1 GiB probe, rounds 2-5, re-read a buffer of which the 256 MB memory-side cache
+                    # keeps a quarter from one pass to the next and reported 6.3 TB/s for a traffic mix that streams at 5.4-5.5,
+                    # tools/ubench/stream_shape.hip)
+                    if L.fmx_debug_stream_bandwidth(local_rank, mode, 15 << 29, 3, C.byref(g)) == 0:
+                        measured[key] = round(g.value, 1)
+            except Exception as e:      # the probe is a diagnostic; the bench line does not depend on it
+                measured = {"error": str(e)}
+            # the stage table as a decomposition of the timed step: the event intervals of the profiled pass, scaled so that they add up to
+            # ms_per_step (the raw intervals stay beside it)
+            raw = [prof["ms"][k] / max(prof["launches"][k], 1) for k in range(3)]
+            ms_step = dt / args.steps * 1e3
+            scale = ms_step / sum(raw) if sum(raw) > 0 else 1.0
+            kernels_ms = {"front_fir": round(raw[0] * scale, 4), "demod_pilot_pss": round(raw[1] * scale, 4), "audio_fir_resample": round(raw[2] * scale, 4),
+                          "scale": round(scale, 4), "note": "raw event intervals x scale = a decomposition of ms_per_step"}
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": {1: "fmx::front_kernel", 3: "fmx::f4::front4_kernel"}.get(front_kernel_used, "?") + " (input FIR stage)",
+                             "achieved": round(achieved, 2),
+                             "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                             "frac_read_only": round(achieved * (8.0 / ALG_BYTES_STAGE_A) / HBM_PEAK_GBPS, 4),
+                             "traffic": traffic, "avg_launch_ms": round(ms_a, 4),
+                             # both byte counts: what the channels consume (every channel reads its stream) and what is unique in HBM
+                             # (a stream several channels listen to is read once from HBM, then from the caches)
+                             "front_fir_bytes": {"per_channel_sample": alg_bytes, "unique_stream": 8.0 * nstreams * n + (8.0 / 12.0) * channels * n,
+                                                 "frac_unique_stream": round((8.0 * nstreams * n + (8.0 / 12.0) * channels * n) / (ms_a * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if ms_a > 0 else None},
+                             "algorithmic_bytes_per_launch": alg_bytes, "measured_stream_bandwidth": measured,
+                             "frac_of_measured": (round(achieved / measured["read12_write1_GBps"], 4)
+                                                  if measured.get("read12_write1_GBps") else None),
+                             # (the read-12-write-1 probe is a kernel of its own shape, not a ceiling -- stage A beats it by 2-15 % --; what nothing beats is this
+                             # GPU's read-only stream: the stage's READ rate against it)
+                             "frac_read_only_of_measured_reads": (round(achieved * (8.0 / ALG_BYTES_STAGE_A) / measured["read_only_GBps"], 4)
+                                                                  if measured.get("read_only_GBps") else None)},
+                "kernels_ms_per_step": kernels_ms,
+                "kernels_ms_per_step_raw": {"front_fir": round(raw[0], 4), "demod_pilot_pss": round(raw[1], 4), "audio_fir_resample": round(raw[2], 4),
+                                            "stage_b_min_median_max": [round(float(v), 4) for v in (np.min(per_step[1]), np.median(per_step[1]), np.max(per_step[1]))],
+                                            "note": "HIP-event intervals of a separate untimed pass of %d steps, each enqueued behind a spin kernel; their sum "
+                                                    "exceeds the timed step by the events' own cost" % launches},
+                "pilot_pll": pll_counts,
+            })
+        out.update({
             **({"stage_groups": {"channels": [channels - f.last_second_group(), f.last_second_group()],
                                  "note": "stages B and C run as two channel groups on two streams (the audio stage of one beside the stereo stage of the other); stage A, "
                                          "the roofline's kernel, is one launch with the chip to itself; the demod_pilot_pss interval ends with the first group's stage B"}}
@@ -696,7 +739,7 @@ def main():
                                 "demodulator's lone-wave recurrences of piece k, stage B / C of piece k - 1); the stage intervals are sums over the pieces and overlap in time"}}
                if pieces > 1 else {}),
             "per_rank_value": [round(rank_channels[r] * n * args.steps / t / 1e6, 3) for r, t in enumerate(per_rank)],
-        }
+        })
         if rds_check: out["rds_check"] = rds_check
         if gather: out["gather"] = gather
         if bcast: out["broadcast"] = bcast

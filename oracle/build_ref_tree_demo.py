@@ -62,8 +62,11 @@ def build(out=OUT):
             subprocess.check_call([MOC] + [i for i in INCS if not i.startswith("-I" + QT)] + [h, "-o", m])
             cc(m, os.path.basename(m))
         cc(os.path.join(LINKDIR, "ref_tree_demo.cpp"), "ref_tree_demo")
+        # libfmx.so is found relative to the executable, not by the absolute path of the tree it was built in: oracle/_ref/ travels to the
+        # GPU box with the tree, and a checkout there may lie anywhere
+        rpath = "$ORIGIN/" + os.path.relpath(LIBDIR, os.path.dirname(os.path.abspath(out)))
         subprocess.check_call(["g++"] + objs + ["-L" + LIBDIR, "-lfmx", QTCORE, "-lpthread", "-Wl,-rpath-link," + os.path.join(QT, "lib"),
-                                                "-Wl,--allow-shlib-undefined", "-Wl,-rpath," + LIBDIR, "-o", out])
+                                                "-Wl,--allow-shlib-undefined", "-Wl,-rpath," + rpath, "-o", out])
     return out
 
 

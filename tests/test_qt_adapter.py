@@ -15,7 +15,7 @@ QTCORE = os.path.join(QT, "lib", "libQt5Core.so.5")
 HOSTQT = os.path.join(ROOT, "sdr-j-fm_amd", "host", "qt")
 LIBDIR = os.path.join(ROOT, "sdr-j-fm_amd", "lib")
 # conda ships an older libstdc++ next to its Qt; the ROCm runtime needs the system's
-RUN_ENV = dict(os.environ, LD_LIBRARY_PATH=os.path.join(QT, "lib"), LD_PRELOAD="/usr/lib/x86_64-linux-gnu/libstdc++.so.6",
+RUN_ENV = dict(os.environ, LD_LIBRARY_PATH=os.path.join(QT, "lib"), LD_PRELOAD=":".join(filter(None, (os.environ.get("LD_PRELOAD"), "/usr/lib/x86_64-linux-gnu/libstdc++.so.6"))),
                QT_QPA_PLATFORM="offscreen")
 
 needs_qt = pytest.mark.skipif(not (os.path.exists(MOC) and os.path.exists(QTCORE)), reason="no Qt (moc / QtCore) in this image")

@@ -77,7 +77,9 @@ import importlib.util  # noqa: E402
 _spec = importlib.util.spec_from_file_location("build_ref_tree_demo", os.path.join(ROOT, "oracle", "build_ref_tree_demo.py"))
 DEMO = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(DEMO)
-RUN_ENV = dict(os.environ, LD_LIBRARY_PATH=os.path.join(QT, "lib"), LD_PRELOAD="/usr/lib/x86_64-linux-gnu/libstdc++.so.6", QT_QPA_PLATFORM="offscreen")
+# (the libfmx.so under test is this tree's build, named to the loader here: the executable in oracle/_ref/ may have been linked in another
+# checkout, and its own search path then points there)
+RUN_ENV = dict(os.environ, LD_LIBRARY_PATH=DEMO.LIBDIR + ":" + os.path.join(QT, "lib"), LD_PRELOAD=":".join(filter(None, (os.environ.get("LD_PRELOAD"), "/usr/lib/x86_64-linux-gnu/libstdc++.so.6"))), QT_QPA_PLATFORM="offscreen")
 
 
 def test_binding_links_with_the_reference_rds_classes():

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in 0 1 2 4 7; do
   lib=$R/sdr-j-fm_amd/lib/ab/libfmx_abl$v.so; [ $v = 0 ] && lib=$R/sdr-j-fm_amd/lib/libfmx.so
   [ -f $lib ] || continue
-  FMX_LIB=$lib python $R/bench.py --channels $CH --steps 6 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+  FMX_LIB=$lib python $R/bench.py --full --channels $CH --steps 6 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.readlines()[-1]); print('abl=$v front ms', j['kernels_ms_per_step']['front_fir'], 'step ms', j['ms_per_step'])"
   FMX_LIB=$lib rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU -d /tmp/abl$v -o p -- python $R/bench.py --channels $CH --steps 2 --warmup 1 --no-cpu-baseline > /tmp/abl$v.log 2>&1

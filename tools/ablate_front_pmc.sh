@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in 0 1 2 4 6 7; do
   lib=$R/sdr-j-fm_amd/lib/ab/libfmx_abl$v.so; [ $v = 0 ] && lib=$R/sdr-j-fm_amd/lib/libfmx.so
   rm -rf /tmp/abl$v
-  FMX_LIB=$lib rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT -d /tmp/abl$v -o p -- python $R/bench.py --quick --no-cpu-baseline > /tmp/abl$v.log 2>&1
+  FMX_LIB=$lib rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT -d /tmp/abl$v -o p -- python $R/bench.py --full --quick --no-cpu-baseline > /tmp/abl$v.log 2>&1
   python - <<PY
 import sqlite3, glob, json
 ms = json.loads([l for l in open("/tmp/abl$v.log") if l.startswith("{")][-1])["kernels_ms_per_step"]["front_fir"]

@@ -5,7 +5,7 @@ for v in default "${TAGS[@]}"; do
   lib=$R/sdr-j-fm_amd/lib/ab/libfmx_$v.so; [ $v = default ] && lib=$R/sdr-j-fm_amd/lib/libfmx.so
   [ -f $lib ] || { echo "no $lib"; continue; }
   for rep in 1 2; do
-  FMX_LIB=$lib python $R/bench.py --quick --no-cpu-baseline "$@" 2>/dev/null | python -c "
+  FMX_LIB=$lib python $R/bench.py --full --quick --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.readlines()[-1]); k = j['kernels_ms_per_step']
 print('%-12s A %.4f  B %.4f  C %.4f  step %.4f  GS/s %.1f' % ('$v', k['front_fir'], k['demod_pilot_pss'], k['audio_fir_resample'], j['ms_per_step'], j['value'] / 1e3))"
