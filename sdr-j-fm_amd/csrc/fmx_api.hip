@@ -24,6 +24,16 @@ namespace {
 
 thread_local std::string g_err;
 int env_int(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
+// The FMX_* environment switches (diagnostics: the runs two GPU tests compare the default schedule with; none is needed by a user): read ONCE, by the
+// first fmx_create of the process -- nothing on the per-call path asks the environment.
+struct EnvSwitches {
+    bool pieces_serial;   // FMX_CALL_PIECES_SERIAL=1: the pieces of an overlapping call one after the other on the caller's stream
+    bool tail_split;      // FMX_TAIL_SPLIT=0: stages B and C as one channel group
+};
+const EnvSwitches &env_switches() {
+    static const EnvSwitches sw{env_int("FMX_CALL_PIECES_SERIAL", 0) != 0, env_int("FMX_TAIL_SPLIT", 1) != 0};
+    return sw;
+}
 int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
 #define HIPCHK(expr)                                                                       \
@@ -66,7 +76,7 @@ struct fmx_handle_s {
     int n_cus = 256; size_t lds_per_block = 65536;     // device limits the stage-A layout choice looks at
     std::vector<int32_t> act_up;                                     // one-shot action bits uploaded with the last parameter upload
     std::vector<uint8_t> rds_reset_req;                              // resetRds / triggerFrequencyChange asked for the group decoder's reset
-    hipEvent_t ev_in = nullptr, ev_dummy = nullptr;
+    hipEvent_t ev_in = nullptr;
     std::mutex mtx;                          // guards the mailbox (set_param from any thread)
     std::vector<ChanUser> user;
     std::vector<ChanParams> params;          // host mirror
@@ -156,8 +166,6 @@ struct fmx_handle_s {
     int64_t last_filter_event_g = 0;     // stream position at which a filter setter was last applied (ola_take_settings)
     std::vector<int64_t> origin_in, origin_au;   // per channel: the stream position (input samples / fm samples) at which the filter's block counter was last 0, as far as a
                                          // FOLDED handle knows it (0 from fmx_create; the machines' own counters at a demotion)
-    bool call_head = true;               // the launch sequence being enqueued is the first of its fmx_process_* call (a call may be made in pieces, run_call): a handle
-                                         // changes its filter structure there only -- fmx_filter_change_due speaks of CALLS
     bool promo_pending = false;          // a filter setter arrived behind the first call
     bool promo_recapture = false;        // ... and a setter of what pre_kernel applies (RF DC removal, balance, oscillator) behind it: the kept samples start over
     int64_t promo_have = 0, promo_g0 = 0;   // samples kept per stream, and the stream position of the first
@@ -788,14 +796,6 @@ int demote(fmx_handle h, hipStream_t s) {
 
 static bool any_rds_on(fmx_handle h) { return h->call_any_rds; }     // (as of the call's flush_mailbox)
 
-constexpr int PIPE_ROWS_AUTO = 3072;      // fm samples per piece of an overlapping call where pllC runs (two of stage B's segments; measured at 4096 channels:
-                                          // 2048 / 3072 / 4608 / 6400 fm samples per piece give 6.37 / 6.18 / 6.46 / 6.79 ms per step, the call made whole 8.24)
-constexpr int PIPE_ROWS_AUTO_PLL = 4608;  // ... where pllC runs for the PLL decoder only (round 6: its chain is 66 issue slots per sample instead of 80 and the launches' own cost counts more:
-                                          // pieces of 3072 x 6 / 4608 x 4 / 5376 x 3 + 3072 / 4608 x 3 + 3072 + 2304 / 4608 x 3 + 3840 + 1536 give 5.29 / 5.21 / 4.92 / 4.82 / 4.83 ms per step)
-constexpr int PIPE_ROWS_AUTO_AM = 3840;   // ... where the AM decoder runs (its chain is longer per sample): 3072 x 6 / 3840 x 4 + 2304 + 1536 / 3840 x 4 + 1536 + 2304 / 3072 x 5 + 2304 + 1536 give 6.0-6.1 / 5.72 / 5.93 / 5.77 ms per step
-constexpr int PIPE_ROWS_AUTO_SQ = 4608;   // ... where only squelches do (noise squelch 6.61 / 5.73 / 5.46 / 5.54 against 5.90 whole, level squelch 5.43 / 4.73 / 4.59 / 4.72 against 5.23)
-constexpr int TAIL_MIN_CHANNELS = 128;    // the second stage-B / C channel group: at least this many channels
-constexpr int PIPE_MIN_CHANNELS = 1024;   // automatic: batches that fill the chip
 constexpr int PLL_SEQ_AUTO_MAX = 64;   // FMX_P_PLL_SOLVER = 0: handles up to this many channels evaluate the pilot PLL sequentially
 
 // the tiled work arrays of the demodulator pre-pass (fmx_demod.hip): limited / unlimited samples in, demodulator output out.  (Allocated by the first call
@@ -862,7 +862,7 @@ int flush_mailbox(fmx_handle h) {
     for (int c = 0; c < h->channels; c++) { h->call_rds_mode[(size_t)c] = (int8_t)h->params[(size_t)c].rds_mode; any_rds |= (h->params[(size_t)c].rds_mode != 0); }
     h->call_any_rds = any_rds;
     // (a channel's RDS path runs while its decoder is on and stands still otherwise -- block filters, phase delay line, decimator and slicer
-    // keep what they hold, as the reference's processor's do: nothing restarts when a decoder is switched; run_call_one counts per channel)
+    // keep what they hold, as the reference's processor's do: nothing restarts when a decoder is switched; run_piece counts per channel)
     if (any_rds) { const int rc = ensure_rds(h); if (rc) return rc; }
     bool any_pll = false;
     for (auto &p : h->params) any_pll |= (p.decoder == 2 || p.decoder == 1 || p.squelch_mode != 0);     // pllC on the fm-rate IQ; |z| for the level squelch; the general AFC body for the noise squelch
@@ -949,39 +949,10 @@ void frames_geom(const fmx_handle h, int64_t n, CallGeom *G) {
 }
 // frames the second converter has put out after `in` frames at the working rate: outputs m with m q < in p
 int64_t conv2_out(const fmx_handle h, int64_t in) { return h->cv_nt ? (in * h->cv_p + h->cv_q - 1) / h->cv_q : in; }
+// PCM frames a call of n input samples produces now
+int64_t call_frames(const fmx_handle h, int64_t n) { CallGeom G{}; frames_geom(h, n, &G); return conv2_out(h, G.M1) - conv2_out(h, G.M0); }
 
-// Stage A runs one workgroup per channel, two per CU: a handle with fewer channels than that leaves compute units idle while each workgroup
-// walks its channel's tiles one after the other.  Such a call splits every channel in time (fmx_front.hip, CallGeom::parts): as many parts as
-// fill the chip, none shorter than FRONT_MIN_PART_TILES tiles (every later part computes one tile twice).  The results are the same bit for bit.
-constexpr int FRONT_MIN_PART_TILES = 6, FRONT_MAX_PARTS = 32, FRONT_TILE = 128 * DECIM;
-int front_parts_for(fmx_handle h, CallGeom &G) {
-    G.parts = 1; G.part_tiles = 0; G.streams = h->streams;
-    const int want = h->front_parts.load();
-    if (h->twins != 1 || want == 1) return FMX_OK;
-    const int64_t r0 = G.g0 % DECIM;
-    const int NT = (int)((r0 + G.n - 1) / FRONT_TILE) + 1;
-    int parts = want > 1 ? want : (2 * h->n_cus) / h->channels;
-    if (want <= 1 && parts > NT / FRONT_MIN_PART_TILES) parts = NT / FRONT_MIN_PART_TILES;
-    if (parts > FRONT_MAX_PARTS) parts = FRONT_MAX_PARTS;
-    if (parts > NT / 2) parts = NT / 2;              // (forced: at least two tiles per part)
-    if (parts < 2) return FMX_OK;
-    const int pt = (NT + parts - 1) / parts;
-    parts = (NT + pt - 1) / pt;
-    if (parts < 2) return FMX_OK;
-    if (!h->B.fsnap) {
-        const size_t C = (size_t)h->channels;
-        h->B.dc_pitch = (int32_t)(h->cfg.max_block / FRONT_TILE + 2);
-        HIPCHK(hipMalloc(&h->B.dc_tiles, sizeof(float4) * 2 * (size_t)h->streams * h->B.dc_pitch));
-        HIPCHK(hipMalloc(&h->B.fsnap, sizeof(FrontSnap) * C));
-        HIPCHK(hipMalloc(&h->B.hist_snap, sizeof(float2) * C * DECIM * A_HIST_COLS));
-        HIPCHK(hipMalloc(&h->B.dcv_snap, sizeof(float2) * C * DCV_SAVE));
-        for (void *p : {(void *)h->B.dc_tiles, (void *)h->B.fsnap, (void *)h->B.hist_snap, (void *)h->B.dcv_snap}) h->tail_ptrs.push_back(p);
-    }
-    G.parts = parts; G.part_tiles = pt;
-    return FMX_OK;
-}
-
-// the handle's side streams (a call made in overlapping pieces: run_call; stage B's last round of workgroups beside stage C: run_call_one), created when first wanted
+// the handle's side streams (a call made in overlapping pieces: run_call; stage B's last round of workgroups beside stage C: run_piece), created when first wanted
 int ensure_pipe_streams(fmx_handle h) {
     if (h->pipe_sA) return FMX_OK;
     // (plain streams, the recurrences' with priority.  Measured and not kept: compute units of their own for the recurrences -- CU-masked streams,
@@ -997,182 +968,202 @@ int ensure_pipe_streams(fmx_handle h) {
     return FMX_OK;
 }
 
-struct PipePiece { int k; };       // a piece of a call made in overlapping pieces (its number)
-int run_call_one(fmx_handle h, const void *d_iq, int32_t fmt, float s16_den, int64_t stream_stride, int64_t n, float2 *d_pcm,
-                 int64_t pcm_stride, int64_t *n_frames, hipStream_t s, const PipePiece *pp = nullptr);
-// One call of the boundary.  The RDS front end works on blocks of RDS_BLK fm samples, every channel on its own block phase, and one launch sequence covers
-// at most one block boundary per channel: while a channel decodes RDS, a longer call is made in pieces (the chain is invariant to how a stream is cut into calls).
-int run_call_pieces(fmx_handle h, const void *d_iq, int32_t fmt, float s16_den, int64_t stream_stride, int64_t n, float2 *d_pcm,
-                    int64_t pcm_stride, int64_t *n_frames, hipStream_t s);
-int run_call(fmx_handle h, const void *d_iq, int32_t fmt, float s16_den, int64_t stream_stride, int64_t n, float2 *d_pcm,
-             int64_t pcm_stride, int64_t *n_frames, hipStream_t s) {
-    h->call_head = true;
-    const int rc = run_call_pieces(h, d_iq, fmt, s16_den, stream_stride, n, d_pcm, pcm_stride, n_frames, s);
-    h->call_head = true;
-    return rc;
-}
-int run_call_pieces(fmx_handle h, const void *d_iq, int32_t fmt, float s16_den, int64_t stream_stride, int64_t n, float2 *d_pcm,
-                    int64_t pcm_stride, int64_t *n_frames, hipStream_t s) {
-    const int64_t PIECE = (int64_t)(RDS_BLK - 1) * h->decim;       // (J1 - J0 <= RDS_BLK whatever the call's phase in the fm-rate grid; decim: input samples per
-                                                                   // fm sample at this handle's rate -- 12, 6 or 1 as the reference decimates)
-    bool any_rds = false;
-    { std::lock_guard<std::mutex> lk(h->mtx); for (auto &p : h->params) any_rds |= (p.rds_mode != 0); }
-    h->last_pieces = 1;
-    if (!any_rds && fmt >= 0 && fmt <= 3 && n <= h->cfg.max_block) {
-        // A batch whose channels need the demodulator pre-pass (PLL / AM decoder, a squelch: fmx_demod.hip).  Its recurrences are one wave per 64 channels
-        // walking the call's fm samples one after the other -- 64 waves on 1024 SIMDs at 4096 channels, for longer than stages A, B and C together take --
-        // and nothing else can run meanwhile: stage B waits for its output, it waits for stage A.  Such a call is made in PIECES (the chain is invariant
-        // to how a stream is cut into calls) on three streams: stage A of piece k + 1 and stage B / C of piece k - 1 fill the chip while the pre-pass
-        // walks piece k.  The pre-pass's work arrays alternate between two halves of their allocation; an event per stage boundary orders the rest.
-        // What the stages share beyond their hand-over arrays: the myCount of the metaData snapshot (kept by stage B, read by the pre-pass: handed over by
-        // the host, CallGeom::host_count) and the RF DC level stage B's snapshot reads from stage A's state (a display value that moves by 1e-7 of its
-        // distance per sample: it may be the next piece's).
-        const int want = h->pipe_rows.load() >= 0 ? h->pipe_rows.load() : env_switches().call_pieces;
-        bool special = false, chain = false, am_chain = false;
-        { std::lock_guard<std::mutex> lk(h->mtx); for (auto &p : h->params) { special |= (p.decoder == 2 || p.decoder == 1 || p.squelch_mode != 0); chain |= (p.decoder == 2 || p.decoder == 1); am_chain |= (p.decoder == 1); } }
-        if (special && !h->ola_mode) { const int rc = ensure_prepass_arrays(h); if (rc) return rc; }
-        // (pllC's chain: longer pieces with a short last one, PIPE_ROWS_AUTO_PLL / _AM)
-        const bool taper = want < 0 && chain;
-        // (a call too short for two of the PLL decoder's longer pieces is cut into the shorter ones)
-        const int64_t rows = want > 0 ? ((want + 15) / 16) * 16
-                                      : (chain ? (n < 2 * (int64_t)(am_chain ? PIPE_ROWS_AUTO_AM : PIPE_ROWS_AUTO_PLL) * h->decim ? PIPE_ROWS_AUTO : (am_chain ? PIPE_ROWS_AUTO_AM : PIPE_ROWS_AUTO_PLL))
-                                               : PIPE_ROWS_AUTO_SQ);
-        const int64_t ends_rows = env_switches().call_pieces_ends >= 0 ? ((env_switches().call_pieces_ends + 15) / 16) * 16 : 0;
-        const int64_t half = (h->work_nj / 2) & ~(int64_t)15;
-        const int64_t piece = rows * h->decim;
-        // (only these batches.  Measured: the headline's batch -- no pre-pass; stage A bound by HBM, stage B by instruction issue -- made in 13 / 6 / 4 / 3 overlapping
-        // pieces takes 4.97 / 3.89 / 3.60 / 3.60 ms per step against 3.46 whole: stage B's workgroups fill the register files, the stages do not share a CU)
-        if (special && h->B.w_iq && want != 0 && !h->ola_mode && !h->cv_nt && (want > 0 || h->channels >= PIPE_MIN_CHANNELS) && rows + 2 <= half && n >= 2 * piece) {
-            {
-                CallGeom G{}; frames_geom(h, n, &G);
-                if (conv2_out(h, G.M1) - conv2_out(h, G.M0) > pcm_stride) return fail(FMX_E_TOO_LARGE, "pcm_stride smaller than the frames this call produces");
-            }
-            { const int rc = ensure_pipe_streams(h); if (rc) return rc; }
-            // the pieces run on the handle's three streams, behind what the caller's stream held when the call began; the caller's stream goes on behind the last of them
-            HIPCHK(hipEventRecord(h->pipe_ev0, s));
-            HIPCHK(hipStreamWaitEvent(h->pipe_sA, h->pipe_ev0, 0)); HIPCHK(hipStreamWaitEvent(h->pipe_sB, h->pipe_ev0, 0));
-            const int64_t bps = (fmt == 0) ? 8 : (fmt == 3 ? 4 : 2);
-            // the pieces' lengths.  What the call pays beyond the chain of the lone waves is its FIRST piece's stage A (nothing to overlap it with yet) and its
-            // LAST piece's stages B and C (the chain has ended): short end pieces of `ends` fm samples, equal ones in between.
-            std::vector<int64_t> lens;
-            const int64_t ends = ends_rows * h->decim;
-            if (ends > 0 && n >= 2 * ends + piece) {
-                const int64_t inner = n - 2 * ends;
-                int64_t m = (inner + piece / 2) / piece; if (m < 1) m = 1;
-                const int64_t grid = 16 * h->decim;
-                int64_t mid = ((inner / m) / grid) * grid;
-                if (mid / h->decim + 2 > half) { m++; mid = ((inner / m) / grid) * grid; }
-                lens.push_back(ends);
-                for (int64_t i = 0; i < m; i++) lens.push_back(mid);
-                lens.push_back(n - ends - m * mid);
-            }
-            if (!env_switches().call_pieces_list.empty()) {      // (a diagnostic: the pieces' fm samples spelt out; the last one takes what is left)
-                lens.clear(); int64_t used = 0;
-                for (int r : env_switches().call_pieces_list) { const int64_t l = (int64_t)r * h->decim; if (used + l < n) { lens.push_back(l); used += l; } }
-                lens.push_back(n - used);
-            }
-            bool fits = !lens.empty();
-            for (int64_t l : lens) fits = fits && l > 0 && l / h->decim + 2 <= half;
-            if (!fits && taper) {
-                // whole pieces, then the rest (between one and two pieces) as a multiple of half a segment of stage B's and a SHORT last piece of one segment to one
-                // and a half: what follows the chain's end is the last piece's stages B and C (19200 fm samples: 4608 4608 4608 3840 1536; AM decoder: 3840 x 4, 2304, 1536)
-                lens.clear();
-                const int64_t seg = (int64_t)1536 * h->decim;           // (stage B's segment, fmx_stageb.hip FB_W)
-                int64_t pos = 0;
-                while (n - pos >= 2 * piece) { lens.push_back(piece); pos += piece; }
-                const int64_t R = n - pos;
-                int64_t a = ((R - seg) / (seg / 2)) * (seg / 2);
-                if (a > piece) a = piece;
-                if (a >= seg) { lens.push_back(a); lens.push_back(R - a); } else lens.push_back(R);
-                fits = true;
-                for (int64_t l : lens) fits = fits && l > 0 && l / h->decim + 2 <= half;
-            }
-            if (!fits) {
-                lens.clear();
-                for (int64_t pos = 0; pos < n;) {
-                    // (a last piece shorter than half a piece rides with the one before it: the arrays' halves hold a piece and a half)
-                    int64_t len = (n - pos < piece) ? n - pos : piece;
-                    if (n - pos - len > 0 && n - pos - len < piece / 2 && (rows * 3) / 2 + 2 <= half) len = n - pos;
-                    lens.push_back(len); pos += len;
-                }
-            }
-            int64_t total = 0, pos = 0; int k = 0;
-            for (int64_t len : lens) {
-                int64_t got = 0;
-                const PipePiece pp{k};
-                const int rc = run_call_one(h, reinterpret_cast<const char *>(d_iq) + pos * bps, fmt, s16_den, stream_stride, len, d_pcm + total, pcm_stride, &got, h->pipe_sB, &pp);
-                if (rc) { (void)hipDeviceSynchronize(); return rc; }
-                total += got; pos += len; k++;
-            }
-            HIPCHK(hipEventRecord(h->pipe_evE, h->pipe_sB)); HIPCHK(hipStreamWaitEvent(s, h->pipe_evE, 0));
-            h->last_pieces = k;
-            if (n_frames) *n_frames = total;
-            return FMX_OK;
-        }
-    }
-    if (!any_rds || n <= PIECE || fmt < 0 || fmt > 3 || n > h->cfg.max_block) return run_call_one(h, d_iq, fmt, s16_den, stream_stride, n, d_pcm, pcm_stride, n_frames, s);
-    {
-        CallGeom G{}; frames_geom(h, n, &G);
-        if (conv2_out(h, G.M1) - conv2_out(h, G.M0) > pcm_stride) return fail(FMX_E_TOO_LARGE, "pcm_stride smaller than the frames this call produces");
-    }
-    const int64_t bps = (fmt == 0) ? 8 : (fmt == 3 ? 4 : 2);
-    int64_t total = 0;
-    for (int64_t pos = 0; pos < n; pos += PIECE) {
-        int64_t got = 0;
-        const int rc = run_call_one(h, reinterpret_cast<const char *>(d_iq) + pos * bps, fmt, s16_den, stream_stride, (n - pos < PIECE) ? n - pos : PIECE,
-                                    d_pcm + total, pcm_stride, &got, s);
-        if (rc) return rc;
-        total += got;
-    }
-    if (n_frames) *n_frames = total;
+int bytes_per_sample(int32_t fmt) { return fmt == FMX_IQ_F32 ? 8 : (fmt == FMX_IQ_S16 ? 4 : 2); }
+
+// the arguments of an fmx_process_* call, checked once at its head (run_call; fmx_process_host_raw for the caller's PCM buffer)
+int check_call(fmx_handle h, int32_t fmt, float s16_den, int64_t n, int64_t pcm_stride) {
+    if (fmt < 0 || fmt > 3) return fail(FMX_E_INVALID, "unknown IQ format");
+    int ex = 0;
+    if (fmt == 3 && (!(s16_den >= 1.0f) || std::frexp(s16_den, &ex) != 0.5f)) return fail(FMX_E_INVALID, "s16_denominator must be a power of two >= 1");
+    if (n <= 0 || n > h->cfg.max_block) return fail(FMX_E_TOO_LARGE, "n_complex must be in [1, max_block]");
+    if (call_frames(h, n) > pcm_stride) return fail(FMX_E_TOO_LARGE, "pcm_stride smaller than the frames this call produces");
     return FMX_OK;
 }
 
-int run_call_one(fmx_handle h, const void *d_iq, int32_t fmt, float s16_den, int64_t stream_stride, int64_t n, float2 *d_pcm,
-                 int64_t pcm_stride, int64_t *n_frames, hipStream_t s, const PipePiece *pp) {
-    if (fmt < 0 || fmt > 3) return fail(FMX_E_INVALID, "unknown IQ format");
-    if (fmt == 3) {
-        int ex = 0; const float m = std::frexp(s16_den, &ex);
-        if (!(s16_den >= 1.0f) || m != 0.5f) return fail(FMX_E_INVALID, "s16_denominator must be a power of two >= 1");
-    }
-    if (n <= 0 || n > h->cfg.max_block) return fail(FMX_E_TOO_LARGE, "n_complex must be in [1, max_block]");
-    int rc;
-    bool capture = false;
-    {   // a folded batch with a filter change pending (fmx_promote.hip): promoted once enough of its streams is kept, else this call's samples are kept too
-        bool do_promote = false, do_demote = false;
-        {
-            std::lock_guard<std::mutex> lk(h->mtx);
-            if (h->ola_mode) {
-                // (a promoted handle whose machines have been quiet goes back to the folded filters: it keeps a block of its streams first)
-                const bool ok = demotable(h);
-                if (!ok || h->promo_recapture) { h->demo_capture = false; h->promo_have = 0; }
-                else if (!h->demo_capture) { h->demo_capture = true; h->promo_have = 0; capture = true; }
-                else if (h->promo_have >= DEMO_TAIL_IN && h->call_head) do_demote = true;
-                else capture = true;
-                h->promo_recapture = false;
-            }
-            else if (!h->promo_pending) h->promo_recapture = false;
-            else if (h->promo_recapture) { h->promo_recapture = false; h->promo_have = 0; }      // (what pre_kernel applies changed: the kept samples start over, behind this call)
-            else if (h->promo_have >= PROMO_TAIL_IN && h->call_head) do_promote = true;
-            else capture = true;
+// what every piece of a call shares
+struct CallArgs { int32_t fmt; float s16_den; int64_t stream_stride, pcm_stride; };
+
+// The promotion turn of a piece.  A folded batch with a filter change pending (fmx_promote.hip) is promoted once enough of its streams is kept, else this
+// piece's samples are kept too (*capture); a promoted handle whose machines have been quiet goes back to the folded filters the same way.  Either change
+// happens at the head of an fmx_process_* call only, not between its pieces: fmx_filter_change_due speaks of CALLS.
+int promotion_turn(fmx_handle h, bool head, hipStream_t s, bool *capture) {
+    bool do_promote = false, do_demote = false;
+    {
+        std::lock_guard<std::mutex> lk(h->mtx);
+        if (h->ola_mode) {
+            const bool ok = demotable(h);      // (a quiet promoted handle keeps a block of its streams before it goes back)
+            if (!ok || h->promo_recapture) { h->demo_capture = false; h->promo_have = 0; }
+            else if (!h->demo_capture) { h->demo_capture = true; h->promo_have = 0; *capture = true; }
+            else if (h->promo_have >= DEMO_TAIL_IN && head) do_demote = true;
+            else *capture = true;
+            h->promo_recapture = false;
         }
-        if (do_promote) { rc = promote(h, s); if (rc) return rc; }
-        if (do_demote) { rc = demote(h, s); if (rc) return rc; }
+        else if (!h->promo_pending) h->promo_recapture = false;
+        else if (h->promo_recapture) { h->promo_recapture = false; h->promo_have = 0; }      // (what pre_kernel applies changed: the kept samples start over, behind this call)
+        else if (h->promo_have >= PROMO_TAIL_IN && head) do_promote = true;
+        else *capture = true;
     }
-    rc = flush_mailbox(h);
-    if (rc) return rc;
+    if (do_promote) return promote(h, s);
+    if (do_demote) return demote(h, s);
+    return FMX_OK;
+}
+
+// keep the piece's samples for the promotion (promotion_turn)
+int capture_samples(fmx_handle h, const void *d_iq, const CallArgs &a, const CallGeom &G, hipStream_t sa) {
+    if (h->tail_iq && h->promo_have + G.n > h->tail_cap) return FMX_OK;      // (cannot happen: a change is applied at the first call boundary behind PROMO_TAIL_IN samples)
+    if (!h->tail_iq) {
+        h->tail_cap = PROMO_TAIL_IN + h->cfg.max_block;
+        HIPCHK(hipMalloc(&h->tail_iq, sizeof(float2) * (size_t)h->streams * h->tail_cap));
+        HIPCHK(hipMalloc(&h->tail_snap, sizeof(FrontSnap) * (size_t)h->channels));
+        h->tail_ptrs.push_back(h->tail_iq); h->tail_ptrs.push_back(h->tail_snap);
+    }
+    if (h->promo_have == 0) { h->promo_g0 = h->g_total; launch_promo_state(h->B.state, h->tail_snap, h->channels, 0, sa); FMX_LAUNCHED(); }
+    launch_capture(d_iq, a.fmt, G.iq_scale, a.stream_stride, G.n, h->streams, h->tail_iq, h->tail_cap, h->promo_have, sa); FMX_LAUNCHED();
+    h->promo_have += G.n;
+    return FMX_OK;
+}
+
+// stage A on `sa` (the block machines: their input side and the stage on `s`): its split in time (plan_front_parts; the snapshot buffers allocated when first
+// needed) and its kernel
+int stage_a(fmx_handle h, CallGeom &G, const void *d_iq, hipStream_t s, hipStream_t sa) {
+    const FrontParts fp = plan_front_parts(G.g0, G.n, h->front_parts.load(), h->twins, h->channels, h->n_cus);
+    if (fp.parts > 1 && !h->B.fsnap) {
+        const size_t C = (size_t)h->channels;
+        h->B.dc_pitch = (int32_t)(h->cfg.max_block / FRONT_TILE + 2);
+        HIPCHK(hipMalloc(&h->B.dc_tiles, sizeof(float4) * 2 * (size_t)h->streams * h->B.dc_pitch));
+        HIPCHK(hipMalloc(&h->B.fsnap, sizeof(FrontSnap) * C));
+        HIPCHK(hipMalloc(&h->B.hist_snap, sizeof(float2) * C * DECIM * A_HIST_COLS));
+        HIPCHK(hipMalloc(&h->B.dcv_snap, sizeof(float2) * C * DCV_SAVE));
+        for (void *p : {(void *)h->B.dc_tiles, (void *)h->B.fsnap, (void *)h->B.hist_snap, (void *)h->B.dcv_snap}) h->tail_ptrs.push_back(p);
+    }
+    G.parts = fp.parts; G.part_tiles = fp.part_tiles;
+    // automatic: the filter on the matrix pipe wherever a handle qualifies and has the channels to fill the chip without splitting them in time
+    // (measured at 4096 channels on one box: 1.52 ms per launch against 1.75 for the four-wave kernel and 1.84 for the six-wave VALU kernel, which
+    // both sit at the packed-FMA power limit)
+    // (the complex-tap variant runs one channel per workgroup: a handle of one channel per compute unit fills the chip)
+    const int fk = h->front_kernel.load();
+    if (h->front4_ok && !h->front4_lo && (fk == 3 || (fk == 0 && G.parts <= 1))) { G.parts = 1; G.front4 = 1; }
+    if (h->front4_ok && h->front4_lo && (fk == 3 || (fk == 0 && h->channels >= h->n_cus))) { G.parts = 1; G.front4 = 2; }
+    // (what is reported is what runs: a call without a whole tile on the kernel's grid goes to front_kernel in launch_front)
+    h->last_front_kernel = (G.front4 && front4_tiles(G, d_iq) > 0) ? 3 : 1;
+    if (h->ola_mode) {
+        // RF DC removal / balance / LO mix per sample, the input filter as the reference's block machine, then the decimators
+        if (const int rc = ola_input_side(h, G, h->B, d_iq, s)) return rc;
+        CallGeom Gp = G; Gp.pre_processed = 1; Gp.iq_format = 0; Gp.iq_scale = 1.0f; Gp.stream_stride = h->cfg.max_block; Gp.streams_private = h->twins == 1 ? 1 : 0;
+        launch_front(h->T, h->B, Gp, h->d_u, h->channels, s);
+    } else
+    launch_front(h->T, h->B, G, d_iq, h->channels, sa);   // stage A: four waves per channel, packed-FMA FIR (fmx_front.hip)
+    FMX_LAUNCHED();
+    return FMX_OK;
+}
+
+// stage B (with its pre-pass for the PLL / AM decoders and the squelches): a piece of an overlapping call (piped), two channel groups (second > 0) or one
+// launch sequence on `s`
+int stage_b(fmx_handle h, const CallGeom &G, int k, bool piped, int second, hipStream_t s, hipStream_t sa) {
+    if (piped) {
+        // stage B of this piece behind its stage A.  The pre-pass of this piece: its parallel part (disc_kernel) behind the piece's stage A on that stream --
+        // and behind the stage B that read the half of the work arrays it is about to overwrite --, the recurrences on theirs, the noise squelch's pipeline
+        // and stage B on `s`
+        HIPCHK(hipEventRecord(h->pipe_evA, sa)); HIPCHK(hipStreamWaitEvent(s, h->pipe_evA, 0));
+        if (k >= 2) HIPCHK(hipStreamWaitEvent(sa, h->pipe_evB[k & 1], 0));
+        DeviceBuffers Bk = h->B;
+        if (k & 1) { const size_t off = (size_t)prepass_half(h->work_nj) * (size_t)h->pitch; Bk.w_iq += off; Bk.w_osc += off; }
+        const PrepassStreams ps{sa, h->pipe_sP, h->pipe_evD, h->pipe_evP};
+        launch_demod_fused(h->T, Bk, G, h->channels, s, &ps);
+        HIPCHK(hipEventRecord(h->pipe_evB[k & 1], s));
+    } else if (second > 0) {
+        // (the second group on the handle's side stream, behind stage A)
+        HIPCHK(hipEventRecord(h->pipe_evA, s)); HIPCHK(hipStreamWaitEvent(h->pipe_sA, h->pipe_evA, 0));
+        CallGeom G1 = G, G2 = G;
+        G1.ch0 = 0; G1.ch_count = h->channels - second; G2.ch0 = h->channels - second; G2.ch_count = second;
+        launch_demod_fused(h->T, h->B, G1, h->channels, s);
+        launch_demod_fused(h->T, h->B, G2, h->channels, h->pipe_sA);
+    } else
+    launch_demod_fused(h->T, h->B, G, h->channels, s);
+    if (G.J1 > G.J0) {       // (stage B's bookkeeping behind the call, fmx_stageb.hip)
+        int cnt = h->my_count_host + (int)(G.J1 - G.J0);
+        if (cnt > (SINCOS_N >> 1)) cnt -= (SINCOS_N >> 1) + 1;
+        h->my_count_host = cnt;
+    }
+    return FMX_OK;
+}
+
+// the RDS path of the channels that decode it, each at its own block phase
+int stage_rds(fmx_handle h, const CallGeom &G, hipStream_t s) {
+    const int64_t nj = G.J1 - G.J0;
+    int modes = 0;
+    for (int c = 0; c < h->channels; c++) {
+        const int m = h->call_rds_mode[(size_t)c];
+        modes |= 1 << m;
+        h->rds_nc0[(size_t)c] = m != 0 ? h->rds_nc[(size_t)c] : -1;
+    }
+    // (pageable source: the copy is staged before the call returns, the vector is free again)
+    HIPCHK(hipMemcpyAsync(h->d_rds_nc0, h->rds_nc0.data(), sizeof(int64_t) * (size_t)h->channels, hipMemcpyHostToDevice, s));
+    launch_rds(h->B, h->R, G, h->channels, h->rds_nc0.data(), modes, s);
+    for (int c = 0; c < h->channels; c++) {
+        const int64_t a = h->rds_nc0[(size_t)c];
+        if (a < 0) { h->last_m0[(size_t)c] = h->last_m1[(size_t)c]; continue; }       // (decoder off in this call: no outputs, not the last on-call's)
+        h->last_m0[(size_t)c] = a / 8; h->last_m1[(size_t)c] = (a + nj) / 8;
+        h->rds_nc[(size_t)c] = a + nj;
+    }
+    return FMX_OK;
+}
+
+// stage C: the audio filter and resampler (the block machines: the audio low-pass and the de-emphasis in front of it), a gain change's correction, the
+// second converter
+int stage_c(fmx_handle h, CallGeom &G, float2 *d_pcm, int64_t frames, int second, hipStream_t s) {
+    DeviceBuffers Bq = h->B;
+    if (h->ola_mode && G.J1 > G.J0) {
+        // the audio low-pass as the reference's block machine on the de-emphasised stream; the resampler reads its output
+        OlaBuffers O{}; O.src = h->B.dring; O.dst = h->d2ring; O.src_stride = O.dst_stride = h->dring; O.src_mask = O.dst_mask = h->dring - 1;
+        O.src_pos = O.dst_pos = G.J0;
+        HStep st1;
+        // de-emphasis behind the filter, as the reference orders them (:589-595)
+        if (ola_single_step(h, h->ola_au, G.J1 - G.J0, &st1)) {
+            OlaStepRef ref; const int rc = step_ref(h, st1, s, &ref); if (rc) return rc;
+            ola_fill(h->ola_au, O);
+            launch_deemph(h->B, G, h->d2ring, h->channels, s, &ref, &O); FMX_LAUNCHED();
+            ola_finish_single(h, h->ola_au, st1, ref, O, s);
+        } else {
+            const int rc = run_ola(h, h->ola_au, O, G.J1 - G.J0, s); if (rc) return rc;
+            launch_deemph(h->B, G, h->d2ring, h->channels, s, nullptr, nullptr); FMX_LAUNCHED();
+        }
+    }
+    if (h->ola_mode) Bq.dring = h->d2ring;
+    if (h->gain_pending && G.M1 > G.M0) { G.gain_fix = 1; launch_gain_fix(h->T, Bq, G, h->channels, s); FMX_LAUNCHED(); h->gain_pending = false; }
+    if (second > 0) {
+        CallGeom G1 = G, G2 = G;
+        G1.ch0 = 0; G2.ch0 = h->channels - second;
+        launch_audio(h->T, Bq, G1, d_pcm, h->channels - second, s);
+        launch_audio(h->T, Bq, G2, d_pcm, second, h->pipe_sA);
+        HIPCHK(hipEventRecord(h->pipe_evE, h->pipe_sA)); HIPCHK(hipStreamWaitEvent(s, h->pipe_evE, 0));
+    } else if (!h->cv_nt) launch_audio(h->T, Bq, G, d_pcm, h->channels, s);
+    else {
+        // the audio stage writes its 48 kHz frames behind the converter's history; theConverter's output goes to the caller
+        CallGeom G48 = G; G48.pcm_stride = h->x48_stride;
+        launch_audio(h->T, Bq, G48, h->d_x48 + h->cv_nt, h->channels, s);
+        launch_conv2(h->d_x48, h->x48_stride, h->d_cv_taps, h->cv_p, h->cv_q, h->cv_nt, G.M0, G.M1 - G.M0, conv2_out(h, G.M0), frames,
+                     d_pcm, G.pcm_stride, h->channels, s);
+    }
+    return FMX_OK;
+}
+
+// One launch sequence: piece k of a call (fmx_plan.h plan_call), n input samples at d_iq, its frames to d_pcm, on `s`.  A piece of an overlapping call runs its
+// stage A on the handle's stream pipe_sA, behind what the caller's stream held when the call began; FMX_CALL_PIECES_SERIAL=1 (a diagnostic) runs the same
+// pieces one after the other on `s` -- what the overlapping run must equal bit for bit.
+int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, float2 *d_pcm, hipStream_t s, int k, bool overlapped, int64_t *n_frames) {
+    bool capture = false;
+    int rc = promotion_turn(h, k == 0, s, &capture);
+    if (rc || (rc = flush_mailbox(h))) return rc;
     CallGeom G{};
     frames_geom(h, n, &G);
     G.ring_mask = h->ring - 1; G.dring_mask = h->dring - 1; G.sring_mask = h->sring - 1;
-    G.input_rate = h->cfg.inputRate; G.pitch = h->pitch; G.streams_private = (h->streams_private && h->twins == 1) ? 1 : 0; G.twins = h->twins; G.channels = h->channels; G.stream_stride = stream_stride; G.pcm_stride = pcm_stride;
-    G.iq_format = fmt; G.iq_scale = (fmt == 3) ? 1.0f / s16_den : 1.0f / 128.0f; G.n_cus = h->n_cus;
+    G.input_rate = h->cfg.inputRate; G.pitch = h->pitch; G.streams_private = (h->streams_private && h->twins == 1) ? 1 : 0; G.twins = h->twins; G.channels = h->channels; G.stream_stride = a.stream_stride; G.pcm_stride = a.pcm_stride;
+    G.iq_format = a.fmt; G.iq_scale = (a.fmt == 3) ? 1.0f / a.s16_den : 1.0f / 128.0f; G.n_cus = h->n_cus; G.streams = h->streams;
     const int64_t frames = conv2_out(h, G.M1) - conv2_out(h, G.M0);
-    if (frames > pcm_stride) return fail(FMX_E_TOO_LARGE, "pcm_stride smaller than the frames this call produces");
     if (h->rds_alloc && any_rds_on(h) && G.J1 - G.J0 > RDS_BLK)
         return fail(FMX_E_TOO_LARGE, "with RDS on, a call may cover at most 32000 fm samples (384000 input samples)");
-    // (a piece of an overlapping call: stage A on its own stream, behind what the caller's stream held when the call began)
-    // (FMX_CALL_PIECES_SERIAL=1, a diagnostic: the same pieces one after the other on the caller's stream -- what the overlapping run must equal bit for bit)
-    const bool piped = pp != nullptr && !h->ola_mode && !env_switches().pieces_serial;
+    const bool piped = overlapped && !h->ola_mode && !env_switches().pieces_serial;
     hipStream_t sa = piped ? h->pipe_sA : s;
     G.host_count1 = piped ? h->my_count_host + 1 : 0;
     ProfRec pr{}; const bool prof = h->prof_on;
@@ -1183,156 +1174,77 @@ int run_call_one(fmx_handle h, const void *d_iq, int32_t fmt, float s16_den, int
     }
     g_launch_err = hipSuccess;
     h->B.lin_rows = (int32_t)h->work_nj;
-    if (capture && h->tail_iq && h->promo_have + n > h->tail_cap) capture = false;      // (cannot happen: a change is applied at the first call boundary behind PROMO_TAIL_IN samples)
-    if (capture) {
-        if (!h->tail_iq) {
-            h->tail_cap = PROMO_TAIL_IN + h->cfg.max_block;
-            HIPCHK(hipMalloc(&h->tail_iq, sizeof(float2) * (size_t)h->streams * h->tail_cap));
-            HIPCHK(hipMalloc(&h->tail_snap, sizeof(FrontSnap) * (size_t)h->channels));
-            h->tail_ptrs.push_back(h->tail_iq); h->tail_ptrs.push_back(h->tail_snap);
-        }
-        if (h->promo_have == 0) { h->promo_g0 = h->g_total; launch_promo_state(h->B.state, h->tail_snap, h->channels, 0, sa); FMX_LAUNCHED(); }
-        launch_capture(d_iq, fmt, G.iq_scale, stream_stride, n, h->streams, h->tail_iq, h->tail_cap, h->promo_have, sa); FMX_LAUNCHED();
-        h->promo_have += n;
-    }
-    rc = front_parts_for(h, G);
-    if (rc) return rc;
-    {
-        const int fk = h->front_kernel.load() ? h->front_kernel.load() : env_switches().front_kernel;     // (the environment: A/B runs of one build)
-        // automatic: the filter on the matrix pipe wherever a handle qualifies and has the channels to fill the chip without splitting them in time
-        // (measured at 4096 channels on one box: 1.52 ms per launch against 1.75 for the four-wave kernel and 1.84 for the six-wave VALU kernel, which
-        // both sit at the packed-FMA power limit)
-        // (the complex-tap variant runs one channel per workgroup: a handle of one channel per compute unit fills the chip)
-        if (h->front4_ok && !h->front4_lo && (fk == 3 || (fk == 0 && G.parts <= 1))) { G.parts = 1; G.front4 = 1; }
-        if (h->front4_ok && h->front4_lo && (fk == 3 || (fk == 0 && h->channels >= h->n_cus))) { G.parts = 1; G.front4 = 2; }
-        // (what is reported is what runs: a call without a whole tile on the kernel's grid goes to front_kernel in launch_front)
-        h->last_front_kernel = (G.front4 && front4_tiles(G, d_iq) > 0) ? 3 : 1;
-    }
-    if (h->ola_mode) {
-        // RF DC removal / balance / LO mix per sample, the input filter as the reference's block machine, then the decimators
-        rc = ola_input_side(h, G, h->B, d_iq, s); if (rc) return rc;
-        CallGeom Gp = G; Gp.pre_processed = 1; Gp.iq_format = 0; Gp.iq_scale = 1.0f; Gp.stream_stride = h->cfg.max_block; Gp.streams_private = h->twins == 1 ? 1 : 0;
-        launch_front(h->T, h->B, Gp, h->d_u, h->channels, s);
-    } else
-    launch_front(h->T, h->B, G, d_iq, h->channels, sa);   // stage A: four waves per channel, packed-FMA FIR (fmx_front.hip)
-    FMX_LAUNCHED();
-    const bool prof_double = env_switches().prof_double != 0;    // (diagnostic: a throw-away event in front of each boundary event)
-    if (prof && prof_double && !h->ev_dummy) HIPCHK(hipEventCreate(&h->ev_dummy));      // (one per handle, destroyed with it)
-    hipEvent_t pdummy = h->ev_dummy;
-    if (prof && prof_double) HIPCHK(hipEventRecord(pdummy, sa));
+    if (capture && (rc = capture_samples(h, d_iq, a, G, sa))) return rc;
+    if ((rc = stage_a(h, G, d_iq, s, sa))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[1], sa));
     G.stageb_form = h->stageb_form.load(); G.no_deemph = h->ola_mode ? 1 : 0;
-    // A plain batch (no pre-pass, no RDS, no scope-tap rows: stage B as the whole kernel, three workgroups per CU) of more channels than one round of stage-B
-    // workgroups: stages B and C run as TWO CHANNEL GROUPS on two streams.  Stage B is bound by instruction issue and leaves its last round of workgroups partly
-    // filled (4096 channels are 5.33 rounds of 768); stage C moves the d ring and the PCM.  With the second group's stage B finished while the first group's still
-    // runs, its stage C fills what stage B leaves free: 3.48 -> 3.32 ms per step at 4096 channels.  Stage A stays one launch with the chip to itself -- the stage the
-    // roofline line is measured on.  The groups touch disjoint channels (CallGeom::ch0 / ch_count); the caller's stream goes on behind both.  FMX_TAIL_SPLIT=0: off.
-    int tail_ch = 0;
-    {
-        const bool tail_on = env_switches().tail_split != 0;
-        const int slots = 3 * (h->n_cus > 0 ? h->n_cus : 256);
-        const bool plain = !piped && !h->ola_mode && !h->B.w_iq && !h->cv_nt && !h->B.rows_on && !(h->rds_alloc && any_rds_on(h)) && !h->gain_pending && G.stageb_form == 0 &&
-                           env_switches().stageb_split < 0 && G.J1 > G.J0 && G.M1 > G.M0;
-        if (tail_on && plain && h->channels > slots) {
-            // (the first group: 2304 of 4096 channels on 256 CUs -- three whole rounds.  Measured there, second group of 256 / 512 / 1024 /
-            // 1792 / 2048 / 3072 channels: 3.47 / 3.45 / 3.35 / 3.32 / 3.39 / 3.43 ms per step against 3.47-3.55 with one group.  FMX_TAIL_CH=n: a diagnostic)
-            // other counts, one group -> two, ms per step: 3840 (2304 + 1536) 3.20 -> 3.12, 3000 (2304 + 696) 2.51 -> 2.43 (1536 + 1464: 2.51), 2048 (1536 + 512)
-            // 1.68 -> 1.63, 1536 (768 + 768) 1.30 -> 1.27, 1024 (768 + 256) 0.915 -> 0.910: the first group is two thirds of the rounds, in whole rounds
-            int first_rounds = (int)(0.65 * (double)h->channels / (double)slots + 0.5);
-            if (first_rounds < 1) first_rounds = 1;
-            tail_ch = h->channels - first_rounds * slots;
-            const int force = env_switches().tail_ch;
-            if (force > 0 && force < h->channels) tail_ch = force;
-            if (tail_ch < TAIL_MIN_CHANNELS) tail_ch = 0;             // (a second group of a few dozen channels is three launches for nothing)
-            if (tail_ch > 0) { const int rc2 = ensure_pipe_streams(h); if (rc2) return rc2; }
-        }
-        h->last_second_group = tail_ch;
-    }
-    if (piped) { HIPCHK(hipEventRecord(h->pipe_evA, sa)); HIPCHK(hipStreamWaitEvent(s, h->pipe_evA, 0)); }      // (stage B of this piece behind its stage A)
-    if (piped) {
-        // the pre-pass of this piece: its parallel part (disc_kernel) behind the piece's stage A on that stream -- and behind the stage B that read the half
-        // of the work arrays it is about to overwrite --, the recurrences on theirs, the noise squelch's pipeline and stage B on `s`
-        if (pp->k >= 2) HIPCHK(hipStreamWaitEvent(sa, h->pipe_evB[pp->k & 1], 0));
-        DeviceBuffers Bk = h->B;
-        if (pp->k & 1) { const size_t off = (size_t)((h->work_nj / 2) & ~(int64_t)15) * (size_t)h->pitch; Bk.w_iq += off; Bk.w_osc += off; }
-        const PrepassStreams ps{sa, h->pipe_sP, h->pipe_evD, h->pipe_evP};
-        launch_demod_fused(h->T, Bk, G, h->channels, s, &ps);
-        HIPCHK(hipEventRecord(h->pipe_evB[pp->k & 1], s));
-    } else if (tail_ch > 0) {
-        // (the second group on the handle's side stream, behind stage A)
-        HIPCHK(hipEventRecord(h->pipe_evA, s)); HIPCHK(hipStreamWaitEvent(h->pipe_sA, h->pipe_evA, 0));
-        CallGeom G1 = G, G2 = G;
-        G1.ch0 = 0; G1.ch_count = h->channels - tail_ch; G2.ch0 = h->channels - tail_ch; G2.ch_count = tail_ch;
-        launch_demod_fused(h->T, h->B, G1, h->channels, s);
-        launch_demod_fused(h->T, h->B, G2, h->channels, h->pipe_sA);
-    } else
-    launch_demod_fused(h->T, h->B, G, h->channels, s);      // (with its pre-pass for the PLL / AM decoders and the squelches)
-    if (G.J1 > G.J0) {       // (stage B's bookkeeping behind the call, fmx_stageb.hip)
-        int cnt = h->my_count_host + (int)(G.J1 - G.J0);
-        if (cnt > (SINCOS_N >> 1)) cnt -= (SINCOS_N >> 1) + 1;
-        h->my_count_host = cnt;
-    }
-    if (h->rds_alloc && any_rds_on(h)) {
-        const int64_t nj = G.J1 - G.J0;
-        int modes = 0;
-        for (int c = 0; c < h->channels; c++) {
-            const int m = h->call_rds_mode[(size_t)c];
-            modes |= 1 << m;
-            h->rds_nc0[(size_t)c] = m != 0 ? h->rds_nc[(size_t)c] : -1;
-        }
-        // (pageable source: the copy is staged before the call returns, the vector is free again)
-        HIPCHK(hipMemcpyAsync(h->d_rds_nc0, h->rds_nc0.data(), sizeof(int64_t) * (size_t)h->channels, hipMemcpyHostToDevice, s));
-        launch_rds(h->B, h->R, G, h->channels, h->rds_nc0.data(), modes, s);
-        for (int c = 0; c < h->channels; c++) {
-            const int64_t a = h->rds_nc0[(size_t)c];
-            if (a < 0) { h->last_m0[(size_t)c] = h->last_m1[(size_t)c]; continue; }       // (decoder off in this call: no outputs, not the last on-call's)
-            h->last_m0[(size_t)c] = a / 8; h->last_m1[(size_t)c] = (a + nj) / 8;
-            h->rds_nc[(size_t)c] = a + nj;
-        }
-    }
-    if (prof && prof_double) HIPCHK(hipEventRecord(pdummy, s));
+    // a plain batch (no pre-pass, no RDS, no scope-tap rows: stage B as the whole kernel) runs stages B and C as two channel groups on two streams where it has
+    // more channels than one round of stage-B workgroups (second_group_channels); FMX_TAIL_SPLIT=0: one group
+    const bool plain = !piped && !h->ola_mode && !h->B.w_iq && !h->cv_nt && !h->B.rows_on && !(h->rds_alloc && any_rds_on(h)) && !h->gain_pending && G.stageb_form == 0 &&
+                       G.J1 > G.J0 && G.M1 > G.M0;
+    const int second = env_switches().tail_split && plain ? second_group_channels(h->channels, h->n_cus) : 0;
+    if (second > 0 && (rc = ensure_pipe_streams(h))) return rc;
+    h->last_second_group = second;
+    if ((rc = stage_b(h, G, k, piped, second, s, sa))) return rc;
+    if (h->rds_alloc && any_rds_on(h) && (rc = stage_rds(h, G, s))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[2], s));
-    DeviceBuffers Bq = h->B;
-    if (h->ola_mode && G.J1 > G.J0) {
-        // the audio low-pass as the reference's block machine on the de-emphasised stream; the resampler reads its output
-        OlaBuffers O{}; O.src = h->B.dring; O.dst = h->d2ring; O.src_stride = O.dst_stride = h->dring; O.src_mask = O.dst_mask = h->dring - 1;
-        O.src_pos = O.dst_pos = G.J0;
-        HStep st1;
-        // de-emphasis behind the filter, as the reference orders them (:589-595)
-        if (ola_single_step(h, h->ola_au, G.J1 - G.J0, &st1)) {
-            OlaStepRef ref; rc = step_ref(h, st1, s, &ref); if (rc) return rc;
-            ola_fill(h->ola_au, O);
-            launch_deemph(h->B, G, h->d2ring, h->channels, s, &ref, &O); FMX_LAUNCHED();
-            ola_finish_single(h, h->ola_au, st1, ref, O, s);
-        } else {
-            rc = run_ola(h, h->ola_au, O, G.J1 - G.J0, s); if (rc) return rc;
-            launch_deemph(h->B, G, h->d2ring, h->channels, s, nullptr, nullptr); FMX_LAUNCHED();
-        }
-    }
-    if (h->ola_mode) Bq.dring = h->d2ring;
-    if (h->gain_pending && G.M1 > G.M0) { G.gain_fix = 1; launch_gain_fix(h->T, Bq, G, h->channels, s); FMX_LAUNCHED(); h->gain_pending = false; }
-    if (tail_ch > 0) {
-        CallGeom G1 = G, G2 = G;
-        G1.ch0 = 0; G2.ch0 = h->channels - tail_ch;
-        launch_audio(h->T, Bq, G1, d_pcm, h->channels - tail_ch, s);
-        launch_audio(h->T, Bq, G2, d_pcm, tail_ch, h->pipe_sA);
-        HIPCHK(hipEventRecord(h->pipe_evE, h->pipe_sA)); HIPCHK(hipStreamWaitEvent(s, h->pipe_evE, 0));
-    } else if (!h->cv_nt) launch_audio(h->T, Bq, G, d_pcm, h->channels, s);
-    else {
-        // the audio stage writes its 48 kHz frames behind the converter's history; theConverter's output goes to the caller
-        CallGeom G48 = G; G48.pcm_stride = h->x48_stride;
-        launch_audio(h->T, Bq, G48, h->d_x48 + h->cv_nt, h->channels, s);
-        launch_conv2(h->d_x48, h->x48_stride, h->d_cv_taps, h->cv_p, h->cv_q, h->cv_nt, G.M0, G.M1 - G.M0, conv2_out(h, G.M0), frames,
-                     d_pcm, pcm_stride, h->channels, s);
-    }
+    if ((rc = stage_c(h, G, d_pcm, frames, second, s))) return rc;
     if (prof) { HIPCHK(hipEventRecord(pr.e[3], s)); h->prof.push_back(pr); }
     FMX_LAUNCHED();
     HIPCHK(g_launch_err);
     actions_consumed(h, G.J1 > G.J0);
     h->last_J0 = G.J0; h->last_J1 = G.J1;
     h->g_total += n;
-    h->call_head = false;
     if (n_frames) *n_frames = frames;
+    return FMX_OK;
+}
+
+// One fmx_process_* call: checked, planned (fmx_plan.h plan_call: whole, in RDS pieces, or in overlapping pre-pass pieces), and run piece by piece.
+int run_call(fmx_handle h, const void *d_iq, int32_t fmt, float s16_den, int64_t stream_stride, int64_t n, float2 *d_pcm,
+             int64_t pcm_stride, int64_t *n_frames, hipStream_t s) {
+    h->last_pieces = 1;
+    int rc = check_call(h, fmt, s16_den, n, pcm_stride);
+    if (rc) return rc;
+    CallShape cs{};
+    {   // (the settings as they stand now; the pieces' own decisions read what their flush_mailbox takes)
+        std::lock_guard<std::mutex> lk(h->mtx);
+        for (auto &p : h->params) { cs.any_rds |= p.rds_mode != 0; cs.prepass |= p.decoder == 2 || p.decoder == 1 || p.squelch_mode != 0; cs.pllc |= p.decoder == 2 || p.decoder == 1; cs.am |= p.decoder == 1; }
+    }
+    // (the pre-pass's work arrays are allocated before the call is cut: the first call of such a batch runs in pieces too)
+    if (!cs.any_rds && cs.prepass && !h->ola_mode && (rc = ensure_prepass_arrays(h))) return rc;
+    cs.n = n; cs.decim = h->decim; cs.call_pieces = h->pipe_rows.load(); cs.channels = h->channels; cs.ola_mode = h->ola_mode; cs.conv2 = h->cv_nt != 0;
+    cs.prepass_arrays = h->B.w_iq != nullptr; cs.half = prepass_half(h->work_nj);
+    const CallPlan plan = plan_call(cs);
+    // A batch whose channels need the demodulator pre-pass (PLL / AM decoder, a squelch: fmx_demod.hip).  Its recurrences are one wave per 64 channels walking
+    // the call's fm samples one after the other -- 64 waves on 1024 SIMDs at 4096 channels, for longer than stages A, B and C together take -- and nothing else
+    // can run meanwhile: stage B waits for its output, it waits for stage A.  Such a call is made in OVERLAPPING PIECES (the chain is invariant to how a stream
+    // is cut into calls) on three streams: stage A of piece k + 1 and stage B / C of piece k - 1 fill the chip while the pre-pass walks piece k.  The pre-pass's
+    // work arrays alternate between two halves of their allocation; an event per stage boundary orders the rest.  What the stages share beyond their hand-over
+    // arrays: the myCount of the metaData snapshot (kept by stage B, read by the pre-pass: handed over by the host, CallGeom::host_count1) and the RF DC level
+    // stage B's snapshot reads from stage A's state (a display value that moves by 1e-7 of its distance per sample: it may be the next piece's).
+    const bool overlapped = plan.kind == CallKind::OVERLAPPED;
+    hipStream_t ps = s;
+    if (overlapped) {
+        if ((rc = ensure_pipe_streams(h))) return rc;
+        // the pieces run on the handle's three streams, behind what the caller's stream held when the call began; the caller's stream goes on behind the last of them
+        HIPCHK(hipEventRecord(h->pipe_ev0, s));
+        HIPCHK(hipStreamWaitEvent(h->pipe_sA, h->pipe_ev0, 0)); HIPCHK(hipStreamWaitEvent(h->pipe_sB, h->pipe_ev0, 0));
+        ps = h->pipe_sB;
+    }
+    const CallArgs a{fmt, s16_den, stream_stride, pcm_stride};
+    const int64_t bps = bytes_per_sample(fmt);
+    int64_t pos = 0, total = 0;
+    for (size_t k = 0; k < plan.lens.size(); k++) {
+        int64_t got = 0;
+        rc = run_piece(h, a, reinterpret_cast<const char *>(d_iq) + pos * bps, plan.lens[k], d_pcm + total, ps, (int)k, overlapped, &got);
+        if (rc) { if (overlapped) (void)hipDeviceSynchronize(); return rc; }
+        pos += plan.lens[k]; total += got;
+    }
+    if (overlapped) {
+        HIPCHK(hipEventRecord(h->pipe_evE, h->pipe_sB)); HIPCHK(hipStreamWaitEvent(s, h->pipe_evE, 0));
+        h->last_pieces = (int)plan.lens.size();
+    }
+    if (n_frames) *n_frames = total;
     return FMX_OK;
 }
 
@@ -1352,21 +1264,6 @@ int prof_drain(fmx_handle h) {
 }
 
 }  // namespace
-
-namespace fmx {
-const EnvSwitches &env_switches() {
-    static const EnvSwitches sw = [] {
-        EnvSwitches e{};
-        e.call_pieces = env_int("FMX_CALL_PIECES", -1); e.call_pieces_ends = env_int("FMX_CALL_PIECES_ENDS", -1);
-        if (const char *v = getenv("FMX_CALL_PIECES_LIST")) { for (const char *q = v; *q;) { e.call_pieces_list.push_back(atoi(q)); while (*q && *q != ',') q++; if (*q) q++; } } e.pieces_serial = env_int("FMX_CALL_PIECES_SERIAL", 0) != 0; e.front_kernel = env_int("FMX_FRONT_KERNEL", 0);
-        e.prof_double = getenv("FMX_PROF_DOUBLE") != nullptr; e.tail_split = env_int("FMX_TAIL_SPLIT", 1) != 0; e.tail_ch = env_int("FMX_TAIL_CH", 0);
-        e.stageb_split = env_int("FMX_STAGEB_SPLIT", -1); e.rows_off_split = getenv("FMX_ROWS_OFF_SPLIT") != nullptr; e.no_sinpoly = getenv("FMX_DEBUG_NO_SINPOLY") != nullptr;
-        e.host_zerocopy = env_int("FMX_HOST_ZEROCOPY", 1) != 0; e.rds_pair = env_int("FMX_RDS_PAIR", 1) != 0;
-        return e;
-    }();
-    return sw;
-}
-}  // namespace fmx
 
 // ---- diagnostics: the practical HBM ceiling (SURVEY 8d asks for the measured device-copy bandwidth next to the nominal 8 TB/s)
 namespace fmx {
@@ -1501,7 +1398,7 @@ int fmx_create(const fmx_config *cfg, fmx_handle *out) {
                 if (std::memcmp(&sn, &sc[i].y, 4) != 0) { if (sp.ns < 4) { sp.s_idx[sp.ns] = i; sp.s_val[sp.ns] = sc[i].y; sp.ns++; } else fits = false; }
                 if (std::memcmp(&cs, &sc[i].x, 4) != 0) { if (sp.nc < 4) { sp.c_idx[sp.nc] = i; sp.c_val[sp.nc] = sc[i].x; sp.nc++; } else fits = false; }
             }
-            sp.ok = (fits && !env_switches().no_sinpoly) ? 1 : 0;
+            sp.ok = fits ? 1 : 0;
             h->T.sp = sp;
         }
         {   // 2-level factorisation of the sine column for the sequential pilot PLL (LDS resident):
@@ -1682,7 +1579,6 @@ int fmx_destroy(fmx_handle h) {
     for (hipStream_t st : {h->pipe_sA, h->pipe_sP, h->pipe_sB}) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     for (hipEvent_t e : {h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
     if (h->ev_in) (void)hipEventDestroy(h->ev_in);
-    if (h->ev_dummy) (void)hipEventDestroy(h->ev_dummy);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return FMX_OK;
@@ -1803,11 +1699,8 @@ int64_t fmx_filter_change_due(fmx_handle h) {
 
 int64_t fmx_frames_for(fmx_handle h, int64_t n) {
     if (!h || n < 0) return -1;
-    CallGeom G{}; frames_geom(h, n, &G);
-    return conv2_out(h, G.M1) - conv2_out(h, G.M0);
+    return call_frames(h, n);
 }
-
-static int bytes_per_sample(int32_t fmt) { return fmt == FMX_IQ_F32 ? 8 : (fmt == FMX_IQ_S16 ? 4 : 2); }
 
 int fmx_process_device_raw(fmx_handle h, const void *d_iq, int32_t format, float s16_den, int64_t stream_stride, int64_t n,
                            float *d_pcm, int64_t pcm_stride, int64_t *n_frames, void *hip_stream) {
@@ -1833,9 +1726,8 @@ int fmx_process_device(fmx_handle h, const float *d_iq, int64_t stream_stride, i
 int fmx_process_host_raw(fmx_handle h, const void *iq, int32_t format, float s16_den, int64_t stream_stride, int64_t n,
                          float *pcm, int64_t pcm_stride, int64_t *n_frames) {
     if (!h || !iq || !pcm) return fail(FMX_E_INVALID, "null argument");
-    if (format < 0 || format > 3) return fail(FMX_E_INVALID, "unknown IQ format");
     if (stream_stride < n) return fail(FMX_E_INVALID, "stream_stride < n_complex");
-    if (n <= 0 || n > h->cfg.max_block) return fail(FMX_E_TOO_LARGE, "n_complex must be in [1, max_block]");
+    if (const int rc = check_call(h, format, s16_den, n, pcm_stride)) return rc;     // (pcm_stride: the caller's buffer; run_call checks the staging buffer's)
     HIPCHK(hipSetDevice(h->cfg.device));
     const int64_t cap = conv2_out(h, h->cfg.max_block / (4 * h->decim) + 96) + 2;
     if (!h->d_iq) {
@@ -1843,16 +1735,13 @@ int fmx_process_host_raw(fmx_handle h, const void *iq, int32_t format, float s16
         HIPCHK(hipMalloc(&h->d_pcm, sizeof(float2) * (size_t)h->channels * cap));
         h->pcm_cap = cap;
     }
-    const int64_t frames = fmx_frames_for(h, n);
-    if (frames > pcm_stride) return fail(FMX_E_TOO_LARGE, "pcm_stride smaller than the frames this call produces");
     const size_t bps = (size_t)bytes_per_sample(format);
     // The single receiver's call (one stream, 16384 samples: 128 KB in, 2.7 KB out) spends a third of its time in the two copies' fixed costs
     // (a pageable buffer is staged by the runtime, each copy is a submission of its own).  Small calls go through pinned, device-visible
     // memory instead: the samples are copied there by the CPU and READ BY STAGE A over the bus, the PCM is written there by stage C.
-    const bool zc_env = env_switches().host_zerocopy != 0;
     constexpr size_t ZC_MAX_IN = (size_t)1 << 20;
     const size_t in_bytes = bps * (size_t)n * (size_t)h->streams;
-    if (zc_env && in_bytes <= ZC_MAX_IN && (size_t)h->channels * (size_t)cap * sizeof(float2) <= ZC_MAX_IN) {
+    if (in_bytes <= ZC_MAX_IN && (size_t)h->channels * (size_t)cap * sizeof(float2) <= ZC_MAX_IN) {
         if (!h->hp_pcm) {
             HIPCHK(hipHostMalloc(&h->hp_iq, ZC_MAX_IN, hipHostMallocDefault)); h->hp_iq_bytes = ZC_MAX_IN;
             HIPCHK(hipHostMalloc((void **)&h->hp_pcm, sizeof(float2) * (size_t)h->channels * cap, hipHostMallocDefault)); h->hp_pcm_cap = cap;

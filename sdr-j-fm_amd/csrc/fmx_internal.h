@@ -2,10 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "fmx_plan.h"
 
 namespace fmx {
 
-constexpr int DECIM = 12;              // inputRate / fmRate (2304000 / 192000)
 constexpr int A_TILE_COLS = 256;       // front-end tile: 256 fm-rate outputs = 3072 input samples
 constexpr int A_HIST_COLS = 25;        // history columns kept per channel (>= max taps/12 + 1)
 constexpr int A_MAX_ND = 25;           // tap columns: 287 taps at off=6 -> 25 columns of 12
@@ -236,7 +236,7 @@ struct CallGeom {
     int32_t cont;            // front_kernel: this launch continues a call whose head another launch has made (the one-shot actions are done)
     int32_t ch_count;        // stage B: workgroups of the launch (0: one per channel of the handle); with ch0:
     int32_t ch0;             // stage B / C: the launch covers the channels ch0 ... ch0 + ch_count - 1 (stage C: + its channel argument - 1) (a batch whose last round of stage-B workgroups
-                             // would leave the chip two thirds empty gives that round to a second stream: fmx_api.hip run_call_one); 0 everywhere else
+                             // would leave the chip two thirds empty gives that round to a second stream: fmx_api.hip run_piece); 0 everywhere else
     int32_t host_count1;     // != 0: the demodulator pre-pass takes the reference's myCount (fm-processor.cpp:662) in front of this call from here (the count
                              // + 1) instead of the channel state -- a call made in overlapping pieces (fmx_api.hip: run_call), where the previous piece's
                              // stage B, which keeps the count, may still be running
@@ -341,7 +341,6 @@ void launch_promo_hist(float2 *hist, const float2 *u, int64_t u_stride, int64_t 
 void launch_promo_inv_deemph(const float2 *dring, int dmask, int64_t J0, int NA, const ChanParams *params, float2 *out, int channels, hipStream_t s);
 
 // ---- RDS path (fmx_rds.hip) -------------------------------------------------------------------
-constexpr int RDS_BLK = 32000;              // overlap-add block of the two 32768-pt filters (fft-filters.cpp:34)
 constexpr int RDS_PHASE_RING = 131072;      // pilot-phase delay line (>= 64000 + one block + one call)
 constexpr int RDS24_RING = 8192;            // 24 kS/s decimator output ring
 constexpr int RDS_BITS_CAP = 8192;          // per-channel bit ring (>= 6 s of bits)
@@ -409,26 +408,8 @@ int front4_tiles(const CallGeom &G, const void *iq);
 void launch_front4(const DeviceTables &T, const DeviceBuffers &B, const CallGeom &G, const void *iq, int channels, hipStream_t s);
 // fmx_front4lo.hip: the same kernel with complex taps, one channel per workgroup (CallGeom::front4 == 2: some channel of the handle has a local oscillator)
 void launch_front4_lo(const DeviceTables &T, const DeviceBuffers &B, const CallGeom &G, const void *iq, int channels, hipStream_t s);
-// The FMX_* environment switches (diagnostics and A/B runs of one build; none is needed by a user): read ONCE, by the first fmx_create of the process --
-// nothing on the per-call path asks the environment.
-struct EnvSwitches {
-    int call_pieces;      // FMX_CALL_PIECES: fm samples per piece of an overlapping call (-1: the handle's setting)
-    int call_pieces_ends; // FMX_CALL_PIECES_ENDS: fm samples of such a call's first and last piece (-1: the library's choice)
-    std::vector<int> call_pieces_list;   // FMX_CALL_PIECES_LIST=a,b,c: the pieces' fm samples spelt out (a diagnostic)
-    int pieces_serial;    // FMX_CALL_PIECES_SERIAL=1: the same pieces one after the other on the caller's stream
-    int front_kernel;     // FMX_FRONT_KERNEL: stage-A kernel where the handle says automatic
-    int prof_double;      // FMX_PROF_DOUBLE: a throw-away event in front of each profiling event
-    int tail_split;       // FMX_TAIL_SPLIT=0: stages B and C as one channel group
-    int tail_ch;          // FMX_TAIL_CH=n: channels of the second group
-    int stageb_split;     // FMX_STAGEB_SPLIT=0 / 1: stage B as one kernel / two (-1: the round arithmetic)
-    int rows_off_split;   // FMX_ROWS_OFF_SPLIT: the round arithmetic also for batches that keep no scope-tap rows
-    int no_sinpoly;       // FMX_DEBUG_NO_SINPOLY: the SinCos table from memory
-    int host_zerocopy;    // FMX_HOST_ZEROCOPY=0: fmx_process_host through staged copies
-    int rds_pair;         // FMX_RDS_PAIR=0: one channel per RDS block transform
-};
-const EnvSwitches &env_switches();
 // first HIP error of the launches / event calls of the current fmx_process_* call (they are enqueued by void helpers);
-// run_call clears it before the launches and turns it into FMX_E_HIP behind them
+// run_piece clears it before the launches and turns it into FMX_E_HIP behind them
 extern thread_local hipError_t g_launch_err;
 inline void note_hip(hipError_t e) { if (e != hipSuccess && g_launch_err == hipSuccess) g_launch_err = e; }
 #define FMX_LAUNCHED() ::fmx::note_hip(hipGetLastError())

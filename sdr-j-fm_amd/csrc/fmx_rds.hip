@@ -724,9 +724,8 @@ __global__ void rds_hil_split(const float2 *__restrict__ Z, const float2 *__rest
 // of their own count), Hilbert of the previous BP result.  Every channel of the handle at once: pairs of channels per transform; a subset (channels
 // that joined at different times): one channel per transform, by list.  Both forms keep their overlap tails by block parity.
 void launch_rds_block(const RdsBuffers &Rb, int C, int64_t blk, const int *h_list, int nlist, hipStream_t s) {
-    const bool pair = env_switches().rds_pair != 0;
     const size_t ov = (size_t)C * RDEG;                           // one parity of an overlap buffer
-    if (pair && C >= 2 && nlist == C) {
+    if (C >= 2 && nlist == C) {
         const int P = (C + 1) / 2;
         const dim3 gp(RN / 256, P);
         // Hilbert of the previous band-pass result: pairs forward straight from the real blocks (rows of V, U as scratch), apart into U,

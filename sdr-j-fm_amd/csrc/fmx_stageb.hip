@@ -51,12 +51,13 @@ namespace fmx {
 #define SB_FTW(k) do { } while (0)
 #endif
 
-constexpr int FB_T = 256, FB_K = 6, FB_W = FB_T * FB_K;        // threads, samples per thread, segment length
+constexpr int FB_T = 256, FB_W = STAGEB_SEG, FB_K = FB_W / FB_T;   // threads, segment length, samples per thread
+static_assert(FB_K * FB_T == FB_W, "a thread's samples tile the segment");
 static_assert(FB_T == fftc::T, "the convolution is written for the workgroup size");
 static_assert(FB_W <= PSS_DELAY, "a segment's PSS errors must only need s-ring entries of earlier segments");
 constexpr int PSS_MAX_ROUNDS = 64;
 #ifndef SB_WG_PER_SIMD
-#define SB_WG_PER_SIMD 3
+#define SB_WG_PER_SIMD STAGEB_WG_PER_CU
 #endif
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1602,21 +1603,9 @@ void launch_demod_fused(const DeviceTables &T, const DeviceBuffers &B, const Cal
     if (G.J1 - G.J0 <= 0) return;
     if (B.w_iq) launch_demod_prepass(T, B, G, C, s, ps);     // some channel has (had) a PLL / AM decoder or a squelch: fmx_demod.hip
     StageBArgs A; A.T = T; A.B = B; A.G = G; A.C = C;
-    // One kernel or two?  Per channel both forms cost the same (measured, 256 ... 4096 channels: the kernel is bound by instruction
-    // issue, a fourth workgroup per CU adds nothing), what differs is the tail: the whole kernel runs 3 workgroups per CU, its halves 4,
-    // and a batch that does not fill the last round of either leaves CUs idle.  The form whose rounds waste less wins; a tie goes to
-    // the single launch.  (4096 channels on 256 CUs: 5.33 rounds of 768 against 4 of 1024 -- 2.05 against 1.91 ms.)
-    // FMX_P_STAGEB_FORM (tests) or the environment (FMX_STAGEB_SPLIT=0 / 1: A/B runs of the bench) force either form.
-    // (the handle's own CU count rides in CallGeom: handles on different devices -- another SKU, another partition mode -- each do their own
-    // round arithmetic)
-    const int env = env_switches().stageb_split;
-    const int force = G.stageb_form ? G.stageb_form - 1 : env;
-    const int cus = G.n_cus > 0 ? G.n_cus : 256;
-    const long whole = (long)((C + SB_WG_PER_SIMD * cus - 1) / (SB_WG_PER_SIMD * cus)) * SB_WG_PER_SIMD * 100;
-    const long halves = (long)((C + 4 * cus - 1) / (4 * cus)) * 4 * 102;          // (two launches, the hand-over through HBM: 2 %)
-    // (a batch that keeps no scope taps and decodes no RDS: the whole kernel leaves the rows unwritten -- 0.63 GB per call at 4096 channels, and writes
-    // are the expensive direction on this GPU -- and is then the faster form where the halves were: 1.60 against 1.69 ms)
-    const bool split = force >= 0 ? force != 0 : (B.rows_on ? halves < whole : (env_switches().rows_off_split ? halves < whole : false));
+    // one kernel or two (fmx_plan.h).  (The handle's own CU count rides in CallGeom: handles on different devices -- another SKU, another partition
+    // mode -- each do their own round arithmetic)
+    const bool split = stageb_two_kernels(C, G.n_cus, B.rows_on != 0, G.stageb_form, SB_WG_PER_SIMD);
     const unsigned grid = (unsigned)(G.ch_count > 0 ? G.ch_count : C);       // (a launch for some of the channels: CallGeom::ch0)
     if (split) {
         hipLaunchKernelGGL(stageb_kernel<1>, dim3(grid), dim3(FB_T), 0, s, A); FMX_LAUNCHED();

@@ -464,7 +464,7 @@ def test_twins_under_runtime_changes(seed, channels, kinds, pieces, extra):
 
 
 def test_stages_b_and_c_as_two_channel_groups_equal_one_group():
-    """A plain batch of more channels than one round of stage-B workgroups runs stages B and C as two channel groups on two streams (fmx_api.hip run_call_one,
+    """A plain batch of more channels than one round of stage-B workgroups runs stages B and C as two channel groups on two streams (fmx_api.hip run_piece,
     fmx_last_second_group): 1100 channels on four programmes (768 + 332), four calls of uneven length, the first and the one behind a volume change made as one group (the gain correction runs) --
     against the same calls with FMX_TAIL_SPLIT=0, bit for bit; twins equal inside each run."""
     import os, subprocess, sys, tempfile

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One run of a plain batch (channel c on programme c % 4, device buffers) whose PCM and second-group size are saved: the GPU suite runs it with FMX_TAIL_SPLIT=0 and =1
-(stages B / C as one channel group and as two, fmx_api.hip run_call_one) and compares bit for bit.  usage: groups_check.py OUT.npz CHANNELS CALLS BLOCK"""
+(stages B / C as one channel group and as two, fmx_api.hip run_piece) and compares bit for bit.  usage: groups_check.py OUT.npz CHANNELS CALLS BLOCK"""
 import importlib, os, sys
 import numpy as np
 import torch
