@@ -156,6 +156,24 @@ typedef enum {
                                   -1 = automatic (default): 3840 (AM decoder) or 4608 (PLL decoder alone) with a short last piece (19200 fm samples are cut 4608 4608 4608 3840 1536)
                                   or 4608 (squelches only) for handles of 1024 channels and more, calls of two pieces and more, no RDS decoder on, no second converter;
                                   0 = never; n > 0: pieces of n fm samples (rounded up to 16) for any handle above 64 channels.  Takes effect at the next call. */
+    FMX_P_SCANNING = 28,       /* startScanning / stopScanning (fm-processor.cpp:361-367): 0 or 1, per channel.  While a channel scans, its fm-rate samples
+                                  (those of FMX_TAP_FM_IQ, the value behind fmBand_2 the reference puts into scanBuffer, :478-481) are collected in
+                                  blocks of 1024; every complete block goes through a 1024-point forward transform (Fft_transform, f32, no scaling)
+                                  and becomes one record of fmx_scan_results: get_db (getSignal) and get_db (getNoise) (:484-493, :886-904,
+                                  fm-constants.h:144) and whether their difference exceeds the threshold (the reference's scanresult ()).  A
+                                  channel's SCAN CARRY (the block being collected, 0..1023 samples) starts empty at fmx_create, is advanced by the
+                                  calls in which the channel scans only, and is never reset: a block may hold samples from before a pause and from
+                                  after it, as the reference's scanPointer (a local of run (), :377, untouched by start / stopScanning) does.
+                                  ONE DELIBERATE DIFFERENCE: the reference skips its demodulator and everything behind it while scanning (:494
+                                  `continue`); here the channel's chain -- stages B and C, the RDS path -- runs on, and its PCM frames of a scanning
+                                  call are written as zeros.  The channels of a handle share one sample and frame timeline, so a channel cannot skip
+                                  fm samples, and the result is exact: outside its scanning calls a channel that scanned is bit-identical to one that
+                                  never did.  So after a scan the chain continues from its running state, where the reference's continues from the
+                                  state it froze.  Taps, meta and peaks of a scanning channel report the running chain (the adapters hold them back
+                                  while scanning).  Takes effect at the next call. */
+    FMX_P_SCAN_THRESHOLD = 29, /* the constructor's thresHold (fm-processor.cpp:63,108; the GUI's ini key `threshold`, default 20, radio.cpp:912-913),
+                                  per channel, in dB: an integral value in -32768..32767 (int16_t), default 20.  A record takes the threshold of the
+                                  call that completed its block.  Takes effect at the next call. */
     /* actions (value ignored) */
     FMX_A_TRIGGER_FREQUENCY_CHANGE = 100, /* triggerFrequencyChange (:849-855) */
     FMX_A_RESTART_PSS = 101,              /* restartPssAnalyzer     (:857-860) */
@@ -188,6 +206,16 @@ typedef enum {
     FMX_TAP_RDS_IQ = 4,        /* complex @24 kS/s after rdsDecimator (RDS_INPUT scope, :566-569)        */
     FMX_TAP_PILOT_PHASE = 5,   /* float   @fmRate currentPilotPhase (:695; the value the RDS mixer's phase buffer takes, :747) */
 } fmx_tap_id;
+
+/* One record of scan mode (FMX_P_SCANNING): what the reference computes for every block of 1024 fm samples it scans (fm-processor.cpp:483-493) */
+typedef struct fmx_scan_result {
+    int64_t block;        /* the channel's scan-block number since fmx_create, from 0 (a gap = records dropped) */
+    int64_t end_sample;   /* fm-sample index (reference numbering, as FMX_TAP_FM_IQ) one past the block's last sample */
+    float   signal_db;    /* get_db (getSignal (X, 1024), 256) */
+    float   noise_db;     /* get_db (getNoise (X, 1024), 256) */
+    int32_t found;        /* signal_db - noise_db > threshold: where the reference emits scanresult () */
+    int32_t reserved;
+} fmx_scan_result;
 
 /* per-kernel timing collected with HIP events on the processing stream */
 typedef struct {
@@ -338,6 +366,10 @@ int64_t fmx_last_rds_samples(fmx_handle h);
  * (fm-processor.cpp:733-754, :551-553) -- so channels that switched their decoders on at different times divide by eight on different phases
  * and a call may give one of them an output more than another.  fmx_last_rds_samples is this for channel 0. */
 int64_t fmx_last_rds_samples_of(fmx_handle h, int32_t channel);
+
+/* replaces the scanresult () signal (fm-processor.h, emitted fm-processor.cpp:489-492): the records completed since the last read, oldest first, at most
+ * `capacity`; the library keeps the last 1024 per channel (a reader that fell behind sees the gap in `block`) */
+int  fmx_scan_results(fmx_handle h, int32_t channel, fmx_scan_result *out, int32_t capacity, int32_t *n_results);
 
 /* introspection used by the parity tests: the filter taps the kernels run with.
  * which: 0 front-end polyphase taps, 1 PSS low-pass, 2 audio+resampler FIR, 3 resampler alone,

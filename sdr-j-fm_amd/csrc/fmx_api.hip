@@ -4,6 +4,7 @@
 #include "../../include/fmx.h"
 #include "../../include/fmx_debug.h"
 #include "fmx_internal.h"
+#include "fmx_scan.h"
 #include "fmx_fftconv.h"
 #include "fmx_rdsgroups.h"
 #include "fmx_design.h"
@@ -62,6 +63,9 @@ struct ChanUser {
     std::vector<float2> delay = std::vector<float2>(1, make_float2(-40.0f, -40.0f));
     uint32_t delay_idx = 0;
     int32_t pk_read = 0;
+    // scan mode (FMX_P_SCANNING, FMX_P_SCAN_THRESHOLD): startScanning / stopScanning, the constructor's thresHold (fm-processor.cpp:63,108,361-367)
+    bool    scanning = false;
+    int16_t scan_thr = 20;
 };
 
 struct ProfRec { hipEvent_t e[4]; int64_t in_samples, ch_samples; int n; };
@@ -129,6 +133,14 @@ struct fmx_handle_s {
     // what a call needs of `params` beyond the device copy, taken under `mtx` by flush_mailbox: fmx_set_param may write `params` from another thread
     // while the processing thread enqueues the call
     std::vector<int8_t> call_rds_mode; bool call_any_rds = false;
+    // scan mode (fmx_scan.hip): the call's scanning channels and their thresholds (flush_mailbox); per channel the block being collected (fill), the blocks
+    // completed since fmx_create, the records handed out, and per record slot the fm sample behind the block and the threshold of the call that completed it
+    // (the device keeps (signal_db, noise_db) per slot); allocated by the first call in which a channel scans
+    std::vector<int32_t> call_scan; std::vector<int16_t> call_scan_thr;
+    bool scan_alloc = false;
+    float2 *d_scan_W = nullptr, *d_scan_carry = nullptr, *d_scan_rec = nullptr; ScanJob *d_scan_jobs = nullptr; int32_t *d_scan_mute = nullptr;
+    std::vector<ScanJob> scan_jobs;
+    std::vector<int32_t> scan_fill; std::vector<int64_t> scan_blocks, scan_read, scan_end; std::vector<int16_t> scan_rec_thr;
     std::atomic<int> stageb_form{0};     // FMX_P_STAGEB_FORM
     std::atomic<int> front_parts{0};     // FMX_P_FRONT_PARTS
     std::atomic<int> front_kernel{0};    // FMX_P_FRONT_KERNEL
@@ -796,6 +808,28 @@ int demote(fmx_handle h, hipStream_t s) {
 
 static bool any_rds_on(fmx_handle h) { return h->call_any_rds; }     // (as of the call's flush_mailbox)
 
+// scan mode's buffers (fmx_scan.hip), allocated by the first call in which a channel scans
+int ensure_scan(fmx_handle h) {
+    if (h->scan_alloc) return FMX_OK;
+    const size_t C = (size_t)h->channels;
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<float2> W((size_t)scan::N);
+    scan::make_twiddles(W.data());
+    HIPCHK(hipMalloc(&h->d_scan_W, sizeof(float2) * scan::N));
+    HIPCHK(hipMemcpy(h->d_scan_W, W.data(), sizeof(float2) * scan::N, hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&h->d_scan_carry, sizeof(float2) * C * scan::N));
+    HIPCHK(hipMemset(h->d_scan_carry, 0, sizeof(float2) * C * scan::N));
+    HIPCHK(hipMalloc(&h->d_scan_rec, sizeof(float2) * C * scan::RING));
+    HIPCHK(hipMemset(h->d_scan_rec, 0, sizeof(float2) * C * scan::RING));
+    HIPCHK(hipMalloc(&h->d_scan_jobs, sizeof(ScanJob) * C));
+    HIPCHK(hipMalloc(&h->d_scan_mute, sizeof(int32_t) * C));
+    for (void *p : {(void *)h->d_scan_W, (void *)h->d_scan_carry, (void *)h->d_scan_rec, (void *)h->d_scan_jobs, (void *)h->d_scan_mute}) h->tail_ptrs.push_back(p);
+    h->scan_fill.assign(C, 0); h->scan_blocks.assign(C, 0); h->scan_read.assign(C, 0);
+    h->scan_end.assign(C * scan::RING, 0); h->scan_rec_thr.assign(C * scan::RING, 0);
+    h->scan_alloc = true;
+    return FMX_OK;
+}
+
 constexpr int PLL_SEQ_AUTO_MAX = 64;   // FMX_P_PLL_SOLVER = 0: handles up to this many channels evaluate the pilot PLL sequentially
 
 // the tiled work arrays of the demodulator pre-pass (fmx_demod.hip): limited / unlimited samples in, demodulator output out.  (Allocated by the first call
@@ -861,6 +895,10 @@ int flush_mailbox(fmx_handle h) {
     h->call_rds_mode.resize((size_t)h->channels);
     for (int c = 0; c < h->channels; c++) { h->call_rds_mode[(size_t)c] = (int8_t)h->params[(size_t)c].rds_mode; any_rds |= (h->params[(size_t)c].rds_mode != 0); }
     h->call_any_rds = any_rds;
+    h->call_scan.clear(); h->call_scan_thr.clear();
+    for (int c = 0; c < h->channels; c++)
+        if (h->user[(size_t)c].scanning) { h->call_scan.push_back(c); h->call_scan_thr.push_back(h->user[(size_t)c].scan_thr); }
+    if (!h->call_scan.empty()) { const int rc = ensure_scan(h); if (rc) return rc; }
     // (a channel's RDS path runs while its decoder is on and stands still otherwise -- block filters, phase delay line, decimator and slicer
     // keep what they hold, as the reference's processor's do: nothing restarts when a decoder is switched; run_piece counts per channel)
     if (any_rds) { const int rc = ensure_rds(h); if (rc) return rc; }
@@ -1109,6 +1147,44 @@ int stage_rds(fmx_handle h, const CallGeom &G, hipStream_t s) {
     return FMX_OK;
 }
 
+// scan mode: the scanning channels' fm samples of the call behind their carries, every complete block of 1024 into the record ring (fmx_scan.hip), on the
+// stream stage A ran on: behind this piece's stage A and ahead of the next one's.  The bookkeeping is the host's; the kernel gets one job per channel.
+int stage_scan(fmx_handle h, const CallGeom &G, hipStream_t sa) {
+    const int64_t nj = G.J1 - G.J0;
+    const size_t n = h->call_scan.size();
+    h->scan_jobs.resize(n);
+    {
+        std::lock_guard<std::mutex> lk(h->mtx);      // (fmx_scan_results reads the counters from any thread)
+        for (size_t i = 0; i < n; i++) {
+            const int c = h->call_scan[i];
+            const int64_t fill = h->scan_fill[(size_t)c], blocks = h->scan_blocks[(size_t)c], nblk = (fill + nj) / scan::N;
+            h->scan_jobs[i] = ScanJob{c, (int32_t)fill, (int32_t)(blocks & (scan::RING - 1)), 0};
+            for (int64_t b = std::max<int64_t>(0, nblk - scan::RING); b < nblk; b++) {
+                const size_t slot = (size_t)c * scan::RING + (size_t)((blocks + b) & (scan::RING - 1));
+                h->scan_end[slot] = G.J0 + (b + 1) * scan::N - fill;          // (a complete block ends in this call: the carry holds < 1024)
+                h->scan_rec_thr[slot] = h->call_scan_thr[i];
+            }
+            h->scan_blocks[(size_t)c] = blocks + nblk;
+            h->scan_fill[(size_t)c] = (int32_t)((fill + nj) % scan::N);
+        }
+    }
+    // (pageable source: the copy is staged before the call returns)
+    HIPCHK(hipMemcpyAsync(h->d_scan_jobs, h->scan_jobs.data(), sizeof(ScanJob) * n, hipMemcpyHostToDevice, sa));
+    ScanArgs A{};
+    A.jobs = h->d_scan_jobs; A.zring = h->B.zring; A.params = h->d_params; A.front_sets = h->d_front_sets; A.W = h->d_scan_W;
+    A.carry = h->d_scan_carry; A.rec = h->d_scan_rec; A.J0 = G.J0; A.J1 = G.J1; A.ring_mask = G.ring_mask;
+    launch_scan(A, (int)n, sa); FMX_LAUNCHED();
+    return FMX_OK;
+}
+
+// the scanning channels' frames of the call are zeros (their chain runs on: outside the scanning calls a channel is what it would have been)
+int stage_scan_mute(fmx_handle h, float2 *d_pcm, int64_t pcm_stride, int64_t frames, hipStream_t s) {
+    const size_t n = h->call_scan.size();
+    HIPCHK(hipMemcpyAsync(h->d_scan_mute, h->call_scan.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+    launch_scan_mute(h->d_scan_mute, (int)n, d_pcm, pcm_stride, frames, s); FMX_LAUNCHED();
+    return FMX_OK;
+}
+
 // stage C: the audio filter and resampler (the block machines: the audio low-pass and the de-emphasis in front of it), a gain change's correction, the
 // second converter
 int stage_c(fmx_handle h, CallGeom &G, float2 *d_pcm, int64_t frames, int second, hipStream_t s) {
@@ -1176,6 +1252,7 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     h->B.lin_rows = (int32_t)h->work_nj;
     if (capture && (rc = capture_samples(h, d_iq, a, G, sa))) return rc;
     if ((rc = stage_a(h, G, d_iq, s, sa))) return rc;
+    if (!h->call_scan.empty() && G.J1 > G.J0 && (rc = stage_scan(h, G, sa))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[1], sa));
     G.stageb_form = h->stageb_form.load(); G.no_deemph = h->ola_mode ? 1 : 0;
     // a plain batch (no pre-pass, no RDS, no scope-tap rows: stage B as the whole kernel) runs stages B and C as two channel groups on two streams where it has
@@ -1189,6 +1266,7 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     if (h->rds_alloc && any_rds_on(h) && (rc = stage_rds(h, G, s))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[2], s));
     if ((rc = stage_c(h, G, d_pcm, frames, second, s))) return rc;
+    if (!h->call_scan.empty() && frames > 0 && (rc = stage_scan_mute(h, d_pcm, G.pcm_stride, frames, s))) return rc;
     if (prof) { HIPCHK(hipEventRecord(pr.e[3], s)); h->prof.push_back(pr); }
     FMX_LAUNCHED();
     HIPCHK(g_launch_err);
@@ -1628,6 +1706,18 @@ int fmx_set_param(fmx_handle h, int32_t channel, int32_t id, double value) {
         if (want != h->ola_mode) { h->ola_mode = want; h->sets_dirty = true; }
         h->folded_pinned = iv == 2;
         return FMX_OK; }
+    case FMX_P_SCANNING:
+    case FMX_P_SCAN_THRESHOLD: {
+        if (id == FMX_P_SCANNING && !(value == 0.0 || value == 1.0)) return fail(FMX_E_INVALID, "scanning must be 0 or 1");
+        if (id == FMX_P_SCAN_THRESHOLD && !(value >= -32768.0 && value <= 32767.0 && value == std::floor(value)))
+            return fail(FMX_E_INVALID, "scan threshold must be an integral number of dB in -32768..32767 (the reference's int16_t thresHold)");
+        std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes both at the next call; nothing on the device changes)
+        const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
+        for (int c = c0; c < c1; c++) {
+            if (id == FMX_P_SCANNING) h->user[(size_t)c].scanning = value != 0.0;
+            else h->user[(size_t)c].scan_thr = (int16_t)value;
+        }
+        return FMX_OK; }
     case FMX_P_DISP_DELAY: if (iv < 0 || iv > 100000) return fail(FMX_E_INVALID, "display delay must be 0..100000 steps"); break;
     case FMX_P_TEST_TONE:
     case FMX_P_VOLUME_DB: case FMX_P_LF_CUTOFF: case FMX_P_ATTENUATION_L: case FMX_P_ATTENUATION_R:
@@ -1932,6 +2022,35 @@ int fmx_rds_symbols(fmx_handle h, int32_t channel, float *iq, int32_t capacity, 
 }
 
 int64_t fmx_last_fm_samples(fmx_handle h) { return h ? (int64_t)(h->last_J1 - h->last_J0) : 0; }
+int fmx_scan_results(fmx_handle h, int32_t channel, fmx_scan_result *out, int32_t capacity, int32_t *n_results) {
+    if (!h || !n_results || channel < 0 || channel >= h->channels || capacity < 0 || (capacity > 0 && !out)) return fail(FMX_E_INVALID, "bad argument");
+    *n_results = 0;
+    if (!h->scan_alloc) return FMX_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipDeviceSynchronize());
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const size_t c = (size_t)channel;
+    const int64_t done = h->scan_blocks[c];
+    if (done - h->scan_read[c] > scan::RING) h->scan_read[c] = done - scan::RING;      // the caller fell behind: the oldest records are gone
+    const int take = (int)std::min<int64_t>(done - h->scan_read[c], capacity);
+    if (take > 0) {
+        std::vector<float2> ring((size_t)scan::RING);
+        HIPCHK(hipMemcpy(ring.data(), h->d_scan_rec + c * scan::RING, sizeof(float2) * scan::RING, hipMemcpyDeviceToHost));
+        for (int k = 0; k < take; k++) {
+            const int64_t b = h->scan_read[c] + k;
+            const size_t slot = (size_t)(b & (scan::RING - 1));
+            fmx_scan_result &r = out[k];
+            r.block = b; r.end_sample = h->scan_end[c * scan::RING + slot];
+            r.signal_db = ring[slot].x; r.noise_db = ring[slot].y;
+            r.found = (r.signal_db - r.noise_db > (float)h->scan_rec_thr[c * scan::RING + slot]) ? 1 : 0;   // fm-processor.cpp:489 (float against int16_t)
+            r.reserved = 0;
+        }
+        h->scan_read[c] += take;
+    }
+    *n_results = take;
+    return FMX_OK;
+}
+
 int64_t fmx_pll_replays(fmx_handle h, int32_t channel) {
     if (!h || channel >= h->channels) return (int64_t)fail(FMX_E_INVALID, "bad argument");
     if (hipSetDevice(h->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return (int64_t)fail(FMX_E_HIP, "device error");

@@ -401,6 +401,23 @@ struct RdsBuffers {
 // modes: bit k = some channel runs RDS_k; h_nc0: the host's copy of RdsBuffers::nc0
 void launch_rds(const DeviceBuffers &B, const RdsBuffers &Rb, const CallGeom &G, int C, const int64_t *h_nc0, int modes, hipStream_t s);
 
+// ---- scan mode (fmx_scan.hip, fmx_scan.h) --------------------------------------------------------------------------------
+// one scanning channel of a call (piece): samples already in its carry, and the record slot its first complete block goes to
+struct ScanJob { int32_t ch, fill, slot0, pad; };
+struct ScanArgs {
+    const ScanJob *jobs;          // [n_jobs] (copied per call on the stream of the launch)
+    const float2 *zring;          // stage A's fm-rate ring, [channels][ring_mask + 1]
+    const ChanParams *params; const FrontSet *front_sets;   // (the channel's delay_fm)
+    const float2 *W;              // [1024] scan::make_twiddles
+    float2 *carry;                // [channels][1024] the block being collected
+    float2 *rec;                  // [channels][scan::RING] (signal_db, noise_db) of the completed blocks
+    int64_t J0, J1;               // the call's fm samples
+    int32_t ring_mask, pad;
+};
+void launch_scan(const ScanArgs &A, int n_jobs, hipStream_t s);
+// zeroes frames [0, frames) of the channels chans [0 .. n - 1] at pcm + ch * pcm_stride
+void launch_scan_mute(const int32_t *chans, int n, float2 *pcm, int64_t pcm_stride, int64_t frames, hipStream_t s);
+
 void launch_front(const DeviceTables &T, const DeviceBuffers &B, const CallGeom &G, const void *iq,
                   int channels, hipStream_t s);
 // fmx_front4.hip: whole tiles of the call front4_kernel can take (0: none), and its launch over that many

@@ -28,6 +28,8 @@ P_CALL_PIECES = 27            # handle-wide: -1 automatic, 0 never, n > 0 fm sam
 P_FRONT_PARTS = 24            # handle-wide: 0 automatic, 1 one workgroup per channel, 2..32 parts in time per channel (bit-identical results)
 P_FILTER_RESTARTS = 23        # handle-wide, before the first call: 0 automatic, 1 the reference's block filters (<= 64 channels), 2 folded FIRs
 P_PLL_SOLVER = 21             # 0 automatic, 1 sequential (the reference's trajectory), 2 Newton while in lock + sequential around lock decisions, 3 Newton always
+P_SCANNING = 28               # per channel: 0 / 1, startScanning / stopScanning (the channel's PCM of a scanning call is zeros; its chain runs on)
+P_SCAN_THRESHOLD = 29         # per channel: the constructor's thresHold in dB, an integer in -32768..32767 (default 20)
 A_TRIGGER_FREQUENCY_CHANGE, A_RESTART_PSS, A_RESET_RDS = 100, 101, 102
 
 TAP_FM_IQ, TAP_DEMOD, TAP_LR_RAW, TAP_PRE_RESAMPLER, TAP_RDS_IQ, TAP_PILOT_PHASE = 0, 1, 2, 3, 4, 5
@@ -37,7 +39,7 @@ EXPORTS = [
     "fmx_abi_version", "fmx_last_error", "fmx_create", "fmx_destroy", "fmx_set_param", "fmx_frames_for", "fmx_filter_change_due",
     "fmx_process_host", "fmx_process_device", "fmx_process_host_raw", "fmx_process_device_raw", "fmx_synchronize",
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
-    "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
+    "fmx_scan_results", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
 ]
 
 
@@ -77,6 +79,17 @@ class FmxRdsInfo(C.Structure):
     def radio_text_unicode(self):
         """The radio text as the reference's setRadioText receives it (prepareText + mapEBUtoUnicode, trimmed)."""
         return "".join(chr(v) for v in self.radio_text_ucs2[:self.radio_text_ucs2_len])
+
+
+class FmxScanResult(C.Structure):
+    _fields_ = [("block", C.c_int64), ("end_sample", C.c_int64), ("signal_db", C.c_float), ("noise_db", C.c_float),
+                ("found", C.c_int32), ("reserved", C.c_int32)]
+
+
+# fmx_scan_result as a numpy record (Fmx.scan_results)
+SCAN_DTYPE = np.dtype([("block", np.int64), ("end_sample", np.int64), ("signal_db", np.float32), ("noise_db", np.float32),
+                       ("found", np.int32), ("reserved", np.int32)])
+assert SCAN_DTYPE.itemsize == C.sizeof(FmxScanResult)
 
 
 class FmxProfile(C.Structure):
@@ -137,6 +150,8 @@ def load_library(path=None):
     L.fmx_rds_map_char.argtypes = [C.c_uint8, C.c_uint8]
     L.fmx_rds_prepare_text.restype = i32
     L.fmx_rds_prepare_text.argtypes = [C.POINTER(C.c_uint8), i32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), i32]
+    L.fmx_scan_results.restype = C.c_int
+    L.fmx_scan_results.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
     L.fmx_rds_bits.restype = C.c_int
     L.fmx_rds_bits.argtypes = [vp, i32, C.POINTER(C.c_uint8), i32, C.POINTER(i32)]
     L.fmx_rds_symbols.restype = C.c_int
@@ -281,6 +296,14 @@ class Fmx:
         self._check(self.L.fmx_get_peaks(self.h, channel, out.ctypes.data_as(C.POINTER(C.c_float)), capacity, C.byref(n)))
         return out[:n.value].copy()
 
+    def scan_results(self, channel=0, capacity=1024):
+        """Scan-mode records completed since the last read, oldest first, as a numpy structured array (SCAN_DTYPE:
+        block, end_sample, signal_db, noise_db, found)."""
+        out = np.zeros(max(capacity, 1), SCAN_DTYPE)
+        n = C.c_int32()
+        self._check(self.L.fmx_scan_results(self.h, channel, out.ctypes.data, capacity, C.byref(n)))
+        return out[:n.value].copy()
+
     def rds_bits(self, channel=0, capacity=8192):
         buf = (C.c_uint8 * capacity)()
         n = C.c_int32()
@@ -375,6 +398,7 @@ class FmProcessor:
                                                    workingRate=workingRate, audioRate=audioRate)
         self.channel = channel
         self.bufferSize = blockSize                       # fm-processor.cpp:374
+        self.scanning = False                             # startScanning / stopScanning: taken over at the next block
 
     def _set(self, pid, v):
         self.fmx.set_param(pid, v, self.channel)
@@ -420,6 +444,15 @@ class FmProcessor:
     def setTestTone(self, b): self._set(P_TEST_TONE, 1 if b else 0)
     def setDispDelay(self, steps): self._set(P_DISP_DELAY, steps)
 
+    # scan mode (fm-processor.cpp:361-367, 478-495): the threshold is the constructor's thresHold, here a setting
+    def startScanning(self): self.scanning = True
+    def stopScanning(self): self.scanning = False
+    def setScanThreshold(self, db): self._set(P_SCAN_THRESHOLD, db)
+
+    def pollScanResults(self):
+        """The scan records since the last poll; the reference emits scanresult () for each with `found` set."""
+        return self.fmx.scan_results(self.channel)
+
     def isPilotLocked(self):
         m = self.fmx.meta(self.channel)
         return bool(m.live_pilot_locked), m.live_lock_strength
@@ -431,7 +464,9 @@ class FmProcessor:
         if self.myRig.Samples() < self.bufferSize:
             return False
         iq = self.myRig.getSamples(self.bufferSize)
+        scanning = self.scanning                          # (read once: the flag and what the sink gets belong to the same block)
+        self._set(P_SCANNING, 1 if scanning else 0)
         pcm = self.fmx.process_host(iq)
-        if self.theSink is not None and pcm.shape[1] > 0:
+        if self.theSink is not None and pcm.shape[1] > 0 and not scanning:    # the reference's loop sends nothing while it scans (:494)
             self.theSink.putSamples(pcm[self.channel])
         return True

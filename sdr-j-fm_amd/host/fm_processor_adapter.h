@@ -102,6 +102,10 @@ public:
     void setTestTone(bool b) { set(FMX_P_TEST_TONE, b); }
     void setDispDelay(int steps) { set(FMX_P_DISP_DELAY, steps); }       // fm-processor.cpp:935-937
     void set_squelchValue(int v) { set(FMX_P_SQUELCH_VALUE, v); }        // :213-215
+    // scan mode (fm-processor.cpp:361-367): taken over at the next block; the constructor's thresHold (:63,108) as a setter
+    void startScanning() { scanning.store(true); }
+    void stopScanning() { scanning.store(false); }
+    void setScanThreshold(int16_t thresHold) { set(FMX_P_SCAN_THRESHOLD, thresHold); }
 
     bool isPilotLocked(float &oLockStrength) {                             // fm-processor.cpp:870-880
         fmx_meta m{};
@@ -126,11 +130,15 @@ public:
     bool take_block() {
         const int32_t amount = myRig->getSamples(inBuf.data(), bufferSize);
         lastN = amount;
+        // the scanning flag is read once per block: while it is set the reference's loop feeds its scan buffer and sends nothing on (:478-495)
+        const bool scan = scanning.load();
+        if (scan != lastScan && !check(fmx_set_param(h, 0, FMX_P_SCANNING, scan ? 1.0 : 0.0))) return false;
+        lastScan = scan;
         int64_t frames = 0;
         if (!check(fmx_process_host(h, reinterpret_cast<const float *>(inBuf.data()), amount, amount,
                                     reinterpret_cast<float *>(outBuf.data()), (int64_t)outBuf.size(), &frames)))
             return false;
-        if (frames > 0 && theSink) theSink->putSamples(outBuf.data(), (int32_t)frames);
+        if (frames > 0 && theSink && !scan) theSink->putSamples(outBuf.data(), (int32_t)frames);
         fmCount += fmx_last_fm_samples(h);                                    // (amount / the reference's decimation at this input rate)
         return true;
     }
@@ -155,9 +163,24 @@ public:
     template <class F> int poll_peaks(F emit_fn) {
         float lr[2 * 64]; int32_t n = 0;
         if (fmx_get_peaks(h, 0, lr, 64, &n) != FMX_OK) return 0;
+        if (lastScan) return 0;                                             // (a scanning block feeds no meter: the windows are taken and dropped)
         for (int32_t k = 0; k < n; k++) emit_fn(lr[2 * k], lr[2 * k + 1]);
         return n;
     }
+
+    // what the reference's scan emits (fm-processor.cpp:483-493): calls `emit_fn(const fmx_scan_result &)` once per block completed since the
+    // last poll, oldest first; the reference emits scanresult () for the records with `found` set
+    template <class F> int poll_scan(F emit_fn) {
+        fmx_scan_result r[64]; int32_t n = 0, total = 0;
+        do {
+            if (fmx_scan_results(h, 0, r, 64, &n) != FMX_OK) return total;
+            for (int32_t k = 0; k < n; k++) emit_fn(r[k]);
+            total += n;
+        } while (n == 64);
+        return total;
+    }
+    // the last block was processed while scanning: the GUI's scope feeds skip it, as the reference's loop does
+    bool lastBlockScanned() const { return lastScan; }
 
     static constexpr int32_t bufferSize = 2 * 8192;                        // fm-processor.cpp:374
 
@@ -180,6 +203,8 @@ private:
     AudioSink *theSink;
     std::vector<std::complex<float>> inBuf, outBuf;
     std::atomic<bool> running{false};
+    std::atomic<bool> scanning{false};
+    bool lastScan = false;                                                  // the flag the last block was processed with (and handed to the library)
     std::string err;
     int64_t fmCount = 0, lastMeta = 0;
     int32_t lastN = 0;

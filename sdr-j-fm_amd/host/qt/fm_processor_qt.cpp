@@ -55,10 +55,11 @@ struct fmProcessor::Impl {
 fmProcessor::fmProcessor(deviceHandler *theDevice, RadioInterface *RI, audioSink *mySink, fm_Demodulator *, int32_t inputRate,
                          int32_t fmRate_, int32_t workingRate, int32_t audioRate, int32_t, int spectrumSize_, int32_t repeatRate_,
                          int ptyLocale, RingBuffer<std::complex<float>> *hfBuffer, RingBuffer<std::complex<float>> *lfBuffer,
-                         RingBuffer<std::complex<float>> *iqBuffer, int16_t, int gpu)
+                         RingBuffer<std::complex<float>> *iqBuffer, int16_t thresHold, int gpu)
     : d(new Impl(theDevice, mySink, inputRate, fmRate_, workingRate, audioRate, gpu, hfBuffer, lfBuffer, iqBuffer)), fmRate(fmRate_),
       repeatRate(repeatRate_), spectrumSize(spectrumSize_) {
     d->core.set_ptyLocale(ptyLocale);
+    d->core.setScanThreshold(thresHold);                   // the scan's threshold (fm-processor.cpp:108, :489)
     qRegisterMetaType<const fmx_qt::fmProcessor::SMetaData *>("const fmx_qt::fmProcessor::SMetaData*");
     QObject *gui = RI;
     if (gui) {      // by name, as the reference's constructors do (a slot the GUI object lacks only prints Qt's warning, as there)
@@ -119,6 +120,8 @@ void fmProcessor::setPSSMode(bool b) { d->core.setPSSMode(b); }
 void fmProcessor::setDCRemove(bool b) { dcRemove.store(b); d->core.setDCRemove(b); }
 void fmProcessor::setTestTone(bool b) { d->core.setTestTone(b); }
 void fmProcessor::setDispDelay(int steps) { d->core.setDispDelay(steps); }
+void fmProcessor::startScanning() { d->core.startScanning(); }
+void fmProcessor::stopScanning() { d->core.stopScanning(); }
 void fmProcessor::set_ptyLocale(int l) { d->core.set_ptyLocale(l); }
 bool fmProcessor::isPilotLocked(float &oLockStrength) { return d->core.isPilotLocked(oLockStrength); }
 float fmProcessor::get_demodDcComponent() { return d->core.get_demodDcComponent(); }
@@ -260,6 +263,13 @@ void fmProcessor::run() {
                 I.dumped[(size_t)i] = x;
             }
             dumpWriter(f, reinterpret_cast<const float *>(I.dumped.data()), amount);
+        }
+        if (I.core.lastBlockScanned()) {
+            // scan mode (:478-495): the block went to the scan; scanresult () for every block over the threshold, and nothing of what the
+            // reference's loop does behind its `continue` -- RDS, LF scope, peak level, metaData
+            I.core.poll_scan([this](const fmx_scan_result &r) { if (r.found) emit scanresult(); });
+            I.core.poll_peaks([](float, float) {});
+            continue;
         }
         feed_rds();
         feed_lf_scope();

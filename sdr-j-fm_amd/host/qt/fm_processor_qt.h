@@ -84,6 +84,8 @@ public:
     void setTestTone(bool b);
     void setDispDelay(int steps);
     void set_ptyLocale(int l);                                             // fm-processor.cpp:939-941
+    void startScanning();                                                  // fm-processor.cpp:361-367 (taken over at the next block)
+    void stopScanning();
     void setlfPlotType(ELfPlot t) {                                        // fm-processor.cpp:244-265
         lfPlot.store((int)t);
         showFullSpectrum.store(t == ELfPlot::IF_FILTERED || t == ELfPlot::RDS_INPUT || t == ELfPlot::RDS_DEMOD);
@@ -110,7 +112,7 @@ signals:
     void showMetaData(const fmx_qt::fmProcessor::SMetaData *);
     void showPeakLevel(const float, const float);
     void setSquelchIsActive(bool);
-    void scanresult();                                                     // (scan mode is out of scope: never emitted)
+    void scanresult();                                                     // once per scanned block of 1024 fm samples over the threshold (fm-processor.cpp:489-492)
     // rds-decoder.h:84-85, rds-groupdecoder.h:90-101, rds-blocksynchronizer.h:102-104
     void setCRCErrors(int);
     void setSyncErrors(int);

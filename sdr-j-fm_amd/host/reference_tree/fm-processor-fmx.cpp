@@ -37,6 +37,8 @@ struct Core {
     int32_t lfCount = 0, iqCounter = 0, lastDecoder = -1;
     int16_t lastSquelchValue = -1;
     bool lastSquelch = false, squelchKnown = false;
+    bool lastScan = false;                                    // the scanning flag the library has (FMX_P_SCANNING)
+    std::vector<fmx_scan_result> scan;
 };
 std::mutex g_mtx;
 std::map<const fmProcessor *, Core *> g_core;
@@ -82,6 +84,7 @@ fmProcessor::fmProcessor(deviceHandler *theDevice, RadioInterface *RI, audioSink
     cfg.max_block = kBlock;
     if (fmx_abi_version() != FMX_ABI_VERSION) qFatal("fmx: libfmx has ABI version %d, this binding was built for %d", fmx_abi_version(), FMX_ABI_VERSION);
     if (fmx_create(&cfg, &c->h) != FMX_OK) qFatal("fmx: %s", fmx_last_error());
+    if (fmx_set_param(c->h, 0, FMX_P_SCAN_THRESHOLD, thresHold_) != FMX_OK) qWarning("fmx: %s", fmx_last_error());   // the scan threshold (:108, :489)
     c->in.resize(kBlock); c->dumped.resize(kBlock);
     // PCM frames of one block: the reference decimates inputRate by 12, 6 or not at all (fm-processor.cpp:68-75,471), four fm samples make
     // one 48 kHz frame, the second converter makes audioRate / workingRate of those -- a 192 kS/s device yields 4096 frames per block, not
@@ -151,7 +154,7 @@ DSPCOMPLEX fmProcessor::audioGainCorrection(DSPCOMPLEX z) {                     
 void fmProcessor::startDumping(SNDFILE *f) { if (dumping) return; dumpFile = f; dumping = true; }   // :338-345
 void fmProcessor::stopDumping() { dumping = false; }
 void fmProcessor::setAttenuation(DSPFLOAT l, DSPFLOAT r) { Lgain = l; Rgain = r; set(this, FMX_P_ATTENUATION_L, l); set(this, FMX_P_ATTENUATION_R, r); }
-void fmProcessor::startScanning() { scanning = true; }                                     // (scan mode: SURVEY 8 a22, out of scope -- the flag is kept, run () ignores it)
+void fmProcessor::startScanning() { scanning = true; }                                     // :361-367 (run () takes the flag over at the next block)
 void fmProcessor::stopScanning() { scanning = false; }
 void fmProcessor::setlfcutoff(int32_t Hz) {                                                // :762-770
     if (Hz > 0) { lowPassFrequency = Hz; fmAudioFilterActive.store(true); } else fmAudioFilterActive.store(false);
@@ -219,9 +222,27 @@ void fmProcessor::run() {
         const bool wantDump = dumping && dumpFile != nullptr;
         if (wantDump) (void)fmx_get_meta(c.h, 0, &before);
 
+        // scan mode (:478-495), read once per block: while it is set the library collects the block's fm samples for the scan and the
+        // reference's loop sends nothing on -- no PCM, no RDS, no LF scope, no peak level, no metaData (the chain runs on in the library)
+        const bool scan = scanning;
+        if (scan != c.lastScan) { c.lastScan = scan; fmx_set_param(c.h, 0, FMX_P_SCANNING, scan ? 1 : 0); }
+
         int64_t frames = 0;
         if (fmx_process_host(c.h, reinterpret_cast<const float *>(c.in.data()), amount, amount, reinterpret_cast<float *>(c.pcm.data()),
                              (int64_t)c.pcm.size(), &frames) != FMX_OK) { qWarning("fmx: %s", fmx_last_error()); continue; }
+        if (scan) {
+            // every block of 1024 fm samples the scan completed; scanresult () where the reference emits it (:489-492)
+            c.scan.resize(64);
+            int32_t ns = 0;
+            do {
+                if (fmx_scan_results(c.h, 0, c.scan.data(), 64, &ns) != FMX_OK) break;
+                for (int32_t k = 0; k < ns; k++) if (c.scan[(size_t)k].found) emit scanresult();
+            } while (ns == 64);
+            float lr[2 * 64]; int32_t npk = 0;
+            (void)fmx_get_peaks(c.h, 0, lr, 64, &npk);                                     // (the meter's windows of a scanning block are dropped)
+            if (rdsModus != rdsDecoder::ERdsMode::RDS_OFF) { int32_t nb = 0; c.bits.resize(8192); (void)fmx_rds_bits(c.h, 0, c.bits.data(), 8192, &nb); }
+            continue;
+        }
         if (frames > 0) theSink->putSamples(c.pcm.data(), (int32_t)frames);                // :825-838
 
         if (wantDump) {
