@@ -133,6 +133,7 @@ def oracle():
         "fmo_pss_reset": (None, [vp]),
         "fmo_pss_process": (f32, [vp, f32, f32]),
         "fmo_resampler_taps": (None, [c_float_p]),
+        "fmo_conv2_design": (C.c_int, [i32, i32, c_i32_p, c_i32_p, c_i32_p, c_float_p]),
         "fmo_sincos_eval": (None, [vp, c_float_p, lng, c_float_p, c_float_p, c_float_p]),
         "fmo_atan2_eval": (None, [c_float_p, c_float_p, lng, c_float_p]),
         "fmo_pi_constrain_eval": (None, [c_float_p, lng, c_float_p]),
