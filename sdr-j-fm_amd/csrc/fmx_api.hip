@@ -1,6 +1,7 @@
 // fmx_api.hip -- the C ABI of libfmx (include/fmx.h): handle, settings mailbox, table/tap
-// design + upload, per-call geometry and the three kernel launches.  No CPU fallback exists:
-// every entry point fails when HIP is unavailable.
+// design + upload, per-call geometry and the three kernel launches.  A handle's device and pinned memory
+// has one owner (DevMem): fmx_destroy names no buffer.  No CPU fallback exists: every entry point fails
+// when HIP is unavailable.
 #include "../../include/fmx.h"
 #include "../../include/fmx_debug.h"
 #include "fmx_internal.h"
@@ -17,6 +18,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace fmx;
@@ -43,6 +45,44 @@ int fail(int code, const std::string &msg) { g_err = msg; return code; }
         if (e_ != hipSuccess)                                                              \
             return fail(FMX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
     } while (0)
+
+#define FMXCHK(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
+
+// The owner of a handle's device and pinned memory: every buffer is its own hipMalloc / hipHostMalloc, recorded the moment it exists, and given back
+// by release (one buffer, now) or release_all (fmx_destroy).  The only place of this library that allocates or frees GPU memory for a handle.
+struct DevMem {
+    std::vector<void *> dev, pinned;
+    template <class T> int alloc(T *&p, size_t n, bool zero = false) {
+        void *q = nullptr;
+        HIPCHK(hipMalloc(&q, sizeof(T) * n));
+        dev.push_back(q); p = static_cast<T *>(q);
+        if (zero) HIPCHK(hipMemset(q, 0, sizeof(T) * n));
+        return FMX_OK;
+    }
+    template <class T> int upload(T *&p, const std::vector<typename std::remove_const<T>::type> &src) {
+        FMXCHK(alloc(p, src.size()));
+        HIPCHK(hipMemcpy(dev.back(), src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+        return FMX_OK;
+    }
+    template <class T> int alloc_pinned(T *&p, size_t n) {
+        void *q = nullptr;
+        HIPCHK(hipHostMalloc(&q, sizeof(T) * n, hipHostMallocDefault));
+        pinned.push_back(q); p = static_cast<T *>(q);
+        return FMX_OK;
+    }
+    template <class T> void release(T *&p) {          // (device or pinned; a null or unknown pointer is only nulled)
+        void *q = const_cast<void *>(static_cast<const void *>(p));
+        auto it = std::find(dev.begin(), dev.end(), q);
+        if (it != dev.end()) { dev.erase(it); (void)hipFree(q); }
+        else if ((it = std::find(pinned.begin(), pinned.end(), q)) != pinned.end()) { pinned.erase(it); (void)hipHostFree(q); }
+        p = nullptr;
+    }
+    void release_all() {
+        for (void *q : dev) (void)hipFree(q);
+        for (void *q : pinned) (void)hipHostFree(q);
+        dev.clear(); pinned.clear();
+    }
+};
 
 int next_pow2(int64_t v) { int64_t p = 1; while (p < v) p <<= 1; return (int)p; }
 
@@ -88,19 +128,15 @@ struct fmx_handle_s {
     bool gain_dirty = true;                                          // volume / balance set since the last call (and before the first); under mtx
     bool gain_pending = false;                                       // ... taken over by flush_mailbox together with the settings themselves (processing
                                                                      // thread only): gain_fix_kernel runs in the first call that produces frames
-    float *d_audio_lp = nullptr, *d_rs_taps = nullptr;
-    float2 *d_audio_spec = nullptr;               // the audio low-pass and the resampler alone (gain_fix_kernel)
+    DevMem mem;                              // every device / pinned buffer of the handle (the RDS path's: rds_mem)
     // unique tap sets
     std::vector<int32_t> front_keys, audio_keys;
     int front_cap = 0, audio_cap = 0;
     std::vector<float> h_front_taps, h_audio_taps, h_pss_taps, h_rs_taps, h_nsq, h_rds1;
-    float *d_nsq = nullptr;
     std::vector<FrontSet> h_front_sets; std::vector<AudioSet> h_audio_sets;
-    // device
-    float *d_front_taps = nullptr, *d_audio_taps = nullptr, *d_pss_taps = nullptr;
-    float2 *d_fft_w = nullptr, *d_pss_hs = nullptr;
+    // device: what the host writes again after the allocation (the kernels' views T.front_taps, T.front_sets, T.audio_taps, T.audio_sets, B.params are const)
+    float *d_front_taps = nullptr, *d_audio_taps = nullptr;
     FrontSet *d_front_sets = nullptr; AudioSet *d_audio_sets = nullptr;
-    float2 *d_sincos = nullptr, *d_lo = nullptr; float *d_atan = nullptr, *d_arcsine = nullptr; double2 *d_trig3 = nullptr;
     ChanParams *d_params = nullptr;
     DeviceTables T{}; DeviceBuffers B{};
     int ring = 0, dring = 0, sring = 0;
@@ -109,14 +145,14 @@ struct fmx_handle_s {
     int64_t work_nj = 0;                     // rows of the sample-major work arrays
     int pitch = 0;                           // their row pitch in elements
     // staging for the host-pointer entry point
-    float2 *d_iq = nullptr, *d_pcm = nullptr; int64_t pcm_cap = 0;
+    float2 *d_iq = nullptr, *d_pcm = nullptr;
     // second converter (audioRate != workingRate, fm-processor.cpp:89-91,825-838)
     int cv_p = 1, cv_q = 1, cv_nt = 0; float *d_cv_taps = nullptr; float2 *d_x48 = nullptr; int64_t x48_stride = 0;
     // profiling
     bool prof_on = false; std::vector<ProfRec> prof; fmx_profile prof_acc{};
     int64_t last_J0 = 0, last_J1 = 0;
     // RDS path (allocated when a channel first switches RDS on)
-    bool rds_alloc = false; RdsBuffers R{};
+    bool rds_alloc = false; RdsBuffers R{}; DevMem rds_mem;     // (an owner of its own: a partial failure gives the whole path back, ensure_rds)
     // per channel: the fm samples its RDS path has processed (it stands still while the channel's decoder is off, as the reference's
     // processor leaves its block filters, phase delay line and decimator alone then: fm-processor.cpp:733-754, :551-553), what RdsBuffers::nc0
     // was in the last call, and the device copy of the latter
@@ -129,7 +165,6 @@ struct fmx_handle_s {
     std::vector<int32_t> rds_gen_dec, rds_gen_sym;   // for fmx_rds_decode, the channel's block synchroniser / group decoder), however late it polls
     std::vector<fmx::RdsGroupDecoderHost> rds_dec;
     std::vector<int64_t> last_m0, last_m1;  // per channel: its 24 kS/s outputs of the last call
-    std::vector<void *> rds_ptrs, tail_ptrs;
     // what a call needs of `params` beyond the device copy, taken under `mtx` by flush_mailbox: fmx_set_param may write `params` from another thread
     // while the processing thread enqueues the call
     std::vector<int8_t> call_rds_mode; bool call_any_rds = false;
@@ -160,7 +195,7 @@ struct fmx_handle_s {
     int last_second_group = 0;           // channels of the second stage-B / C group of the last call (fmx_last_second_group)
     int my_count_host = 0;               // the reference's myCount (fm-processor.cpp:662-684) as stage B keeps it in every channel's state: the same in all of them
     PreLook pre_look{};                  // pre_kernel's look-back buffers (ensure_ola)
-    void *hp_iq = nullptr; float2 *hp_pcm = nullptr; size_t hp_iq_bytes = 0; int64_t hp_pcm_cap = 0;   // fmx_process_host: pinned, device-visible staging of small calls
+    char *hp_iq = nullptr; float2 *hp_pcm = nullptr;   // fmx_process_host: pinned, device-visible staging of small calls
     // the reference's two overlap-add filters as the block machines they are (fmx_ola.hip): handles of up to OLA_MAX_CH channels
     bool ola_mode = false;               // FMX_P_FILTER_RESTARTS resolved (fixed once the first call has been made)
     struct OlaSide {
@@ -294,10 +329,10 @@ int ensure_sets(fmx_handle h) {
             for (size_t p = 0; p < TW; p++) { h->h_front_sets[i * TW + p].zshift = dl[p] - dmin; h->h_front_sets[i * TW + p].delay_fm = (int32_t)(TW * (size_t)dmin); }
         }
         if ((int)NS > h->front_cap) {
-            if (h->d_front_taps) { (void)hipFree(h->d_front_taps); (void)hipFree(h->d_front_sets); }
+            h->mem.release(h->d_front_taps); h->mem.release(h->d_front_sets);
             h->front_cap = std::max<int>((int)NS, 4);
-            HIPCHK(hipMalloc(&h->d_front_taps, sizeof(float) * A_TAPS_DEV * h->front_cap));
-            HIPCHK(hipMalloc(&h->d_front_sets, sizeof(FrontSet) * h->front_cap));
+            FMXCHK(h->mem.alloc(h->d_front_taps, (size_t)A_TAPS_DEV * h->front_cap));
+            FMXCHK(h->mem.alloc(h->d_front_sets, (size_t)h->front_cap));
         }
         HIPCHK(hipDeviceSynchronize());
         std::vector<float> dev(NS * A_TAPS_DEV, 0.f);                    // device image: [set][r][d]
@@ -316,10 +351,10 @@ int ensure_sets(fmx_handle h) {
         for (size_t i = 0; i < ak.size(); i++)
             build_audio_set(ak[i], h->cfg.fmRate, h->h_rs_taps, &h->h_audio_taps[i * C_TAPS_STRIDE], &h->h_audio_sets[i]);
         if ((int)ak.size() > h->audio_cap) {
-            if (h->d_audio_taps) { (void)hipFree(h->d_audio_taps); (void)hipFree(h->d_audio_sets); }
+            h->mem.release(h->d_audio_taps); h->mem.release(h->d_audio_sets);
             h->audio_cap = std::max<int>((int)ak.size(), 4);
-            HIPCHK(hipMalloc(&h->d_audio_taps, sizeof(float) * C_TAPS_STRIDE * h->audio_cap));
-            HIPCHK(hipMalloc(&h->d_audio_sets, sizeof(AudioSet) * h->audio_cap));
+            FMXCHK(h->mem.alloc(h->d_audio_taps, (size_t)C_TAPS_STRIDE * h->audio_cap));
+            FMXCHK(h->mem.alloc(h->d_audio_sets, (size_t)h->audio_cap));
         }
         HIPCHK(hipDeviceSynchronize());
         HIPCHK(hipMemcpy(h->d_audio_taps, h->h_audio_taps.data(), sizeof(float) * h->h_audio_taps.size(), hipMemcpyHostToDevice));
@@ -328,11 +363,9 @@ int ensure_sets(fmx_handle h) {
         {   // the two factors of the folded FIR, separately (gain_fix_kernel)
             std::vector<float> lp(ak.size() * AUDIO_TAPS, 0.f);
             for (size_t i = 0; i < ak.size(); i++) if (ak[i] > 0) { const std::vector<float> ha = design::lowpass(AUDIO_TAPS, ak[i], h->cfg.fmRate); std::copy(ha.begin(), ha.end(), lp.begin() + i * AUDIO_TAPS); }
-            if (h->d_audio_lp) (void)hipFree(h->d_audio_lp);
-            HIPCHK(hipMalloc(&h->d_audio_lp, sizeof(float) * lp.size()));
-            HIPCHK(hipMemcpy(h->d_audio_lp, lp.data(), sizeof(float) * lp.size(), hipMemcpyHostToDevice));
-            if (!h->d_rs_taps) { HIPCHK(hipMalloc(&h->d_rs_taps, sizeof(float) * RS_TAPS)); HIPCHK(hipMemcpy(h->d_rs_taps, h->h_rs_taps.data(), sizeof(float) * RS_TAPS, hipMemcpyHostToDevice)); }
-            h->T.audio_lp_taps = h->d_audio_lp; h->T.rs_taps = h->d_rs_taps;
+            h->mem.release(h->T.audio_lp_taps);
+            FMXCHK(h->mem.upload(h->T.audio_lp_taps, lp));
+            if (!h->T.rs_taps) FMXCHK(h->mem.upload(h->T.rs_taps, h->h_rs_taps));
             // spectra of the four decimation phases g_p[i] = g[4 i + p] of the folded FIR (audio_fft_kernel); h_audio_taps holds g reversed
             std::vector<float2> W(fftc::W_COUNT), spec(ak.size() * 4 * fftc::N);
             fftc::make_twiddles(W.data());
@@ -345,10 +378,8 @@ int ensure_sets(fmx_handle h) {
                     fftc::make_spectrum(gp.data(), (int)gp.size(), &spec[(i * 4 + p) * fftc::N], W.data());
                 }
             }
-            if (h->d_audio_spec) (void)hipFree(h->d_audio_spec);
-            HIPCHK(hipMalloc(&h->d_audio_spec, sizeof(float2) * spec.size()));
-            HIPCHK(hipMemcpy(h->d_audio_spec, spec.data(), sizeof(float2) * spec.size(), hipMemcpyHostToDevice));
-            h->T.audio_spec = h->d_audio_spec;
+            h->mem.release(h->T.audio_spec);
+            FMXCHK(h->mem.upload(h->T.audio_spec, spec));
         }
     }
     h->sets_dirty = false;
@@ -374,67 +405,54 @@ void refresh_derived(fmx_handle h, int c) {
 }
 
 int ensure_lo_table(fmx_handle h) {
-    if (h->d_lo) return FMX_OK;
+    if (h->T.lo_table) return FMX_OK;
     const int32_t R = h->cfg.inputRate;
     std::vector<float2> tab((size_t)R);
     for (int32_t i = 0; i < R; i++)             // Oscillator ctor oscillator.cpp:26-35
         tab[i] = make_float2((float)std::cos(2.0 * design::kPi * i / R), (float)std::sin(2.0 * design::kPi * i / R));
-    HIPCHK(hipMalloc(&h->d_lo, sizeof(float2) * (size_t)R));
-    HIPCHK(hipMemcpy(h->d_lo, tab.data(), sizeof(float2) * (size_t)R, hipMemcpyHostToDevice));
-    h->T.lo_table = h->d_lo;
-    return FMX_OK;
+    return h->mem.upload(h->T.lo_table, tab);
 }
 
 int ensure_rds_body(fmx_handle h);
 int ensure_rds(fmx_handle h) {
     if (h->rds_alloc) return FMX_OK;
     const int rc = ensure_rds_body(h);
-    if (rc) {                                       // partial failure: give everything back, the next enable tries again
-        for (void *p : h->rds_ptrs) if (p) (void)hipFree(p);
-        h->rds_ptrs.clear(); h->R = RdsBuffers{};
-    }
+    if (rc) { h->rds_mem.release_all(); h->R = RdsBuffers{}; h->d_rds_nc0 = nullptr; }      // partial failure: give everything back, the next enable tries again
     return rc;
 }
 int ensure_rds_body(fmx_handle h) {
     const size_t C = (size_t)h->channels;
     const int32_t fmRate = h->cfg.fmRate;
-    auto dalloc = [&](void **p, size_t bytes, bool zero) -> int {
-        HIPCHK(hipMalloc(p, bytes));
-        if (zero) HIPCHK(hipMemset(*p, 0, bytes));
-        h->rds_ptrs.push_back(*p);
-        return FMX_OK;
-    };
+    DevMem &M = h->rds_mem;
     RdsBuffers &R = h->R;
-    int rc;
-    if ((rc = dalloc((void **)&R.in_blk, sizeof(float) * C * RDS_BLK, true))) return rc;
-    if ((rc = dalloc((void **)&R.bpreal, sizeof(float) * C * 2 * RDS_BLK, true))) return rc;
-    if ((rc = dalloc((void **)&R.bp_over, sizeof(float2) * 2 * C * 768, true))) return rc;
-    if ((rc = dalloc((void **)&R.hil, sizeof(float2) * C * 2 * RDS_BLK, true))) return rc;
-    if ((rc = dalloc((void **)&R.hil_over, sizeof(float2) * 2 * C * 768, true))) return rc;
-    if ((rc = dalloc((void **)&R.phase_ring, sizeof(float) * C * RDS_PHASE_RING, true))) return rc;
-    if ((rc = dalloc((void **)&R.U, sizeof(float2) * C * 32768, false))) return rc;
-    if ((rc = dalloc((void **)&R.V, sizeof(float2) * C * 32768, false))) return rc;
-    if ((rc = dalloc((void **)&R.rds24, sizeof(float2) * C * RDS24_RING, true))) return rc;
+    FMXCHK(M.alloc(R.in_blk, C * RDS_BLK, true));
+    FMXCHK(M.alloc(R.bpreal, C * 2 * RDS_BLK, true));
+    FMXCHK(M.alloc(R.bp_over, 2 * C * 768, true));
+    FMXCHK(M.alloc(R.hil, C * 2 * RDS_BLK, true));
+    FMXCHK(M.alloc(R.hil_over, 2 * C * 768, true));
+    FMXCHK(M.alloc(R.phase_ring, C * RDS_PHASE_RING, true));
+    FMXCHK(M.alloc(R.U, C * 32768));
+    FMXCHK(M.alloc(R.V, C * 32768));
+    FMXCHK(M.alloc(R.rds24, C * RDS24_RING, true));
     R.pitch = h->pitch;
-    if ((rc = dalloc((void **)&R.mf, sizeof(float2) * (size_t)(h->work_nj / 8 + 8) * h->pitch, false))) return rc;
+    FMXCHK(M.alloc(R.mf, (size_t)(h->work_nj / 8 + 8) * h->pitch));
     R.mfc_stride = ((h->work_nj / 8 + 8 + 2 + 7) / 8) * 8;
-    if ((rc = dalloc((void **)&R.mfc, sizeof(float2) * (size_t)R.mfc_stride * C, true))) return rc;
-    if ((rc = dalloc((void **)&R.mfm, sizeof(float) * (size_t)R.mfc_stride * C, true))) return rc;
-    if ((rc = dalloc((void **)&R.bits, C * RDS_BITS_CAP, true))) return rc;
-    if ((rc = dalloc((void **)&R.sym, sizeof(float2) * C * RDS_SYM_CAP, true))) return rc;
+    FMXCHK(M.alloc(R.mfc, (size_t)R.mfc_stride * C, true));
+    FMXCHK(M.alloc(R.mfm, (size_t)R.mfc_stride * C, true));
+    FMXCHK(M.alloc(R.bits, C * RDS_BITS_CAP, true));
+    FMXCHK(M.alloc(R.sym, C * RDS_SYM_CAP, true));
     {   // rdsDecoder_2 / AGC / Costas constructor state (rds-decoder-2.cpp:44-78, rds-decoder.cpp:41-43)
         RdsState s0; std::memset(&s0, 0, sizeof(s0));
         s0.gain = 9.0f; s0.mu = 0.f; s0.skip = 3; s0.sample_count = 0;
         s0.c_limit = (float)(2 * design::kPi * (double)10.0f / (double)(float)24000);
         std::vector<RdsState> init(C, s0);
-        if ((rc = dalloc((void **)&R.state, sizeof(RdsState) * C, false))) return rc;
-        HIPCHK(hipMemcpy(R.state, init.data(), sizeof(RdsState) * C, hipMemcpyHostToDevice));
+        FMXCHK(M.upload(R.state, init));
     }
     {   // spectra: the DFT of the zero-padded band-pass kernel (fft-filters.cpp:71-82, setBand(57000 -+ 2400)), and the
         // analytic-signal mask of fftFilterHilbert::setHilbert (:177-190)
         const int N = 32768, D = 768;
         std::vector<float> k = design::bandpass(D, 3 * 19000 - 4800 / 2, 3 * 19000 + 4800 / 2, fmRate);
-        std::vector<float2> S((size_t)N), M((size_t)N);
+        std::vector<float2> S((size_t)N), Hm((size_t)N);
         std::vector<double> cs((size_t)N), sn((size_t)N);
         for (int i = 0; i < N; i++) { cs[i] = std::cos(-2 * design::kPi * i / N); sn[i] = std::sin(-2 * design::kPi * i / N); }
         for (int f = 0; f < N; f++) {
@@ -445,14 +463,10 @@ int ensure_rds_body(fmx_handle h) {
                 im += (double)k[2 * i] * sn[a] + (double)k[2 * i + 1] * cs[a];
             }
             S[f] = make_float2((float)re, (float)im);
-            M[f] = make_float2(f == 0 || f == N / 2 ? 1.0f : (f < N / 2 ? 2.0f : 0.0f), 0.f);
+            Hm[f] = make_float2(f == 0 || f == N / 2 ? 1.0f : (f < N / 2 ? 2.0f : 0.0f), 0.f);
         }
-        float2 *dS, *dM;
-        if ((rc = dalloc((void **)&dS, sizeof(float2) * N, false))) return rc;
-        if ((rc = dalloc((void **)&dM, sizeof(float2) * N, false))) return rc;
-        HIPCHK(hipMemcpy(dS, S.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dM, M.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
-        R.S_bp = dS; R.S_hil = dM;
+        FMXCHK(M.upload(R.S_bp, S));
+        FMXCHK(M.upload(R.S_hil, Hm));
         {   // the band-pass kernel is complex and only the real part of its result is kept (fm-processor.cpp:741): for a real input
             // Re (a * s) = a * Re (s), the DFT of Re (s) is the Hermitian part of S -- the filter vector of the paired transforms
             std::vector<float2> Sr((size_t)N);
@@ -460,24 +474,20 @@ int ensure_rds_body(fmx_handle h) {
                 const float2 a = S[(size_t)f], b = S[(size_t)((N - f) & (N - 1))];
                 Sr[(size_t)f] = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
             }
-            float2 *dSr;
-            if ((rc = dalloc((void **)&dSr, sizeof(float2) * N, false))) return rc;
-            HIPCHK(hipMemcpy(dSr, Sr.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
-            R.S_bp_re = dSr;
+            FMXCHK(M.upload(R.S_bp_re, Sr));
         }
         std::vector<float> dk = design::decim_complex(11, 24000 / 2, fmRate);      // rdsDecimator fm-processor.cpp:382
         std::vector<float> rr = design::rrc(1.0, 24000, 2 * 1187.5f, 1.0, 45);       // rds-decoder-2.cpp:67-71
-        float2 *dd; float *dr;
-        if ((rc = dalloc((void **)&dd, sizeof(float2) * 11, false))) return rc;
-        if ((rc = dalloc((void **)&dr, sizeof(float) * 45, false))) return rc;
+        float2 *dd;                                                                  // (dk: 11 (re, im) pairs as floats)
+        FMXCHK(M.alloc(dd, 11));
+        FMXCHK(M.upload(R.rrc, rr));
         HIPCHK(hipMemcpy(dd, dk.data(), sizeof(float2) * 11, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dr, rr.data(), sizeof(float) * 45, hipMemcpyHostToDevice));
-        R.dec_taps = dd; R.rrc = dr;
+        R.dec_taps = dd;
     }
     {   // RDS_1: Costas state, rdsFilter / Match / sharpFilter coefficients (rds-decoder-1.cpp:43-100), rings at 24 kS/s
-        if ((rc = dalloc((void **)&R.c_ring, sizeof(float) * C * RDS24_RING, true))) return rc;
-        if ((rc = dalloc((void **)&R.f_ring, sizeof(float) * C * RDS24_RING, true))) return rc;
-        if ((rc = dalloc((void **)&R.state1, sizeof(Rds1State) * C, true))) return rc;
+        FMXCHK(M.alloc(R.c_ring, C * RDS24_RING, true));
+        FMXCHK(M.alloc(R.f_ring, C * RDS24_RING, true));
+        FMXCHK(M.alloc(R.state1, C, true));
         std::vector<float> co = design::lowpass(RDS1_FIR, 2 * 2400, 24000);            // rdsFilter (21, RDS_WIDTH, rate)
         const std::vector<float> mk = design::rds1_match_kernel(24000);
         if ((int)mk.size() != RDS1_MATCH) return fail(FMX_E_HIP, "unexpected length of the RDS_1 matched filter");
@@ -486,26 +496,20 @@ int ensure_rds_body(fmx_handle h) {
         if (bp.nq != RDS1_QUADS) return fail(FMX_E_HIP, "unexpected biquad count of the RDS_1 band-pass");
         for (int i = 0; i < RDS1_QUADS; i++) { co.push_back(bp.q[i][1]); co.push_back(bp.q[i][2]); co.push_back(bp.q[i][4]); co.push_back(bp.q[i][5]); }
         co.push_back(bp.gain);
-        float *dc;
-        if ((rc = dalloc((void **)&dc, sizeof(float) * co.size(), false))) return rc;
-        HIPCHK(hipMemcpy(dc, co.data(), sizeof(float) * co.size(), hipMemcpyHostToDevice));
-        R.rds1_coef = dc; h->h_rds1 = co;
+        FMXCHK(M.upload(R.rds1_coef, co));
+        h->h_rds1 = co;
     }
     {   // RDS_3: state, and mySinCos (rate) of rdsDecoder_3 (rds-decoder-3.cpp:49): SinCos ctor sincos.cpp:45-54 at Rate 24000
-        if ((rc = dalloc((void **)&R.state3, sizeof(Rds3State) * C, true))) return rc;
+        FMXCHK(M.alloc(R.state3, C, true));
         std::vector<float2> sc24(24000);
         for (int i = 0; i < 24000; i++) sc24[i] = make_float2((float)std::cos(2 * design::kPi * i / 24000), (float)std::sin(2 * design::kPi * i / 24000));
-        float2 *d24;
-        if ((rc = dalloc((void **)&d24, sizeof(float2) * 24000, false))) return rc;
-        HIPCHK(hipMemcpy(d24, sc24.data(), sizeof(float2) * 24000, hipMemcpyHostToDevice));
-        R.sincos24 = d24;
+        FMXCHK(M.upload(R.sincos24, sc24));
     }
     h->rds_read.assign(C, 0);
     {
-        int *cl = nullptr;
-        if ((rc = dalloc((void **)&h->d_rds_nc0, sizeof(int64_t) * C, true))) return rc;
-        if ((rc = dalloc((void **)&cl, sizeof(int) * C, true))) return rc;
-        R.nc0 = h->d_rds_nc0; R.chlist = cl;
+        FMXCHK(M.alloc(h->d_rds_nc0, C, true));
+        FMXCHK(M.alloc(R.chlist, C, true));
+        R.nc0 = h->d_rds_nc0;
         h->rds_nc.assign(C, 0); h->rds_nc0.assign(C, -1); h->last_m0.assign(C, 0); h->last_m1.assign(C, 0);
     }
     h->rds_alloc = true;
@@ -516,33 +520,26 @@ int ensure_rds_body(fmx_handle h) {
 int ola_alloc_side(fmx_handle h, fmx_handle_s::OlaSide &S, int L, int degree) {
     const size_t C = (size_t)h->channels;
     S.L = L; S.degree = degree;
-    HIPCHK(hipMalloc(&S.A, sizeof(float2) * C * L)); HIPCHK(hipMemset(S.A, 0, sizeof(float2) * C * L));
-    HIPCHK(hipMalloc(&S.C, sizeof(float2) * C * L)); HIPCHK(hipMemset(S.C, 0, sizeof(float2) * C * L));
-    HIPCHK(hipMalloc(&S.over, sizeof(float2) * C * OLA_MAX_TAPS)); HIPCHK(hipMemset(S.over, 0, sizeof(float2) * C * OLA_MAX_TAPS));
-    HIPCHK(hipMalloc(&S.over_new, sizeof(float2) * C * OLA_MAX_TAPS)); HIPCHK(hipMemset(S.over_new, 0, sizeof(float2) * C * OLA_MAX_TAPS));
-    HIPCHK(hipMalloc(&S.taps, sizeof(float) * C * OLA_MAX_TAPS)); HIPCHK(hipMemset(S.taps, 0, sizeof(float) * C * OLA_MAX_TAPS));
+    FMXCHK(h->mem.alloc(S.A, C * L, true));
+    FMXCHK(h->mem.alloc(S.C, C * L, true));
+    FMXCHK(h->mem.alloc(S.over, C * OLA_MAX_TAPS, true));
+    FMXCHK(h->mem.alloc(S.over_new, C * OLA_MAX_TAPS, true));
+    FMXCHK(h->mem.alloc(S.taps, C * OLA_MAX_TAPS, true));
     S.inp.assign(C, 0); S.on.assign(C, 0); S.key.assign(C, -1);
-    for (void *p : {(void *)S.A, (void *)S.C, (void *)S.over, (void *)S.over_new, (void *)S.taps}) h->tail_ptrs.push_back(p);
     return FMX_OK;
 }
 int ensure_ola(fmx_handle h) {
     if (h->d_v) return FMX_OK;
     const size_t C = (size_t)h->channels;
-    HIPCHK(hipMalloc(&h->d_v, sizeof(float2) * C * h->cfg.max_block));
-    HIPCHK(hipMalloc(&h->d_u, sizeof(float2) * C * h->cfg.max_block));
-    HIPCHK(hipMalloc(&h->d2ring, sizeof(float2) * C * h->dring));
-    HIPCHK(hipMemset(h->d2ring, 0, sizeof(float2) * C * h->dring));
-    for (void *p : {(void *)h->d_v, (void *)h->d_u, (void *)h->d2ring}) h->tail_ptrs.push_back(p);
+    FMXCHK(h->mem.alloc(h->d_v, C * h->cfg.max_block));
+    FMXCHK(h->mem.alloc(h->d_u, C * h->cfg.max_block));
+    FMXCHK(h->mem.alloc(h->d2ring, C * h->dring, true));
     h->pre_look.max_tiles = (int32_t)(h->cfg.max_block / PRE_TILE_SAMPLES + 1);
-    HIPCHK(hipMalloc(&h->pre_look.maps, sizeof(float4) * C * h->pre_look.max_tiles));
-    HIPCHK(hipMalloc(&h->pre_look.flags, sizeof(int32_t) * C * h->pre_look.max_tiles));
-    HIPCHK(hipMemset(h->pre_look.flags, 0, sizeof(int32_t) * C * h->pre_look.max_tiles));
-    HIPCHK(hipMalloc(&h->pre_look.tickets, sizeof(uint32_t) * C));
-    HIPCHK(hipMemset(h->pre_look.tickets, 0, sizeof(uint32_t) * C));
+    FMXCHK(h->mem.alloc(h->pre_look.maps, C * h->pre_look.max_tiles));
+    FMXCHK(h->mem.alloc(h->pre_look.flags, C * h->pre_look.max_tiles, true));
+    FMXCHK(h->mem.alloc(h->pre_look.tickets, C, true));
     h->pre_look.ticket_base = 0;
-    h->tail_ptrs.push_back(h->pre_look.maps); h->tail_ptrs.push_back(h->pre_look.flags); h->tail_ptrs.push_back(h->pre_look.tickets);
-    int rc = ola_alloc_side(h, h->ola_in, 2 * 32768 - 251, 251);          // inputFilter (2 * 32768, 251) fm-processor.cpp:77
-    if (rc) return rc;
+    FMXCHK(ola_alloc_side(h, h->ola_in, 2 * 32768 - 251, 251));          // inputFilter (2 * 32768, 251) fm-processor.cpp:77
     return ola_alloc_side(h, h->ola_au, 2 * 4096 - AUDIO_TAPS, AUDIO_TAPS);   // fmAudioFilter (2 * 4096, 756) :76
 }
 // setBandwidth / setlfcutoff as the reference's loop takes them over at a block start (fm-processor.cpp:396-408): a new value designs the
@@ -576,10 +573,9 @@ int step_ref(fmx_handle h, const HStep &st, hipStream_t s, OlaStepRef *out) {
     if (h->channels <= OLA_MAX_CH) { for (int c = 0; c < h->channels; c++) out->val.ch[c] = st.ch[(size_t)c]; return FMX_OK; }
     const size_t C = (size_t)h->channels;
     if (!h->step_dev) {
-        HIPCHK(hipMalloc(&h->step_dev, sizeof(OlaChan) * C * fmx_handle_s::STEP_SLOTS));
-        HIPCHK(hipHostMalloc((void **)&h->step_host, sizeof(OlaChan) * C * fmx_handle_s::STEP_SLOTS, hipHostMallocDefault));
+        FMXCHK(h->mem.alloc(h->step_dev, C * fmx_handle_s::STEP_SLOTS));
+        FMXCHK(h->mem.alloc_pinned(h->step_host, C * fmx_handle_s::STEP_SLOTS));
         for (auto &e : h->step_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->tail_ptrs.push_back(h->step_dev);
     }
     const int k = h->step_next; h->step_next = (k + 1) % fmx_handle_s::STEP_SLOTS;
     if (h->step_used[k]) HIPCHK(hipEventSynchronize(h->step_ev[k]));          // (the copy that last used this slot's host side has run)
@@ -667,15 +663,14 @@ int promote(fmx_handle h, hipStream_t s) {
     HIPCHK(hipDeviceSynchronize());
     int rc = ensure_ola(h); if (rc) return rc;
     if (h->h_front_sets.size() > h->old_sets_cap) {
-        if (h->d_old_sets) (void)hipFree(h->d_old_sets);
-        h->d_old_sets = nullptr; h->old_sets_cap = h->h_front_sets.size() + 8;
-        HIPCHK(hipMalloc(&h->d_old_sets, sizeof(FrontSet) * h->old_sets_cap));
+        h->mem.release(h->d_old_sets);
+        h->old_sets_cap = h->h_front_sets.size() + 8;
+        FMXCHK(h->mem.alloc(h->d_old_sets, h->old_sets_cap));
     }
     if (!h->d_old_set_of) {
-        HIPCHK(hipMalloc(&h->d_old_set_of, sizeof(int32_t) * C));
-        HIPCHK(hipMalloc(&h->d_params_replay, sizeof(ChanParams) * C));
-        HIPCHK(hipMalloc(&h->d_au_tail, sizeof(float2) * C * PROMO_TAIL_AU));
-        for (void *p : {(void *)h->d_old_set_of, (void *)h->d_params_replay, (void *)h->d_au_tail}) h->tail_ptrs.push_back(p);
+        FMXCHK(h->mem.alloc(h->d_old_set_of, C));
+        FMXCHK(h->mem.alloc(h->d_params_replay, C));
+        FMXCHK(h->mem.alloc(h->d_au_tail, C * PROMO_TAIL_AU));
     }
     {   // what the folded stage A used: its tap sets' delays (the ring's newest entries move by them), and the parameters the kept samples were taken under
         std::vector<int32_t> set_of(C);
@@ -815,15 +810,11 @@ int ensure_scan(fmx_handle h) {
     HIPCHK(hipDeviceSynchronize());
     std::vector<float2> W((size_t)scan::N);
     scan::make_twiddles(W.data());
-    HIPCHK(hipMalloc(&h->d_scan_W, sizeof(float2) * scan::N));
-    HIPCHK(hipMemcpy(h->d_scan_W, W.data(), sizeof(float2) * scan::N, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&h->d_scan_carry, sizeof(float2) * C * scan::N));
-    HIPCHK(hipMemset(h->d_scan_carry, 0, sizeof(float2) * C * scan::N));
-    HIPCHK(hipMalloc(&h->d_scan_rec, sizeof(float2) * C * scan::RING));
-    HIPCHK(hipMemset(h->d_scan_rec, 0, sizeof(float2) * C * scan::RING));
-    HIPCHK(hipMalloc(&h->d_scan_jobs, sizeof(ScanJob) * C));
-    HIPCHK(hipMalloc(&h->d_scan_mute, sizeof(int32_t) * C));
-    for (void *p : {(void *)h->d_scan_W, (void *)h->d_scan_carry, (void *)h->d_scan_rec, (void *)h->d_scan_jobs, (void *)h->d_scan_mute}) h->tail_ptrs.push_back(p);
+    FMXCHK(h->mem.upload(h->d_scan_W, W));
+    FMXCHK(h->mem.alloc(h->d_scan_carry, C * scan::N, true));
+    FMXCHK(h->mem.alloc(h->d_scan_rec, C * scan::RING, true));
+    FMXCHK(h->mem.alloc(h->d_scan_jobs, C));
+    FMXCHK(h->mem.alloc(h->d_scan_mute, C));
     h->scan_fill.assign(C, 0); h->scan_blocks.assign(C, 0); h->scan_read.assign(C, 0);
     h->scan_end.assign(C * scan::RING, 0); h->scan_rec_thr.assign(C * scan::RING, 0);
     h->scan_alloc = true;
@@ -837,11 +828,8 @@ constexpr int PLL_SEQ_AUTO_MAX = 64;   // FMX_P_PLL_SOLVER = 0: handles up to th
 int ensure_prepass_arrays(fmx_handle h) {
     if (h->B.w_iq) return FMX_OK;
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMalloc(&h->B.w_iq, sizeof(float2) * (size_t)h->work_nj * h->pitch));
-    HIPCHK(hipMemset(h->B.w_iq, 0, sizeof(float2) * (size_t)h->work_nj * h->pitch));
-    HIPCHK(hipMalloc(&h->B.w_osc, sizeof(float) * (size_t)h->work_nj * h->pitch));
-    HIPCHK(hipMemset(h->B.w_osc, 0, sizeof(float) * (size_t)h->work_nj * h->pitch));
-    return FMX_OK;
+    FMXCHK(h->mem.alloc(h->B.w_iq, (size_t)h->work_nj * h->pitch, true));
+    return h->mem.alloc(h->B.w_osc, (size_t)h->work_nj * h->pitch, true);
 }
 int flush_mailbox(fmx_handle h) {
     std::lock_guard<std::mutex> lk(h->mtx);
@@ -909,9 +897,7 @@ int flush_mailbox(fmx_handle h) {
         const bool keep = want < 0 ? h->channels <= 64 : want != 0;
         if (keep && !h->w_diff_mem) {
             HIPCHK(hipDeviceSynchronize());
-            HIPCHK(hipMalloc(&h->w_diff_mem, sizeof(float) * (size_t)h->work_nj * h->pitch));
-            HIPCHK(hipMemset(h->w_diff_mem, 0, sizeof(float) * (size_t)h->work_nj * h->pitch));
-            h->tail_ptrs.push_back(h->w_diff_mem);
+            FMXCHK(h->mem.alloc(h->w_diff_mem, (size_t)h->work_nj * h->pitch, true));
         }
         h->B.w_diff = keep ? h->w_diff_mem : nullptr;
         h->taps_kept = keep;
@@ -926,7 +912,7 @@ int flush_mailbox(fmx_handle h) {
     }
     bool any_nsq = false;
     for (auto &p : h->params) any_nsq |= (p.squelch_mode == 1);
-    if (any_nsq && !h->d_nsq) {
+    if (any_nsq && !h->T.nsq_coef) {
         // squelch ctor squelchClass.cpp:11-18 with mySquelch (1, 70000, fmRate / 20, fmRate) fm-processor.cpp:87
         const design::Iir hp = design::iir_chebyshev_lowhigh(true, 20, 70000 - 100, h->cfg.fmRate);
         const design::Iir lp = design::iir_chebyshev_lowhigh(false, 20, 70000, h->cfg.fmRate);
@@ -941,9 +927,7 @@ int flush_mailbox(fmx_handle h) {
             h->h_nsq[2 * NSQ_QUADS * 4 + f] = F.gain;
         }
         HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMalloc(&h->d_nsq, sizeof(float) * h->h_nsq.size()));
-        HIPCHK(hipMemcpy(h->d_nsq, h->h_nsq.data(), sizeof(float) * h->h_nsq.size(), hipMemcpyHostToDevice));
-        h->T.nsq_coef = h->d_nsq; h->tail_ptrs.push_back(h->d_nsq);
+        FMXCHK(h->mem.upload(h->T.nsq_coef, h->h_nsq));
     }
     if (any_pll) { const int rc = ensure_prepass_arrays(h); if (rc) return rc; }
     for (int c = 0; c < h->channels; c++) {            // set_squelchValue takes effect at a block start, when it differs (fm-processor.cpp:410-413)
@@ -1051,9 +1035,8 @@ int capture_samples(fmx_handle h, const void *d_iq, const CallArgs &a, const Cal
     if (h->tail_iq && h->promo_have + G.n > h->tail_cap) return FMX_OK;      // (cannot happen: a change is applied at the first call boundary behind PROMO_TAIL_IN samples)
     if (!h->tail_iq) {
         h->tail_cap = PROMO_TAIL_IN + h->cfg.max_block;
-        HIPCHK(hipMalloc(&h->tail_iq, sizeof(float2) * (size_t)h->streams * h->tail_cap));
-        HIPCHK(hipMalloc(&h->tail_snap, sizeof(FrontSnap) * (size_t)h->channels));
-        h->tail_ptrs.push_back(h->tail_iq); h->tail_ptrs.push_back(h->tail_snap);
+        FMXCHK(h->mem.alloc(h->tail_iq, (size_t)h->streams * h->tail_cap));
+        FMXCHK(h->mem.alloc(h->tail_snap, (size_t)h->channels));
     }
     if (h->promo_have == 0) { h->promo_g0 = h->g_total; launch_promo_state(h->B.state, h->tail_snap, h->channels, 0, sa); FMX_LAUNCHED(); }
     launch_capture(d_iq, a.fmt, G.iq_scale, a.stream_stride, G.n, h->streams, h->tail_iq, h->tail_cap, h->promo_have, sa); FMX_LAUNCHED();
@@ -1068,11 +1051,10 @@ int stage_a(fmx_handle h, CallGeom &G, const void *d_iq, hipStream_t s, hipStrea
     if (fp.parts > 1 && !h->B.fsnap) {
         const size_t C = (size_t)h->channels;
         h->B.dc_pitch = (int32_t)(h->cfg.max_block / FRONT_TILE + 2);
-        HIPCHK(hipMalloc(&h->B.dc_tiles, sizeof(float4) * 2 * (size_t)h->streams * h->B.dc_pitch));
-        HIPCHK(hipMalloc(&h->B.fsnap, sizeof(FrontSnap) * C));
-        HIPCHK(hipMalloc(&h->B.hist_snap, sizeof(float2) * C * DECIM * A_HIST_COLS));
-        HIPCHK(hipMalloc(&h->B.dcv_snap, sizeof(float2) * C * DCV_SAVE));
-        for (void *p : {(void *)h->B.dc_tiles, (void *)h->B.fsnap, (void *)h->B.hist_snap, (void *)h->B.dcv_snap}) h->tail_ptrs.push_back(p);
+        FMXCHK(h->mem.alloc(h->B.dc_tiles, 2 * (size_t)h->streams * h->B.dc_pitch));
+        FMXCHK(h->mem.alloc(h->B.fsnap, C));
+        FMXCHK(h->mem.alloc(h->B.hist_snap, C * DECIM * A_HIST_COLS));
+        FMXCHK(h->mem.alloc(h->B.dcv_snap, C * DCV_SAVE));
     }
     G.parts = fp.parts; G.part_tiles = fp.part_tiles;
     // automatic: the filter on the matrix pipe wherever a handle qualifies and has the channels to fill the chip without splitting them in time
@@ -1369,14 +1351,13 @@ __global__ __launch_bounds__(256) void stream_probe_kernel(const f32x4_t *__rest
 }
 }  // namespace fmx
 
-extern "C" {
+namespace {
 
-int fmx_abi_version(void) { return FMX_ABI_VERSION; }
-const char *fmx_last_error(void) { return g_err.c_str(); }
+// ---- fmx_create, step by step -------------------------------------------------------------------------------------------
+struct Conv2Design { int p = 1, q = 1, nt = 0; std::vector<float> taps; };     // the second converter (audioRate != workingRate), design::design_conv2
 
-int fmx_create(const fmx_config *cfg, fmx_handle *out) {
-    if (!cfg || !out) return fail(FMX_E_INVALID, "null argument");
-    (void)env_switches();                       // (the FMX_* environment switches: read here, once per process)
+// 1. the configuration: what this build implements, the reference's total decimation for cfg.inputRate, the second converter
+int validate_config(const fmx_config *cfg, int *decim_out, Conv2Design *cv) {
     if (cfg->struct_size != (int32_t)sizeof(fmx_config)) return fail(FMX_E_INVALID, "fmx_config.struct_size mismatch");
     if (cfg->channels < 1) return fail(FMX_E_INVALID, "channels must be >= 1");
     if (cfg->fmRate != 192000 || cfg->workingRate != 48000)
@@ -1398,10 +1379,10 @@ int fmx_create(const fmx_config *cfg, fmx_handle *out) {
             decim = 6 * (int)d2;
         }
     }
-    std::vector<float> cv_taps; int cv_p = 1, cv_q = 1, cv_nt = 0;
+    *decim_out = decim;
     if (cfg->audioRate != cfg->workingRate) {
         if (cfg->audioRate < 8000 || cfg->audioRate > 192000 ||
-            !design::design_conv2(cfg->workingRate, cfg->audioRate, &cv_p, &cv_q, &cv_nt, &cv_taps))
+            !design::design_conv2(cfg->workingRate, cfg->audioRate, &cv->p, &cv->q, &cv->nt, &cv->taps))
             return fail(FMX_E_UNSUPPORTED, "audioRate: 8000 .. 192000 with audioRate / gcd (audioRate, workingRate) <= 640 (the second converter's phases)");
     }
     if (cfg->max_block < 12 || cfg->max_block > (1 << 20)) return fail(FMX_E_INVALID, "max_block must be in [12, 1048576]");
@@ -1409,23 +1390,18 @@ int fmx_create(const fmx_config *cfg, fmx_handle *out) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(FMX_E_NO_DEVICE, "no HIP device visible: libfmx has no CPU fallback");
     if (cfg->device < 0 || cfg->device >= ndev) return fail(FMX_E_INVALID, "device ordinal out of range");
-    HIPCHK(hipSetDevice(cfg->device));
+    return FMX_OK;
+}
 
-    fmx_handle h = new (std::nothrow) fmx_handle_s();
-    if (!h) return fail(FMX_E_NOMEM, "out of host memory");
-    // every failure below goes through fmx_destroy: nothing of a half-built handle stays behind
-    auto init = [&]() -> int {
+// 2. the handle's shape, every channel's constructor defaults and its stream
+int init_channels(fmx_handle h, const fmx_config *cfg, int decim, const Conv2Design &cv) {
     h->cfg = *cfg; h->cfg.stream_of_channel = nullptr;
     h->decim = decim; h->twins = DECIM / decim;
     h->channels = cfg->channels;
     h->streams = cfg->streams > 0 ? cfg->streams : cfg->channels;
-    if (cv_nt) {
-        h->cv_p = cv_p; h->cv_q = cv_q; h->cv_nt = cv_nt;
-        h->x48_stride = cv_nt + cfg->max_block / (4 * h->decim) + 96;
-        HIPCHK(hipMalloc(&h->d_cv_taps, sizeof(float) * cv_taps.size()));
-        HIPCHK(hipMemcpy(h->d_cv_taps, cv_taps.data(), sizeof(float) * cv_taps.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc(&h->d_x48, sizeof(float2) * (size_t)h->channels * h->x48_stride));
-        HIPCHK(hipMemset(h->d_x48, 0, sizeof(float2) * (size_t)h->channels * h->x48_stride));
+    if (cv.nt) {
+        h->cv_p = cv.p; h->cv_q = cv.q; h->cv_nt = cv.nt;
+        h->x48_stride = cv.nt + cfg->max_block / (4 * h->decim) + 96;
     }
     h->ola_mode = h->channels <= OLA_MAX_CH;          // FMX_P_FILTER_RESTARTS = 0 (automatic)
     h->user.assign(h->channels, ChanUser());
@@ -1443,100 +1419,94 @@ int fmx_create(const fmx_config *cfg, fmx_handle *out) {
         p.squelch_mode = 0; p.squelch_thr = std::pow(10.0f, (float)(1 - 80) / 30.0f); p.squelch_nthr = 1.0f - 1 / 100.0f;
         refresh_derived(h, c);
     }
-    {
-        std::vector<int> users((size_t)h->streams, 0);
-        h->streams_private = true;
-        for (auto &p : h->params) if (++users[(size_t)p.stream] > 1) h->streams_private = false;
-    }
-    {
-        hipDeviceProp_t dp;
-        HIPCHK(hipGetDeviceProperties(&dp, cfg->device));
-        h->n_cus = dp.multiProcessorCount;
-        int optin = 0;
-        if (hipDeviceGetAttribute(&optin, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg->device) != hipSuccess) optin = 0;
-        h->lds_per_block = std::max((size_t)dp.sharedMemPerBlock, (size_t)optin);
-    }
+    std::vector<int> users((size_t)h->streams, 0);
+    h->streams_private = true;
+    for (auto &p : h->params) if (++users[(size_t)p.stream] > 1) h->streams_private = false;
+    return FMX_OK;
+}
+
+// 3. the device's limits, the handle's stream and event
+int init_device(fmx_handle h) {
+    hipDeviceProp_t dp;
+    HIPCHK(hipGetDeviceProperties(&dp, h->cfg.device));
+    h->n_cus = dp.multiProcessorCount;
+    int optin = 0;
+    if (hipDeviceGetAttribute(&optin, hipDeviceAttributeMaxSharedMemoryPerBlock, h->cfg.device) != hipSuccess) optin = 0;
+    h->lds_per_block = std::max((size_t)dp.sharedMemPerBlock, (size_t)optin);
     HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
+    return FMX_OK;
+}
 
-    // ---- tables -------------------------------------------------------------------------
-    const int32_t fmRate = cfg->fmRate;
-    {
-        std::vector<float2> sc((size_t)SINCOS_N);                       // SinCos ctor sincos.cpp:45-54
-        for (int i = 0; i < SINCOS_N; i++)
-            sc[i] = make_float2((float)std::cos(2 * design::kPi * i / fmRate), (float)std::sin(2 * design::kPi * i / fmRate));
-        HIPCHK(hipMalloc(&h->d_sincos, sizeof(float2) * SINCOS_N));
-        HIPCHK(hipMemcpy(h->d_sincos, sc.data(), sizeof(float2) * SINCOS_N, hipMemcpyHostToDevice));
-        {   // the table as two polynomials (SinPoly): accept it only if it reproduces every entry, bar a few listed exceptions
-            SinPoly sp{}; sp.step = 2 * design::kPi / fmRate;
-            bool fits = (fmRate == SINCOS_N);
-            for (int i = 0; fits && i < SINCOS_N; i++) {
-                float sn, cs;
-                sincos_poly(i, sp.step, &sn, &cs);
-                if (std::memcmp(&sn, &sc[i].y, 4) != 0) { if (sp.ns < 4) { sp.s_idx[sp.ns] = i; sp.s_val[sp.ns] = sc[i].y; sp.ns++; } else fits = false; }
-                if (std::memcmp(&cs, &sc[i].x, 4) != 0) { if (sp.nc < 4) { sp.c_idx[sp.nc] = i; sp.c_val[sp.nc] = sc[i].x; sp.nc++; } else fits = false; }
-            }
-            sp.ok = fits ? 1 : 0;
-            h->T.sp = sp;
+// 4a. the trigonometric tables: SinCos and the three bit-exactness checks of what the kernels use in its place, atan, arcsine
+int build_trig_tables(fmx_handle h) {
+    const int32_t fmRate = h->cfg.fmRate;
+    std::vector<float2> sc((size_t)SINCOS_N);                       // SinCos ctor sincos.cpp:45-54
+    for (int i = 0; i < SINCOS_N; i++)
+        sc[i] = make_float2((float)std::cos(2 * design::kPi * i / fmRate), (float)std::sin(2 * design::kPi * i / fmRate));
+    FMXCHK(h->mem.upload(h->T.sincos, sc));
+    {   // the table as two polynomials (SinPoly): accept it only if it reproduces every entry, bar a few listed exceptions
+        SinPoly sp{}; sp.step = 2 * design::kPi / fmRate;
+        bool fits = (fmRate == SINCOS_N);
+        for (int i = 0; fits && i < SINCOS_N; i++) {
+            float sn, cs;
+            sincos_poly(i, sp.step, &sn, &cs);
+            if (std::memcmp(&sn, &sc[i].y, 4) != 0) { if (sp.ns < 4) { sp.s_idx[sp.ns] = i; sp.s_val[sp.ns] = sc[i].y; sp.ns++; } else fits = false; }
+            if (std::memcmp(&cs, &sc[i].x, 4) != 0) { if (sp.nc < 4) { sp.c_idx[sp.nc] = i; sp.c_val[sp.nc] = sc[i].x; sp.nc++; } else fits = false; }
         }
-        {   // 2-level factorisation of the sine column for the sequential pilot PLL (LDS resident):
-            // sin(2 pi idx/N) = Im(EA[a] EB[b]), idx = 256 a + b.  Used only if the f64 expression rounds to
-            // exactly the reference's f32 table entry for EVERY idx (checked here with the same unfused
-            // multiply/add sequence the kernel runs); otherwise the kernel reads the global table.
-            std::vector<double2> tr((size_t)TRIG2_N);
-            for (int a = 0; a < TRIG2_A; a++) { double t = 2 * design::kPi * (256.0 * a) / fmRate; tr[a] = make_double2(std::cos(t), std::sin(t)); }
-            for (int a = 0; a < TRIG2_APAD; a++) tr[TRIG2_A + a] = tr[a];          // idx in [N, N + 512) wraps to idx - N
-            for (int b = 0; b < TRIG2_B; b++) { double t = 2 * design::kPi * (double)b / fmRate; tr[TRIG2_A + TRIG2_APAD + b] = make_double2(std::cos(t), std::sin(t)); }
-            bool exact = (fmRate == TRIG2_A * TRIG2_B);
-            for (int i = 0; exact && i < SINCOS_N; i++) {
-                const double2 ea = tr[i >> 8], eb = tr[TRIG2_A + TRIG2_APAD + (i & 255)];
-                const float sn = (float)(ea.y * eb.x + ea.x * eb.y);
-                if (std::memcmp(&sn, &sc[i].y, 4) != 0) exact = false;
-            }
-            if (exact) {
-                HIPCHK(hipMalloc(&h->d_trig3, sizeof(double2) * TRIG2_N));
-                HIPCHK(hipMemcpy(h->d_trig3, tr.data(), sizeof(double2) * TRIG2_N, hipMemcpyHostToDevice));
-            }
-        }
-        {   // the pilot-phase wrap: (float)((double)v - 2 pi) == (v - P32) + C32 in f32 for every float v the PLL can
-            // produce there, v in [P32, P32 + 0.7)?  (P32 = the float just above 2 pi.)  Checked bit for bit.
-            const float P32 = 6.2831855f;
-            const float C32 = (float)((double)P32 - 2 * design::kPi);
-            bool ok = true;
-            for (float v = P32; ok && v < P32 + 0.7f; v = std::nextafterf(v, 100.f)) {
-                const float want = (float)((double)v - 2 * design::kPi);
-                volatile float d = v - P32;
-                const float got = d + C32;
-                if (std::memcmp(&want, &got, 4) != 0) ok = false;
-            }
-            h->T.wrap32_c = C32; h->T.wrap32_ok = ok ? 1 : 0;
-        }
-        std::vector<float> at((size_t)ATAN_N + 1);                      // compAtan ctor Xtan2.cpp:28-31
-        const float St = (float)design::kPi;
-        for (int i = 0; i <= ATAN_N; i++) { float f = (float)i / ATAN_N; at[i] = (float)((double)(std::atan(f) * St) / design::kPi); }
-        HIPCHK(hipMalloc(&h->d_atan, sizeof(float) * (ATAN_N + 1)));
-        HIPCHK(hipMemcpy(h->d_atan, at.data(), sizeof(float) * (ATAN_N + 1), hipMemcpyHostToDevice));
-        std::vector<float> as((size_t)ARCSINE_N + 1);                   // fm-demodulator.cpp:74-77
-        for (int i = 0; i <= ARCSINE_N; i++) as[i] = (float)(std::asin(2.0 * i / ARCSINE_N - 1.0) / 2.0);
-        HIPCHK(hipMalloc(&h->d_arcsine, sizeof(float) * (ARCSINE_N + 1)));
-        HIPCHK(hipMemcpy(h->d_arcsine, as.data(), sizeof(float) * (ARCSINE_N + 1), hipMemcpyHostToDevice));
-        h->h_pss_taps = design::lowpass(PSS_TAPS, 15000, fmRate);      // stereo-separation.cpp:31,39
-        HIPCHK(hipMalloc(&h->d_pss_taps, sizeof(float) * PSS_TAPS));
-        HIPCHK(hipMemcpy(h->d_pss_taps, h->h_pss_taps.data(), sizeof(float) * PSS_TAPS, hipMemcpyHostToDevice));
-        h->h_rs_taps = design::resampler(RS_TAPS);
+        sp.ok = fits ? 1 : 0;
+        h->T.sp = sp;
     }
-    h->T.sincos = h->d_sincos; h->T.atan_ppy = h->d_atan; h->T.arcsine = h->d_arcsine; h->T.lo_table = nullptr; h->T.trig2 = h->d_trig3;
-    h->T.pss_taps = h->d_pss_taps;
+    {   // 2-level factorisation of the sine column for the sequential pilot PLL (LDS resident):
+        // sin(2 pi idx/N) = Im(EA[a] EB[b]), idx = 256 a + b.  Used only if the f64 expression rounds to
+        // exactly the reference's f32 table entry for EVERY idx (checked here with the same unfused
+        // multiply/add sequence the kernel runs); otherwise the kernel reads the global table.
+        std::vector<double2> tr((size_t)TRIG2_N);
+        for (int a = 0; a < TRIG2_A; a++) { double t = 2 * design::kPi * (256.0 * a) / fmRate; tr[a] = make_double2(std::cos(t), std::sin(t)); }
+        for (int a = 0; a < TRIG2_APAD; a++) tr[TRIG2_A + a] = tr[a];          // idx in [N, N + 512) wraps to idx - N
+        for (int b = 0; b < TRIG2_B; b++) { double t = 2 * design::kPi * (double)b / fmRate; tr[TRIG2_A + TRIG2_APAD + b] = make_double2(std::cos(t), std::sin(t)); }
+        bool exact = (fmRate == TRIG2_A * TRIG2_B);
+        for (int i = 0; exact && i < SINCOS_N; i++) {
+            const double2 ea = tr[i >> 8], eb = tr[TRIG2_A + TRIG2_APAD + (i & 255)];
+            const float sn = (float)(ea.y * eb.x + ea.x * eb.y);
+            if (std::memcmp(&sn, &sc[i].y, 4) != 0) exact = false;
+        }
+        if (exact) FMXCHK(h->mem.upload(h->T.trig2, tr));
+    }
+    {   // the pilot-phase wrap: (float)((double)v - 2 pi) == (v - P32) + C32 in f32 for every float v the PLL can
+        // produce there, v in [P32, P32 + 0.7)?  (P32 = the float just above 2 pi.)  Checked bit for bit.
+        const float P32 = 6.2831855f;
+        const float C32 = (float)((double)P32 - 2 * design::kPi);
+        bool ok = true;
+        for (float v = P32; ok && v < P32 + 0.7f; v = std::nextafterf(v, 100.f)) {
+            const float want = (float)((double)v - 2 * design::kPi);
+            volatile float d = v - P32;
+            const float got = d + C32;
+            if (std::memcmp(&want, &got, 4) != 0) ok = false;
+        }
+        h->T.wrap32_c = C32; h->T.wrap32_ok = ok ? 1 : 0;
+    }
+    std::vector<float> at((size_t)ATAN_N + 1);                      // compAtan ctor Xtan2.cpp:28-31
+    const float St = (float)design::kPi;
+    for (int i = 0; i <= ATAN_N; i++) { float f = (float)i / ATAN_N; at[i] = (float)((double)(std::atan(f) * St) / design::kPi); }
+    FMXCHK(h->mem.upload(h->T.atan_ppy, at));
+    std::vector<float> as((size_t)ARCSINE_N + 1);                   // fm-demodulator.cpp:74-77
+    for (int i = 0; i <= ARCSINE_N; i++) as[i] = (float)(std::asin(2.0 * i / ARCSINE_N - 1.0) / 2.0);
+    return h->mem.upload(h->T.arcsine, as);
+}
+
+// 4b. the PSS low-pass and its spectrum, the resampler's taps, the DeviceTables scalars
+int build_filter_tables(fmx_handle h) {
+    const int32_t fmRate = h->cfg.fmRate;
+    h->h_pss_taps = design::lowpass(PSS_TAPS, 15000, fmRate);      // stereo-separation.cpp:31,39
+    FMXCHK(h->mem.upload(h->T.pss_taps, h->h_pss_taps));
+    h->h_rs_taps = design::resampler(RS_TAPS);
     {   // fast-convolution form of the PSS low-pass (fmx_fftconv.h): twiddles and the taps' spectrum in the device transform's own order
         std::vector<float2> W(fftc::W_COUNT), Hs(fftc::N);
         fftc::make_twiddles(W.data());
         fftc::make_spectrum(h->h_pss_taps.data(), PSS_TAPS, Hs.data(), W.data());
-        HIPCHK(hipMalloc(&h->d_fft_w, sizeof(float2) * fftc::W_COUNT));
-        HIPCHK(hipMalloc(&h->d_pss_hs, sizeof(float2) * fftc::N));
-        HIPCHK(hipMemcpy(h->d_fft_w, W.data(), sizeof(float2) * fftc::W_COUNT, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_pss_hs, Hs.data(), sizeof(float2) * fftc::N, hipMemcpyHostToDevice));
-        h->T.fft_w = h->d_fft_w;
-        h->T.pss_hs = h->d_pss_hs;
+        FMXCHK(h->mem.upload(h->T.fft_w, W));
+        FMXCHK(h->mem.upload(h->T.pss_hs, Hs));
     }
     h->T.sincos_C = fmRate / (2 * design::kPi);
     {   // fm_Demodulator ctor fm-demodulator.cpp:57-72
@@ -1557,81 +1527,91 @@ int fmx_create(const fmx_config *cfg, fmx_handle *out) {
     h->T.afc_l2 = (float)std::log2((double)(1 - 0.0001f));                              // fm-demodulator.cpp:197 (1 - fmDcAlpha)
     h->T.lock_l2 = (float)std::log2(1.0 - (double)(1.0f / 3000.0f));                    // pilot-recover.cpp:66 (1.0 - alpha)
     h->T.pssmean_l2 = (float)std::log2((double)(1.0f - h->T.pss_lock_alpha));          // stereo-separation.cpp:90 (1.0f - lockAlpha)
+    return FMX_OK;
+}
 
-    // ---- per-channel buffers ------------------------------------------------------------
-    const int64_t fm_per_call = cfg->max_block / h->decim + 2;
+// 5. the per-channel rings, stage B's work arrays, the PCM tail's buffers, the second converter's, the channels' initial state
+int alloc_channel_buffers(fmx_handle h, const Conv2Design &cv) {
+    DevMem &M = h->mem;
+    DeviceBuffers &B = h->B;
+    const int32_t max_block = h->cfg.max_block;
+    const int64_t fm_per_call = max_block / h->decim + 2;
     h->ring = next_pow2((2 * 32768 - 251) / h->decim + 1 + fm_per_call + 512);      // the input filter's latency in fm samples + a call
     // (a batch keeps three blocks of the audio filter in its d ring: what its promotion to the block machines runs the audio machine over, fmx_promote.hip)
     h->dring = next_pow2(std::max<int64_t>(AUDIO_DELAY + C_MAX_TAPS, h->channels > OLA_MAX_CH ? PROMO_TAIL_AU + 8 : 0) + fm_per_call + 192 + 4 * C_TILE);
     h->sring = 4096;
     const size_t C = (size_t)h->channels;
     const size_t CT = C * (size_t)h->twins;                    // stage-A workgroups: `twins` per channel
-    HIPCHK(hipMalloc(&h->B.hist, sizeof(float2) * CT * DECIM * A_HIST_COLS));
-    HIPCHK(hipMalloc(&h->B.dcv_hist, sizeof(float2) * CT * DCV_SAVE));
-    HIPCHK(hipMemset(h->B.dcv_hist, 0, sizeof(float2) * CT * DCV_SAVE));
-    if (h->twins > 1) {
-        HIPCHK(hipMalloc(&h->B.state_tw, sizeof(ChanState) * C * (size_t)(h->twins - 1)));
-        HIPCHK(hipMemset(h->B.state_tw, 0, sizeof(ChanState) * C * (size_t)(h->twins - 1)));
-        h->tail_ptrs.push_back(h->B.state_tw);
+    if (cv.nt) {
+        FMXCHK(M.upload(h->d_cv_taps, cv.taps));
+        FMXCHK(M.alloc(h->d_x48, C * h->x48_stride, true));
     }
-    HIPCHK(hipMalloc(&h->B.zring, sizeof(float2) * C * h->ring));
-    HIPCHK(hipMalloc(&h->B.sring, sizeof(float2) * C * h->sring));
-    HIPCHK(hipMalloc(&h->B.dring, sizeof(float2) * C * h->dring));
+    FMXCHK(M.alloc(B.hist, CT * DECIM * A_HIST_COLS, true));
+    FMXCHK(M.alloc(B.dcv_hist, CT * DCV_SAVE, true));
+    if (h->twins > 1) FMXCHK(M.alloc(B.state_tw, C * (size_t)(h->twins - 1), true));
+    FMXCHK(M.alloc(B.zring, C * h->ring, true));
+    FMXCHK(M.alloc(B.sring, C * h->sring, true));
+    FMXCHK(M.alloc(B.dring, C * h->dring, true));
     {
         const size_t NJ = (((size_t)fm_per_call + 1 + WT - 1) / WT) * WT;      // whole work-array tiles (widx)
         h->work_nj = (int64_t)NJ;
         h->pitch = ((h->channels + 63) / 64) * 64 + 64;
-        const size_t C = (size_t)h->pitch;   // rows are padded (see CallGeom.pitch)
-        HIPCHK(hipMalloc(&h->B.w_dem, sizeof(float) * NJ * C));
-        HIPCHK(hipMalloc(&h->B.w_cur, sizeof(float) * NJ * C));
-        h->B.w_diff = nullptr;      // (flush_mailbox: FMX_P_SCOPE_TAPS)
-        h->B.lockm_stride = (int32_t)(NJ / 6 + 512);
-        HIPCHK(hipMalloc(&h->B.w_lockm, (size_t)h->B.lockm_stride * C));
-        HIPCHK(hipMemset(h->B.w_lockm, 0, (size_t)h->B.lockm_stride * C));
-        h->tail_ptrs.push_back(h->B.w_lockm);
-        HIPCHK(hipMalloc(&h->B.gfix, sizeof(float2) * GAIN_FIX_FRAMES * C));
-        HIPCHK(hipMemset(h->B.gfix, 0, sizeof(float2) * GAIN_FIX_FRAMES * C));
-        h->B.w_iq = nullptr;
+        const size_t P = (size_t)h->pitch;   // rows are padded (see CallGeom.pitch)
         // the recurrence kernels move whole 64-channel row blocks, pad columns included: keep those finite
-        HIPCHK(hipMemset(h->B.w_dem, 0, sizeof(float) * NJ * C));
-        HIPCHK(hipMemset(h->B.w_cur, 0, sizeof(float) * NJ * C));
+        FMXCHK(M.alloc(B.w_dem, NJ * P, true));
+        FMXCHK(M.alloc(B.w_cur, NJ * P, true));
+        B.lockm_stride = (int32_t)(NJ / 6 + 512);
+        FMXCHK(M.alloc(B.w_lockm, (size_t)B.lockm_stride * P, true));
+        FMXCHK(M.alloc(B.gfix, GAIN_FIX_FRAMES * P, true));
     }
-    HIPCHK(hipMalloc(&h->B.state, sizeof(ChanState) * C));
-    HIPCHK(hipMalloc(&h->d_params, sizeof(ChanParams) * C));
+    {
+        ChanState s0; std::memset(&s0, 0, sizeof(s0));
+        s0.Imin1 = s0.Qmin1 = s0.Imin2 = s0.Qmin2 = (float)0.01;        // fm-demodulator.cpp:79-82
+        FMXCHK(M.upload(B.state, std::vector<ChanState>(C, s0)));
+    }
+    FMXCHK(M.alloc(h->d_params, C));
+    B.params = h->d_params;
     {   // PCM tail: one test-tone burst (fm-processor.cpp:808-813,818-821: float phase += float incr, PI_Constrain, sinf)
         // and the peak meter's per-tile maxima / window ring
         std::vector<float> tone((size_t)TT_BURST);
-        float ph = 0.0f; const float inc = (float)(2 * design::kPi / cfg->workingRate * 1000.0f);
+        float ph = 0.0f; const float inc = (float)(2 * design::kPi / h->cfg.workingRate * 1000.0f);
         for (int i = 0; i < TT_BURST; i++) {
             ph += inc;
             if (!(0 <= ph && ph < 2 * design::kPi)) ph = (float)std::fmod((double)ph, 2 * design::kPi);   // PI_Constrain fm-constants.h:149-153 (ph > 0 here)
             tone[i] = std::sin(ph);
         }
-        float *d_tone = nullptr;
-        HIPCHK(hipMalloc(&d_tone, sizeof(float) * TT_BURST));
-        HIPCHK(hipMemcpy(d_tone, tone.data(), sizeof(float) * TT_BURST, hipMemcpyHostToDevice));
-        h->B.tone = d_tone; h->tail_ptrs.push_back(d_tone);
-        h->B.pk_tiles = (int32_t)((cfg->max_block / (4 * h->decim) + 96) / C_TILE + 8);
-        HIPCHK(hipMalloc(&h->B.pk_part, sizeof(float4) * C * h->B.pk_tiles));
-        HIPCHK(hipMalloc(&h->B.pk_ring, sizeof(float2) * C * PK_RING));
-        HIPCHK(hipMemset(h->B.pk_part, 0, sizeof(float4) * C * h->B.pk_tiles));
-        HIPCHK(hipMemset(h->B.pk_ring, 0, sizeof(float2) * C * PK_RING));
-        h->tail_ptrs.push_back(h->B.pk_part); h->tail_ptrs.push_back(h->B.pk_ring);
+        FMXCHK(M.upload(B.tone, tone));
+        B.pk_tiles = (int32_t)((max_block / (4 * h->decim) + 96) / C_TILE + 8);
+        FMXCHK(M.alloc(B.pk_part, C * B.pk_tiles, true));
+        FMXCHK(M.alloc(B.pk_ring, C * PK_RING, true));
     }
-    HIPCHK(hipMemset(h->B.hist, 0, sizeof(float2) * CT * DECIM * A_HIST_COLS));
-    HIPCHK(hipMemset(h->B.zring, 0, sizeof(float2) * C * h->ring));
-    HIPCHK(hipMemset(h->B.sring, 0, sizeof(float2) * C * h->sring));
-    HIPCHK(hipMemset(h->B.dring, 0, sizeof(float2) * C * h->dring));
-    {
-        ChanState s0; std::memset(&s0, 0, sizeof(s0));
-        s0.Imin1 = s0.Qmin1 = s0.Imin2 = s0.Qmin2 = (float)0.01;        // fm-demodulator.cpp:79-82
-        std::vector<ChanState> init(C, s0);
-        HIPCHK(hipMemcpy(h->B.state, init.data(), sizeof(ChanState) * C, hipMemcpyHostToDevice));
-    }
-    h->B.params = h->d_params;
-    return ensure_sets(h);
-    };
-    const int rc = init();
+    return FMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmx_abi_version(void) { return FMX_ABI_VERSION; }
+const char *fmx_last_error(void) { return g_err.c_str(); }
+
+int fmx_create(const fmx_config *cfg, fmx_handle *out) {
+    if (!cfg || !out) return fail(FMX_E_INVALID, "null argument");
+    (void)env_switches();                       // (the FMX_* environment switches: read here, once per process)
+    int decim = DECIM;
+    Conv2Design cv;
+    FMXCHK(validate_config(cfg, &decim, &cv));
+    HIPCHK(hipSetDevice(cfg->device));
+
+    fmx_handle h = new (std::nothrow) fmx_handle_s();
+    if (!h) return fail(FMX_E_NOMEM, "out of host memory");
+    int rc = init_channels(h, cfg, decim, cv);
+    if (!rc) rc = init_device(h);
+    if (!rc) rc = build_trig_tables(h);
+    if (!rc) rc = build_filter_tables(h);
+    if (!rc) rc = alloc_channel_buffers(h, cv);
+    if (!rc) rc = ensure_sets(h);
+    // every failure goes through fmx_destroy: nothing of a half-built handle stays behind
     if (rc) { const std::string msg = g_err; (void)fmx_destroy(h); g_err = msg; return rc; }
     *out = h;
     return FMX_OK;
@@ -1640,24 +1620,12 @@ int fmx_create(const fmx_config *cfg, fmx_handle *out) {
 int fmx_destroy(fmx_handle h) {
     if (!h) return FMX_OK;
     (void)hipSetDevice(h->cfg.device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    for (hipStream_t st : {h->stream, h->pipe_sA, h->pipe_sP, h->pipe_sB}) if (st) (void)hipStreamSynchronize(st);
     for (auto &pr : h->prof) for (int i = 0; i < 4; i++) (void)hipEventDestroy(pr.e[i]);
-    void *ptrs[] = { h->d_audio_spec, h->d_audio_lp, h->d_rs_taps, h->B.gfix, h->d_fft_w, h->d_pss_hs, h->d_front_taps, h->d_audio_taps, h->d_pss_taps, h->d_front_sets, h->d_audio_sets, h->d_sincos,
-                     h->d_lo, h->d_atan, h->d_arcsine, h->d_trig3, h->d_params, h->B.hist, h->B.dcv_hist, h->B.zring,
-                     h->B.sring, h->B.dring, h->B.state, h->d_iq, h->d_pcm, h->B.w_dem, h->B.w_iq, h->B.w_cur,
-                     h->B.w_osc, h->d_cv_taps, h->d_x48 };      // (the LR tap's rows are in tail_ptrs)
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (void *p : h->rds_ptrs) if (p) (void)hipFree(p);
-    for (void *p : h->tail_ptrs) if (p) (void)hipFree(p);
-    if (h->d_old_sets) (void)hipFree(h->d_old_sets);
-    if (h->step_host) (void)hipHostFree(h->step_host);
     for (hipEvent_t e : h->step_ev) if (e) (void)hipEventDestroy(e);
-    if (h->hp_iq) (void)hipHostFree(h->hp_iq);
-    if (h->hp_pcm) (void)hipHostFree(h->hp_pcm);
-    for (hipStream_t st : {h->pipe_sA, h->pipe_sP, h->pipe_sB}) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-    for (hipEvent_t e : {h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
-    if (h->ev_in) (void)hipEventDestroy(h->ev_in);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    for (hipEvent_t e : {h->ev_in, h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
+    for (hipStream_t st : {h->stream, h->pipe_sA, h->pipe_sP, h->pipe_sB}) if (st) (void)hipStreamDestroy(st);
+    h->mem.release_all(); h->rds_mem.release_all();
     delete h;
     return FMX_OK;
 }
@@ -1821,9 +1789,8 @@ int fmx_process_host_raw(fmx_handle h, const void *iq, int32_t format, float s16
     HIPCHK(hipSetDevice(h->cfg.device));
     const int64_t cap = conv2_out(h, h->cfg.max_block / (4 * h->decim) + 96) + 2;
     if (!h->d_iq) {
-        HIPCHK(hipMalloc(&h->d_iq, sizeof(float2) * (size_t)h->streams * h->cfg.max_block));    // sized for the widest format
-        HIPCHK(hipMalloc(&h->d_pcm, sizeof(float2) * (size_t)h->channels * cap));
-        h->pcm_cap = cap;
+        FMXCHK(h->mem.alloc(h->d_iq, (size_t)h->streams * h->cfg.max_block));    // sized for the widest format
+        FMXCHK(h->mem.alloc(h->d_pcm, (size_t)h->channels * cap));
     }
     const size_t bps = (size_t)bytes_per_sample(format);
     // The single receiver's call (one stream, 16384 samples: 128 KB in, 2.7 KB out) spends a third of its time in the two copies' fixed costs
@@ -1833,11 +1800,11 @@ int fmx_process_host_raw(fmx_handle h, const void *iq, int32_t format, float s16
     const size_t in_bytes = bps * (size_t)n * (size_t)h->streams;
     if (in_bytes <= ZC_MAX_IN && (size_t)h->channels * (size_t)cap * sizeof(float2) <= ZC_MAX_IN) {
         if (!h->hp_pcm) {
-            HIPCHK(hipHostMalloc(&h->hp_iq, ZC_MAX_IN, hipHostMallocDefault)); h->hp_iq_bytes = ZC_MAX_IN;
-            HIPCHK(hipHostMalloc((void **)&h->hp_pcm, sizeof(float2) * (size_t)h->channels * cap, hipHostMallocDefault)); h->hp_pcm_cap = cap;
+            FMXCHK(h->mem.alloc_pinned(h->hp_iq, ZC_MAX_IN));
+            FMXCHK(h->mem.alloc_pinned(h->hp_pcm, (size_t)h->channels * cap));
         }
         for (int sidx = 0; sidx < h->streams; sidx++)
-            std::memcpy((char *)h->hp_iq + (size_t)sidx * bps * n, (const char *)iq + (size_t)sidx * bps * stream_stride, bps * (size_t)n);
+            std::memcpy(h->hp_iq + (size_t)sidx * bps * n, (const char *)iq + (size_t)sidx * bps * stream_stride, bps * (size_t)n);
         int64_t got = 0;
         int rc = run_call(h, h->hp_iq, format, s16_den, n, n, h->hp_pcm, cap, &got, h->stream);
         if (rc) return rc;
@@ -2228,9 +2195,9 @@ int fmx_debug_phase_cycles(fmx_handle h, int32_t enable, unsigned long long *out
         HIPCHK(hipMemcpy(tmp.data(), h->B.dbg, nb, hipMemcpyDeviceToHost));
         for (int k = 0; k < DBG_SLOTS; k++) { out[k] = 0; for (int c = 0; c < h->channels; c++) out[k] += tmp[(size_t)c * DBG_SLOTS + k]; }
     }
-    if (enable && !h->B.dbg) { HIPCHK(hipMalloc(&h->B.dbg, nb)); }
+    if (enable && !h->B.dbg) FMXCHK(h->mem.alloc(h->B.dbg, DBG_SLOTS * (size_t)h->channels));
     if (h->B.dbg) HIPCHK(hipMemset(h->B.dbg, 0, nb));
-    if (!enable && h->B.dbg) { (void)hipFree(h->B.dbg); h->B.dbg = nullptr; }
+    if (!enable) h->mem.release(h->B.dbg);
     return FMX_OK;
 }
 
