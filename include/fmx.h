@@ -380,6 +380,44 @@ int  fmx_get_taps(fmx_handle h, int32_t channel, int32_t which, float *dst, int3
 int  fmx_profile_enable(fmx_handle h, int32_t on);
 int  fmx_profile_read(fmx_handle h, fmx_profile *out, int32_t reset);
 
+/* ---- Stage W: wide-band ingest (no counterpart in the reference, whose device handlers deliver one station's 2 304 000 S/s; contract: DESIGN.md
+ * "Stage W").  One object takes `streams` inputs at Rw = factor * 2 304 000 S/s (factor K = 2 .. 16: what a 10 - 20 MS/s receiver delivers) and
+ * produces `outputs` complex f32 streams at 2 304 000 S/s -- one per station -- in exactly the layout fmx_process_device takes: every wide
+ * sample is read from device memory once for all the stations of its stream.  Output m, offset f_m (integer Hz, |f_m| <= Rw / 2 - 150 000):
+ *     v_m [n] = x [n] O (P_m [n]),  P_m [n] = (P_m [n - 1] - f_m) mod Rw,  O (p) = (cos, sin) (2 pi p / Rw) in f64 rounded to f32
+ *                                   (the reference oscillator's integer phase, oscillator.cpp:26-35,49-58, at the wide rate; P_m starts at 0)
+ *     y_m [j] = sum_{i < T} h [i] v_m [jK + K - 1 - i],  T = 16 K + 1,  h = the reference's Blackman low-pass (fir-filters.cpp:41-62) at 400 kHz
+ * f32 accumulation.  The samples in front of the first call are zeros; the last T - 1 samples of every stream and every P_m carry from call to
+ * call, so the outputs do not depend on how a stream is cut into calls (bit for bit).  One processing thread per object. */
+typedef struct fmx_wideband_s *fmx_wideband;
+typedef struct {
+    int32_t struct_size;       /* sizeof(fmx_wideband_config) */
+    int32_t device;            /* HIP device ordinal */
+    int32_t streams;           /* wide input streams (>= 1) */
+    int32_t factor;            /* K: 2 .. 16 */
+    int32_t outputs;           /* stations (>= 1) */
+    const int32_t *stream_of_output;  /* [outputs] */
+    const int32_t *offset_hz;  /* [outputs] f_m, or NULL: all 0 */
+    int32_t max_block;         /* max wide samples per stream per call, a multiple of K */
+} fmx_wideband_config;
+int  fmx_wideband_create(const fmx_wideband_config *cfg, fmx_wideband *out);
+int  fmx_wideband_destroy(fmx_wideband w);
+/* Any thread.  Takes effect at the first sample of the next call: the samples of the history were mixed with the old offset and stay so, P_m is
+ * kept (never reset).  The call that applies a change waits on its stream once per changed output while the new taps are uploaded (a retune is a rare event); calls without a change
+ * stay asynchronous. */
+int  fmx_wideband_set_offset(fmx_wideband w, int32_t output, int32_t hz);
+/* Formats and conversion rules of fmx_process_device_raw; strides in complex samples.  n_wide must be a multiple of K (else FMX_E_INVALID) and at
+ * most max_block; *n_narrow = n_wide / K.  Output m at d_narrow + 2 * m * narrow_stride: what fmx_process_device takes as its d_iq with
+ * stream_stride = narrow_stride -- called on the same hip_stream behind this call it needs no copy and no synchronisation.  hip_stream NULL: the
+ * object's own stream, behind the work queued on HIP's default stream at the time of the call, and the default stream waits for the result. */
+int  fmx_wideband_process_device_raw(fmx_wideband w, const void *d_wide, int32_t format, float s16_denominator, int64_t wide_stride, int64_t n_wide,
+                                     float *d_narrow, int64_t narrow_stride, int64_t *n_narrow, void *hip_stream);
+/* The same with host buffers; synchronous. */
+int  fmx_wideband_process_host_raw(fmx_wideband w, const void *wide, int32_t format, float s16_denominator, int64_t wide_stride, int64_t n_wide,
+                                   float *narrow, int64_t narrow_stride, int64_t *n_narrow);
+/* The T = 16 K + 1 taps h for a factor (host only, needs no device); *n = T, FMX_E_TOO_LARGE when capacity < T. */
+int  fmx_wideband_taps(int32_t factor, float *dst, int32_t capacity, int32_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ SOURCES = [
     ("fmx_ola.hip", ["-ffp-contract=off"]),
     ("fmx_promote.hip", ["-ffp-contract=off"]),
     ("fmx_scan.hip", []),
+    ("fmx_wide.hip", []),
     ("fmx_api.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -418,6 +418,31 @@ void launch_scan(const ScanArgs &A, int n_jobs, hipStream_t s);
 // zeroes frames [0, frames) of the channels chans [0 .. n - 1] at pcm + ch * pcm_stride
 void launch_scan_mute(const int32_t *chans, int n, float2 *pcm, int64_t pcm_stride, int64_t frames, hipStream_t s);
 
+// ---- stage W: wide-band ingest (fmx_wide.hip; DESIGN.md "Stage W") ----------------------------------------------------------
+// One stream at K * 2 304 000 S/s feeds many outputs at 2 304 000 S/s: per-sample mix, T = 16 K + 1 real taps, / K.
+constexpr int W_RATE0 = 2304000;       // the narrow rate, and the circle of the output rotator's table
+constexpr int W_MIN_K = 2, W_MAX_K = 16;
+constexpr int W_HCOLS = 16;            // history columns: T - 1 = 16 K samples = 16 columns of K
+constexpr int W_HIST = W_HCOLS * W_MAX_K;   // history entries kept per stream (16 K used)
+constexpr int W_TILE = 256;            // outputs per workgroup (tile): K = 16 -> 34.9 KB of LDS, four workgroups per compute unit
+constexpr int W_MAX_SEG = 17;          // a window of T - 1 = 16 K samples meets at most 16 call boundaries: 17 runs of one offset
+// A run of samples mixed with one offset: sample n >= nbase (global index, up to the next newer run's nbase) was mixed with the phase
+// (pbase - (n - nbase + 1) f) mod Rw.  Calls are multiples of K samples and a change begins a call, so pbase is a multiple of K.
+struct WideSeg { int64_t nbase; int32_t pbase, f; };       // f already reduced to [0, Rw)
+struct WideOut { int32_t stream, nseg; WideSeg seg[W_MAX_SEG]; };   // seg[0]: the current run, seg[k]: older ones still inside a window
+struct WideArgs {
+    const void *src; int32_t fmt; float qs;    // fmx_iq_format, 1 / 128 or 1 / denominator
+    int64_t src_stride, n_wide, n_out, g0;     // complex samples; g0: wide samples per stream in front of this call
+    float2 *dst; int64_t dst_stride;
+    const float2 *hist_in; float2 *hist_out;   // [streams][W_HIST]: the last 16 K converted samples, oldest first (two buffers, swapped per call)
+    const float2 *taps;                        // [outputs][T] h[i] O(i f): the mix folded into the taps
+    const float *h;                            // [T]
+    const float2 *rot;                         // [W_RATE0] (cos, sin) 2 pi i / 2304000
+    const WideOut *outs;
+    const int32_t *first, *list;               // outputs of stream s: list[first[s] .. first[s + 1])
+};
+void launch_wide(const WideArgs &A, int K, int streams, hipStream_t s);
+
 void launch_front(const DeviceTables &T, const DeviceBuffers &B, const CallGeom &G, const void *iq,
                   int channels, hipStream_t s);
 // fmx_front4.hip: whole tiles of the call front4_kernel can take (0: none), and its launch over that many

@@ -40,6 +40,7 @@ EXPORTS = [
     "fmx_process_host", "fmx_process_device", "fmx_process_host_raw", "fmx_process_device_raw", "fmx_synchronize",
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
     "fmx_scan_results", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
+    "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
 ]
 
 
@@ -55,6 +56,13 @@ class FmxConfig(C.Structure):
         ("stream_of_channel", C.POINTER(C.c_int32)),
         ("inputRate", C.c_int32), ("fmRate", C.c_int32), ("workingRate", C.c_int32), ("audioRate", C.c_int32),
         ("max_block", C.c_int32),
+    ]
+
+
+class FmxWidebandConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("device", C.c_int32), ("streams", C.c_int32), ("factor", C.c_int32), ("outputs", C.c_int32),
+        ("stream_of_output", C.POINTER(C.c_int32)), ("offset_hz", C.POINTER(C.c_int32)), ("max_block", C.c_int32),
     ]
 
 
@@ -180,6 +188,18 @@ def load_library(path=None):
     L.fmx_profile_enable.argtypes = [vp, i32]
     L.fmx_profile_read.restype = C.c_int
     L.fmx_profile_read.argtypes = [vp, C.POINTER(FmxProfile), i32]
+    L.fmx_wideband_create.restype = C.c_int
+    L.fmx_wideband_create.argtypes = [C.POINTER(FmxWidebandConfig), C.POINTER(vp)]
+    L.fmx_wideband_destroy.restype = C.c_int
+    L.fmx_wideband_destroy.argtypes = [vp]
+    L.fmx_wideband_set_offset.restype = C.c_int
+    L.fmx_wideband_set_offset.argtypes = [vp, i32, i32]
+    L.fmx_wideband_process_device_raw.restype = C.c_int
+    L.fmx_wideband_process_device_raw.argtypes = [vp, vp, i32, C.c_float, i64, i64, vp, i64, C.POINTER(i64), vp]
+    L.fmx_wideband_process_host_raw.restype = C.c_int
+    L.fmx_wideband_process_host_raw.argtypes = [vp, vp, i32, C.c_float, i64, i64, f32p, i64, C.POINTER(i64)]
+    L.fmx_wideband_taps.restype = C.c_int
+    L.fmx_wideband_taps.argtypes = [i32, f32p, i32, C.POINTER(i32)]
     if path is None:
         _lib = L
     return L
@@ -375,6 +395,80 @@ class Fmx:
         self._check(self.L.fmx_profile_read(self.h, C.byref(p), 1 if reset else 0))
         return {"launches": list(p.launches), "ms": list(p.ms), "input_samples": p.input_samples,
                 "channel_samples": p.channel_samples}
+
+
+def wideband_taps(factor):
+    """The T = 16 K + 1 low-pass taps of stage W for a factor K (host only, needs no device)."""
+    L = load_library()
+    h = np.zeros(16 * 16 + 1, np.float32)
+    n = C.c_int32()
+    rc = L.fmx_wideband_taps(int(factor), h.ctypes.data_as(C.POINTER(C.c_float)), h.size, C.byref(n))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode())
+    return h[:n.value].copy()
+
+
+class Wideband:
+    """Stage W (include/fmx.h fmx_wideband): `streams` inputs at factor * 2 304 000 S/s -> one 2 304 000 S/s complex stream per station, in the
+    layout Fmx.process_device takes."""
+    NARROW_RATE = 2304000
+
+    def __init__(self, factor, stream_of_output, offset_hz, streams=1, max_block=None, device=0):
+        self.L = load_library()
+        self.factor, self.streams, self.outputs = int(factor), int(streams), len(stream_of_output)
+        self.max_block = int(max_block) if max_block is not None else 16384 * self.factor
+        assert len(offset_hz) == self.outputs
+        cfg = FmxWidebandConfig()
+        cfg.struct_size = C.sizeof(FmxWidebandConfig)
+        cfg.device, cfg.streams, cfg.factor, cfg.outputs, cfg.max_block = device, self.streams, self.factor, self.outputs, self.max_block
+        self._map = (C.c_int32 * max(self.outputs, 1))(*[int(x) for x in stream_of_output])
+        self._off = (C.c_int32 * max(self.outputs, 1))(*[int(x) for x in offset_hz])
+        cfg.stream_of_output = C.cast(self._map, C.POINTER(C.c_int32))
+        cfg.offset_hz = C.cast(self._off, C.POINTER(C.c_int32))
+        self.h = C.c_void_p()
+        self._check(self.L.fmx_wideband_create(C.byref(cfg), C.byref(self.h)))
+
+    def _check(self, rc):
+        if rc != FMX_OK:
+            raise FmxError(rc, self.L.fmx_last_error().decode("utf-8", "replace"))
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            self.L.fmx_wideband_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_offset(self, output, hz):
+        self._check(self.L.fmx_wideband_set_offset(self.h, int(output), int(hz)))
+
+    def process_host(self, wide, fmt=IQ_F32, s16_denominator=2048.0):
+        """wide: [streams, n_wide, 2] (or [n_wide, 2] for one stream) of float32 / uint8 / int8 / int16 according to fmt
+        -> complex IQ float32 [outputs, n_wide / factor, 2]."""
+        dt = {IQ_U8: np.uint8, IQ_S8: np.int8, IQ_S16: np.int16, IQ_F32: np.float32}[fmt]
+        wide = np.ascontiguousarray(wide, dt)
+        if wide.ndim == 2:
+            wide = wide[None]
+        assert wide.shape[0] == self.streams and wide.shape[2] == 2
+        n = wide.shape[1]
+        cap = max(n // self.factor, 1)
+        out = np.zeros((self.outputs, cap, 2), np.float32)
+        got = C.c_int64()
+        self._check(self.L.fmx_wideband_process_host_raw(self.h, wide.ctypes.data_as(C.c_void_p), fmt, float(s16_denominator), n, n,
+                                                         out.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(got)))
+        return out[:, :got.value]
+
+    def process_device(self, d_wide_ptr, wide_stride, n_wide, d_narrow_ptr, narrow_stride, fmt=IQ_F32, s16_denominator=2048.0, hip_stream=None):
+        """Device pointers, asynchronous on hip_stream; returns n_wide / factor.  Fmx.process_device (d_narrow_ptr, narrow_stride, ...) on the
+        same stream takes the result as it lies."""
+        got = C.c_int64()
+        self._check(self.L.fmx_wideband_process_device_raw(self.h, C.c_void_p(d_wide_ptr), fmt, float(s16_denominator), wide_stride, n_wide,
+                                                           C.c_void_p(d_narrow_ptr), narrow_stride, C.byref(got), C.c_void_p(hip_stream or 0)))
+        return got.value
 
 
 class FmProcessor:

@@ -1,0 +1,71 @@
+// wideband_adapter.h -- host-side C++ wrapper of stage W, the wide-band ingest stage (include/fmx.h fmx_wideband; DESIGN.md "Stage W").
+//
+// The stage has no counterpart in the reference: its device handlers deliver one station's 2 304 000 S/s.  A receiver of 10 - 20 MS/s
+// (Airspy R2, HackRF, LimeSDR, Pluto) hands its stream to a Wideband object, which produces one 2 304 000 S/s stream per station in the
+// layout fmx_process_device takes; the handle behind it is the one fm_processor_adapter.h wraps.  Header-only; links against libfmx.so
+// only.  Nothing throws: a failed call returns false and lastError() holds the library's text.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/fmx.h"
+
+namespace fmx_host {
+
+class Wideband {
+public:
+    // stream_of_output [m]: the wide stream station m is cut from; offset_hz [m]: its carrier relative to the stream's centre
+    Wideband(int32_t factor, int32_t streams, const std::vector<int32_t> &stream_of_output, const std::vector<int32_t> &offset_hz,
+             int32_t max_block, int device = 0)
+        : K(factor), nOutputs((int32_t)stream_of_output.size()) {
+        if (fmx_abi_version() != FMX_ABI_VERSION) { err = "libfmx has another ABI version than this adapter was built for"; return; }
+        if (offset_hz.size() != stream_of_output.size()) { err = "one offset per output"; return; }
+        fmx_wideband_config c{};
+        c.struct_size = (int32_t)sizeof(c); c.device = device; c.streams = streams; c.factor = factor; c.outputs = nOutputs;
+        c.stream_of_output = stream_of_output.data(); c.offset_hz = offset_hz.data(); c.max_block = max_block;
+        if (fmx_wideband_create(&c, &w) != FMX_OK) { err = fmx_last_error(); w = nullptr; }
+    }
+    ~Wideband() { if (w) fmx_wideband_destroy(w); }
+    Wideband(const Wideband &) = delete;
+    Wideband &operator=(const Wideband &) = delete;
+
+    bool ok() const { return w != nullptr; }
+    const std::string &lastError() const { return err; }
+    int32_t factor() const { return K; }
+    int32_t outputs() const { return nOutputs; }
+    static int32_t narrowRate() { return 2304000; }
+
+    // retune station m; any thread; takes effect at the first sample of the next call
+    bool setOffset(int32_t output, int32_t hz) { return check(fmx_wideband_set_offset(w, output, hz)); }
+
+    // n_wide (a multiple of factor ()) samples per stream, device pointers, asynchronous on hip_stream: station m's n_wide / factor ()
+    // samples land at d_narrow + 2 * m * narrow_stride -- fmx_process_device (h, d_narrow, narrow_stride, n_wide / factor (), ...) on the
+    // same stream takes them as they lie
+    bool processDevice(const void *d_wide, fmx_iq_format format, float s16_denominator, int64_t wide_stride, int64_t n_wide,
+                       float *d_narrow, int64_t narrow_stride, void *hip_stream, int64_t *n_narrow = nullptr) {
+        return check(fmx_wideband_process_device_raw(w, d_wide, (int32_t)format, s16_denominator, wide_stride, n_wide, d_narrow, narrow_stride,
+                                                     n_narrow, hip_stream));
+    }
+    // the same with host buffers, synchronous
+    bool processHost(const void *wide, fmx_iq_format format, float s16_denominator, int64_t wide_stride, int64_t n_wide, float *narrow,
+                     int64_t narrow_stride, int64_t *n_narrow = nullptr) {
+        return check(fmx_wideband_process_host_raw(w, wide, (int32_t)format, s16_denominator, wide_stride, n_wide, narrow, narrow_stride, n_narrow));
+    }
+    // the stage's low-pass: 16 factor + 1 real taps (needs no device)
+    static std::vector<float> taps(int32_t factor) {
+        std::vector<float> h(16 * 16 + 1);
+        int32_t n = 0;
+        if (fmx_wideband_taps(factor, h.data(), (int32_t)h.size(), &n) != FMX_OK) n = 0;
+        h.resize((size_t)n);
+        return h;
+    }
+
+private:
+    bool check(int rc) { if (rc != FMX_OK) err = fmx_last_error(); return rc == FMX_OK; }
+    fmx_wideband w = nullptr;
+    int32_t K, nOutputs;
+    std::string err;
+};
+
+}  // namespace fmx_host
