@@ -1,0 +1,47 @@
+// wideband_adapter_demo.cpp -- the C++ wrapper of stage W (sdr-j-fm_amd/host/wideband_adapter.h) driven as a receiver's thread would: one
+// wide stream from a raw F32 file, processHost in two calls with a setOffset between them, the narrow streams written to a file
+// ([outputs][n_wide / factor] complex f32).  Prints `taps5 <n>` (the low-pass needs no device), then `ok 1`, or `ok 0 error <text>` and
+// exit code 3 where the object could not be created (no device).
+// Used by tests/test_gpu_wideband_edges.py::test_cpp_adapter and tests/test_wideband_edges_cpu.py.
+#include <cstdio>
+#include <cstdlib>
+#include "wideband_adapter.h"
+
+int main(int argc, char **argv) {
+    if (argc < 8) {
+        std::fprintf(stderr, "usage: %s wide.f32 narrow.f32 factor n_first retuned_output retuned_hz offset_hz...\n", argv[0]);
+        return 2;
+    }
+    const int32_t K = (int32_t)std::atoi(argv[3]);
+    const int64_t n_first = std::atoll(argv[4]);
+    const int32_t retuned = (int32_t)std::atoi(argv[5]), retuned_hz = (int32_t)std::atoi(argv[6]);
+    std::vector<int32_t> offs, sof;
+    for (int a = 7; a < argc; a++) { offs.push_back((int32_t)std::atoi(argv[a])); sof.push_back(0); }
+    std::printf("taps5 %zu\n", fmx_host::Wideband::taps(5).size());
+    FILE *fi = std::fopen(argv[1], "rb");
+    if (!fi) return 2;
+    std::fseek(fi, 0, SEEK_END); const long bytes = std::ftell(fi); std::fseek(fi, 0, SEEK_SET);
+    std::vector<float> wide((size_t)bytes / sizeof(float));
+    if (std::fread(wide.data(), 1, (size_t)bytes, fi) != (size_t)bytes) return 2;
+    std::fclose(fi);
+    const int64_t n = (int64_t)(wide.size() / 2);
+    if (K < 1 || n % K != 0 || n_first < 0 || n_first > n) return 2;
+    fmx_host::Wideband w(K, 1, sof, offs, (int32_t)n);
+    if (!w.ok()) { std::printf("ok 0 error %s\n", w.lastError().c_str()); return 3; }
+    std::printf("ok 1 factor %d outputs %d\n", (int)w.factor(), (int)w.outputs());
+    const int64_t n_out = n / K;
+    std::vector<float> narrow((size_t)w.outputs() * (size_t)n_out * 2);
+    int64_t got = 0;
+    if (!w.processHost(wide.data(), FMX_IQ_F32, 2048.0f, n, n_first, narrow.data(), n_out, &got) || got != n_first / K) {
+        std::fprintf(stderr, "fmx: %s\n", w.lastError().c_str()); return 1;
+    }
+    if (!w.setOffset(retuned, retuned_hz)) { std::fprintf(stderr, "fmx: %s\n", w.lastError().c_str()); return 1; }
+    if (!w.processHost(wide.data() + 2 * n_first, FMX_IQ_F32, 2048.0f, n - n_first, n - n_first, narrow.data() + 2 * got, n_out, &got) ||
+        got != (n - n_first) / K) {
+        std::fprintf(stderr, "fmx: %s\n", w.lastError().c_str()); return 1;
+    }
+    FILE *fo = std::fopen(argv[2], "wb");
+    if (!fo || std::fwrite(narrow.data(), sizeof(float), narrow.size(), fo) != narrow.size()) return 2;
+    std::fclose(fo);
+    return 0;
+}
