@@ -1,7 +1,8 @@
 // fmx_api.hip -- the C ABI of libfmx (include/fmx.h): handle, settings mailbox, table/tap
 // design + upload, per-call geometry and the three kernel launches.  A handle's device and pinned memory
-// has one owner (DevMem): fmx_destroy names no buffer.  No CPU fallback exists: every entry point fails
-// when HIP is unavailable.
+// has one owner (DevMem): fmx_destroy names no buffer.  What a handle's settings mean for its next call is decided
+// in fmx_needs.h, how the call becomes launches in fmx_plan.h (both pure, checked on the CPU); here are the locks,
+// allocations, uploads and launches.  No CPU fallback exists: every entry point fails when HIP is unavailable.
 #include "../../include/fmx.h"
 #include "../../include/fmx_debug.h"
 #include "fmx_internal.h"
@@ -161,13 +162,12 @@ struct fmx_handle_s {
     std::vector<int32_t> rds_read;          // per channel: bits already handed out by fmx_rds_bits
     std::vector<int32_t> rds_read_dec;      // ... and by fmx_rds_decode
     std::vector<int32_t> rds_read_sym;      // ... symbols handed out by fmx_rds_symbols
-    std::atomic<int32_t> rds_gen{0};        // (rounds 2-4 counted restarts of the RDS path here; nothing restarts it any more) a consumer that saw an older generation starts over (its own read position and,
-    std::vector<int32_t> rds_gen_dec, rds_gen_sym;   // for fmx_rds_decode, the channel's block synchroniser / group decoder), however late it polls
     std::vector<fmx::RdsGroupDecoderHost> rds_dec;
     std::vector<int64_t> last_m0, last_m1;  // per channel: its 24 kS/s outputs of the last call
     // what a call needs of `params` beyond the device copy, taken under `mtx` by flush_mailbox: fmx_set_param may write `params` from another thread
     // while the processing thread enqueues the call
-    std::vector<int8_t> call_rds_mode; bool call_any_rds = false;
+    std::vector<int8_t> call_rds_mode;
+    CallNeeds needs{};                       // the summary of the settings the call's kernels and buffers are chosen from (fmx_needs.h)
     // scan mode (fmx_scan.hip): the call's scanning channels and their thresholds (flush_mailbox); per channel the block being collected (fill), the blocks
     // completed since fmx_create, the records handed out, and per record slot the fm sample behind the block and the threshold of the call that completed it
     // (the device keeps (signal_db, noise_db) per slot); allocated by the first call in which a channel scans
@@ -182,8 +182,6 @@ struct fmx_handle_s {
     std::atomic<int> scope_taps{-1};     // FMX_P_SCOPE_TAPS
     bool taps_kept = true;               // the last call kept the scope-tap rows (fmx_get_tap)
     float *w_diff_mem = nullptr;         // the LR scope tap's rows (allocated when first wanted; DeviceBuffers::w_diff is null while the tap is off)
-    bool front4_ok = false;              // every channel qualifies for front4_kernel (flush_mailbox)
-    bool front4_lo = false;              // ... and some channel has a local oscillator: the complex-tap variant (fmx_front4lo.hip)
     std::vector<std::pair<int32_t, int32_t>> hlo_key;   // per channel: the (bandwidth, oscillator) its ChanParams::hlo_* were computed for
     int last_front_kernel = 1;           // what the last call's stage A was given (FMX_P_FRONT_KERNEL numbering): fmx_last_front_kernel
     // a batch call whose channels need the demodulator pre-pass (a lone wave per 64 channels walking the call sample by sample: 6 % of the chip for
@@ -801,8 +799,6 @@ int demote(fmx_handle h, hipStream_t s) {
     return FMX_OK;
 }
 
-static bool any_rds_on(fmx_handle h) { return h->call_any_rds; }     // (as of the call's flush_mailbox)
-
 // scan mode's buffers (fmx_scan.hip), allocated by the first call in which a channel scans
 int ensure_scan(fmx_handle h) {
     if (h->scan_alloc) return FMX_OK;
@@ -821,8 +817,6 @@ int ensure_scan(fmx_handle h) {
     return FMX_OK;
 }
 
-constexpr int PLL_SEQ_AUTO_MAX = 64;   // FMX_P_PLL_SOLVER = 0: handles up to this many channels evaluate the pilot PLL sequentially
-
 // the tiled work arrays of the demodulator pre-pass (fmx_demod.hip): limited / unlimited samples in, demodulator output out.  (Allocated by the first call
 // that needs them -- before run_call decides how the call is made: a call in pieces needs them too.)
 int ensure_prepass_arrays(fmx_handle h) {
@@ -831,88 +825,55 @@ int ensure_prepass_arrays(fmx_handle h) {
     FMXCHK(h->mem.alloc(h->B.w_iq, (size_t)h->work_nj * h->pitch, true));
     return h->mem.alloc(h->B.w_osc, (size_t)h->work_nj * h->pitch, true);
 }
+// the summary of the settings as they stand (fmx_needs.h); under mtx
+CallNeeds summarize(fmx_handle h) {
+    CallNeeds nd = needs_begin(h->channels, h->twins, h->ola_mode, h->scope_taps.load());
+    for (const ChanParams &p : h->params) {
+        const FrontSet &fs = h->h_front_sets[(size_t)p.front_set];
+        needs_add(nd, ChanNeeds{p.decoder, p.squelch_mode, p.rds_mode, p.lo_freq, p.att_l, p.att_r, fs.nd, fs.dc_k});
+    }
+    return nd;
+}
 int flush_mailbox(fmx_handle h) {
     std::lock_guard<std::mutex> lk(h->mtx);
     if (h->gain_dirty) { h->gain_pending = true; h->gain_dirty = false; }   // (a change arriving behind this point belongs to the next call, flag and value)
     if (h->ola_mode) { int rc = ensure_ola(h); if (rc) return rc; rc = ola_take_settings(h); if (rc) return rc; }
     else if (!h->promo_pending) for (auto &u : h->user) { u.bw_event = false; u.lf_event = false; }     // (a folded handle applies a filter value, not the setter's call)
     if (h->sets_dirty) { int rc = ensure_sets(h); if (rc) return rc; h->params_dirty = true; }
-    bool any_lo = false;
-    for (auto &p : h->params) any_lo |= (p.lo_freq != 0);
-    if (any_lo) { int rc = ensure_lo_table(h); if (rc) return rc; }
-    {
-        // stage A on the matrix pipe (fmx_front4.hip): every tap set the long fold with its RfDC taken 12 columns back; a handle with a local oscillator somewhere
-        // runs the complex-tap variant (fmx_front4lo.hip)
-        bool ok = h->twins == 1 && !h->ola_mode;
-        for (auto &p : h->params) { if (!ok) break; ok = h->h_front_sets[(size_t)p.front_set].nd > 4; }
-        // front4_kernel applies the IQ balance in front of its filter together with the tile's scale and takes the RF DC recurrence's column sums back
-        // through 1 / balance: a balance of 0 (the slider's end, radio.cpp:989-995) or one no slider produces goes to front_kernel's per-sample pass
-        for (auto &p : h->params) {
-            if (!ok) break;
-            const float al = std::fabs(p.att_l), ar = std::fabs(p.att_r);
-            ok = h->h_front_sets[(size_t)p.front_set].dc_k == 12 && al >= 1e-6f && al <= 1e6f && ar >= 1e-6f && ar <= 1e6f;
-        }
-        h->front4_ok = ok; h->front4_lo = any_lo;
-        if (ok && any_lo) {
-            // the sum of a channel's complex taps, Hlo = sum_m G [m] e^(j 2 pi ((m lo) mod R) / R): what the filter makes of the RF DC value (fmx_front4.hip)
-            // (computed when a channel's tap set or oscillator changes, not per call: 300 sine / cosine pairs per channel)
-            const int R = h->cfg.inputRate;
-            h->hlo_key.resize(h->params.size(), std::make_pair(-1, 0x7fffffff));
-            for (size_t ci = 0; ci < h->params.size(); ci++) {
-                ChanParams &p = h->params[ci];
-                const std::pair<int32_t, int32_t> key(h->front_keys[(size_t)p.front_set / (size_t)h->twins], p.lo_freq);
-                if (h->hlo_key[ci] == key) continue;
-                h->hlo_key[ci] = key;
-                const FrontSet &fs = h->h_front_sets[(size_t)p.front_set];
-                const float *tz = &h->h_front_taps[(size_t)p.front_set * A_TAPS_STRIDE];
-                double hr = 0, hi = 0;
-                for (int d = 0; d < A_MAX_ND; d++)
-                    for (int r = 0; r < DECIM; r++) {
-                        const int m = 12 * d + fs.off - r;
-                        if (m < 0) continue;
-                        const int64_t ph = (((int64_t)m * p.lo_freq) % R + R) % R;
-                        const double g = (double)tz[(d + 1) * DECIM + r], a = 2.0 * design::kPi * (double)ph / (double)R;
-                        hr += g * std::cos(a); hi += g * std::sin(a);
-                    }
-                const float fr = (float)hr, fi = (float)hi;
-                if (fr != p.hlo_re || fi != p.hlo_im) { p.hlo_re = fr; p.hlo_im = fi; h->params_dirty = true; }
-            }
+    const CallNeeds nd = h->needs = summarize(h);
+    if (nd.any_lo) { int rc = ensure_lo_table(h); if (rc) return rc; }
+    if (nd.front4_ok && nd.any_lo) {
+        // the complex-tap variant of stage A on the matrix pipe (fmx_front4lo.hip): the sum of every channel's complex taps (tap_sum_lo)
+        // (computed when a channel's tap set or oscillator changes, not per call: 300 sine / cosine pairs per channel)
+        h->hlo_key.resize(h->params.size(), std::make_pair(-1, 0x7fffffff));
+        for (size_t ci = 0; ci < h->params.size(); ci++) {
+            ChanParams &p = h->params[ci];
+            const std::pair<int32_t, int32_t> key(h->front_keys[(size_t)p.front_set / (size_t)h->twins], p.lo_freq);
+            if (h->hlo_key[ci] == key) continue;
+            h->hlo_key[ci] = key;
+            const TapSum H = tap_sum_lo(&h->h_front_taps[(size_t)p.front_set * A_TAPS_STRIDE], A_MAX_ND, h->h_front_sets[(size_t)p.front_set].off, p.lo_freq, h->cfg.inputRate);
+            if (H.re != p.hlo_re || H.im != p.hlo_im) { p.hlo_re = H.re; p.hlo_im = H.im; h->params_dirty = true; }
         }
     }
-    bool any_rds = false;
     h->call_rds_mode.resize((size_t)h->channels);
-    for (int c = 0; c < h->channels; c++) { h->call_rds_mode[(size_t)c] = (int8_t)h->params[(size_t)c].rds_mode; any_rds |= (h->params[(size_t)c].rds_mode != 0); }
-    h->call_any_rds = any_rds;
+    for (int c = 0; c < h->channels; c++) h->call_rds_mode[(size_t)c] = (int8_t)h->params[(size_t)c].rds_mode;
     h->call_scan.clear(); h->call_scan_thr.clear();
     for (int c = 0; c < h->channels; c++)
         if (h->user[(size_t)c].scanning) { h->call_scan.push_back(c); h->call_scan_thr.push_back(h->user[(size_t)c].scan_thr); }
     if (!h->call_scan.empty()) { const int rc = ensure_scan(h); if (rc) return rc; }
     // (a channel's RDS path runs while its decoder is on and stands still otherwise -- block filters, phase delay line, decimator and slicer
     // keep what they hold, as the reference's processor's do: nothing restarts when a decoder is switched; run_piece counts per channel)
-    if (any_rds) { const int rc = ensure_rds(h); if (rc) return rc; }
-    bool any_pll = false;
-    for (auto &p : h->params) any_pll |= (p.decoder == 2 || p.decoder == 1 || p.squelch_mode != 0);     // pllC on the fm-rate IQ; |z| for the level squelch; the general AFC body for the noise squelch
-    {   // the scope taps that are rows of stage B's work arrays (FMX_P_SCOPE_TAPS): display feeds, kept where there is a display; the RDS path reads two of them
-        const int want = h->scope_taps.load();
-        const bool keep = want < 0 ? h->channels <= 64 : want != 0;
-        if (keep && !h->w_diff_mem) {
-            HIPCHK(hipDeviceSynchronize());
-            FMXCHK(h->mem.alloc(h->w_diff_mem, (size_t)h->work_nj * h->pitch, true));
-        }
-        h->B.w_diff = keep ? h->w_diff_mem : nullptr;
-        h->taps_kept = keep;
-        h->B.rows_on = (keep || any_rds) ? 1 : 0;
-        h->B.peaks_on = keep ? 1 : 0;
+    if (nd.any_rds) { const int rc = ensure_rds(h); if (rc) return rc; }
+    if (nd.keep_taps && !h->w_diff_mem) {
+        HIPCHK(hipDeviceSynchronize());
+        FMXCHK(h->mem.alloc(h->w_diff_mem, (size_t)h->work_nj * h->pitch, true));
     }
-    {
-        int var = 0;
-        for (auto &p : h->params)          // (of the channels the pre-pass touches: fmx_demod.hip, afc_kernel's variants)
-            var |= (p.decoder == 2 ? 1 : 0) | (p.decoder == 1 ? 2 : 0) | (p.squelch_mode == 2 ? 4 : 0) | ((p.decoder > 2 && p.squelch_mode != 0) ? 8 : 0);
-        h->B.prepass_var = var;
-    }
-    bool any_nsq = false;
-    for (auto &p : h->params) any_nsq |= (p.squelch_mode == 1);
-    if (any_nsq && !h->T.nsq_coef) {
+    h->B.w_diff = nd.keep_taps ? h->w_diff_mem : nullptr;
+    h->taps_kept = nd.keep_taps;
+    h->B.rows_on = nd.rows_on ? 1 : 0;
+    h->B.peaks_on = nd.peaks_on ? 1 : 0;
+    h->B.prepass_var = nd.prepass_var;
+    if (nd.any_nsq && !h->T.nsq_coef) {
         // squelch ctor squelchClass.cpp:11-18 with mySquelch (1, 70000, fmRate / 20, fmRate) fm-processor.cpp:87
         const design::Iir hp = design::iir_chebyshev_lowhigh(true, 20, 70000 - 100, h->cfg.fmRate);
         const design::Iir lp = design::iir_chebyshev_lowhigh(false, 20, 70000, h->cfg.fmRate);
@@ -929,13 +890,13 @@ int flush_mailbox(fmx_handle h) {
         HIPCHK(hipDeviceSynchronize());
         FMXCHK(h->mem.upload(h->T.nsq_coef, h->h_nsq));
     }
-    if (any_pll) { const int rc = ensure_prepass_arrays(h); if (rc) return rc; }
+    if (nd.prepass) { const int rc = ensure_prepass_arrays(h); if (rc) return rc; }
     for (int c = 0; c < h->channels; c++) {            // set_squelchValue takes effect at a block start, when it differs (fm-processor.cpp:410-413)
         ChanUser &u = h->user[c];
         if (u.squelch_value != u.squelch_old) {
             u.squelch_level = u.squelch_value; u.squelch_old = u.squelch_value;
-            h->params[c].squelch_thr = std::pow(10.0f, (float)(u.squelch_level - 80) / 30.0f);       // squelchClass.cpp:33-37
-            h->params[c].squelch_nthr = 1.0f - (float)u.squelch_level / 100.0f;
+            const SquelchThr t = squelch_thresholds(u.squelch_level);
+            h->params[c].squelch_thr = t.level; h->params[c].squelch_nthr = t.noise;
             h->params_dirty = true;
         }
     }
@@ -994,9 +955,7 @@ int bytes_per_sample(int32_t fmt) { return fmt == FMX_IQ_F32 ? 8 : (fmt == FMX_I
 
 // the arguments of an fmx_process_* call, checked once at its head (run_call; fmx_process_host_raw for the caller's PCM buffer)
 int check_call(fmx_handle h, int32_t fmt, float s16_den, int64_t n, int64_t pcm_stride) {
-    if (fmt < 0 || fmt > 3) return fail(FMX_E_INVALID, "unknown IQ format");
-    int ex = 0;
-    if (fmt == 3 && (!(s16_den >= 1.0f) || std::frexp(s16_den, &ex) != 0.5f)) return fail(FMX_E_INVALID, "s16_denominator must be a power of two >= 1");
+    if (const ParamCheck pc = check_iq_format(fmt, s16_den); pc.code) return fail(pc.code, pc.msg);
     if (n <= 0 || n > h->cfg.max_block) return fail(FMX_E_TOO_LARGE, "n_complex must be in [1, max_block]");
     if (call_frames(h, n) > pcm_stride) return fail(FMX_E_TOO_LARGE, "pcm_stride smaller than the frames this call produces");
     return FMX_OK;
@@ -1056,14 +1015,8 @@ int stage_a(fmx_handle h, CallGeom &G, const void *d_iq, hipStream_t s, hipStrea
         FMXCHK(h->mem.alloc(h->B.hist_snap, C * DECIM * A_HIST_COLS));
         FMXCHK(h->mem.alloc(h->B.dcv_snap, C * DCV_SAVE));
     }
-    G.parts = fp.parts; G.part_tiles = fp.part_tiles;
-    // automatic: the filter on the matrix pipe wherever a handle qualifies and has the channels to fill the chip without splitting them in time
-    // (measured at 4096 channels on one box: 1.52 ms per launch against 1.75 for the four-wave kernel and 1.84 for the six-wave VALU kernel, which
-    // both sit at the packed-FMA power limit)
-    // (the complex-tap variant runs one channel per workgroup: a handle of one channel per compute unit fills the chip)
-    const int fk = h->front_kernel.load();
-    if (h->front4_ok && !h->front4_lo && (fk == 3 || (fk == 0 && G.parts <= 1))) { G.parts = 1; G.front4 = 1; }
-    if (h->front4_ok && h->front4_lo && (fk == 3 || (fk == 0 && h->channels >= h->n_cus))) { G.parts = 1; G.front4 = 2; }
+    const FrontChoice fc = choose_front(h->needs.front4_ok, h->needs.any_lo, h->front_kernel.load(), fp.parts, h->channels, h->n_cus);
+    G.parts = fc.parts; G.part_tiles = fp.part_tiles; G.front4 = fc.front4;
     // (what is reported is what runs: a call without a whole tile on the kernel's grid goes to front_kernel in launch_front)
     h->last_front_kernel = (G.front4 && front4_tiles(G, d_iq) > 0) ? 3 : 1;
     if (h->ola_mode) {
@@ -1139,15 +1092,15 @@ int stage_scan(fmx_handle h, const CallGeom &G, hipStream_t sa) {
         std::lock_guard<std::mutex> lk(h->mtx);      // (fmx_scan_results reads the counters from any thread)
         for (size_t i = 0; i < n; i++) {
             const int c = h->call_scan[i];
-            const int64_t fill = h->scan_fill[(size_t)c], blocks = h->scan_blocks[(size_t)c], nblk = (fill + nj) / scan::N;
-            h->scan_jobs[i] = ScanJob{c, (int32_t)fill, (int32_t)(blocks & (scan::RING - 1)), 0};
-            for (int64_t b = std::max<int64_t>(0, nblk - scan::RING); b < nblk; b++) {
-                const size_t slot = (size_t)c * scan::RING + (size_t)((blocks + b) & (scan::RING - 1));
-                h->scan_end[slot] = G.J0 + (b + 1) * scan::N - fill;          // (a complete block ends in this call: the carry holds < 1024)
+            const ScanProduce sp = scan_produce(h->scan_fill[(size_t)c], h->scan_blocks[(size_t)c], nj, G.J0, scan::N, scan::RING);
+            h->scan_jobs[i] = ScanJob{c, sp.job_fill, sp.job_slot0, 0};
+            for (int64_t b = sp.b0; b < sp.nblk; b++) {
+                const size_t slot = (size_t)c * scan::RING + (size_t)sp.slot(b);
+                h->scan_end[slot] = sp.end_sample(b);
                 h->scan_rec_thr[slot] = h->call_scan_thr[i];
             }
-            h->scan_blocks[(size_t)c] = blocks + nblk;
-            h->scan_fill[(size_t)c] = (int32_t)((fill + nj) % scan::N);
+            h->scan_blocks[(size_t)c] = sp.new_blocks;
+            h->scan_fill[(size_t)c] = sp.new_fill;
         }
     }
     // (pageable source: the copy is staged before the call returns)
@@ -1219,7 +1172,8 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     G.input_rate = h->cfg.inputRate; G.pitch = h->pitch; G.streams_private = (h->streams_private && h->twins == 1) ? 1 : 0; G.twins = h->twins; G.channels = h->channels; G.stream_stride = a.stream_stride; G.pcm_stride = a.pcm_stride;
     G.iq_format = a.fmt; G.iq_scale = (a.fmt == 3) ? 1.0f / a.s16_den : 1.0f / 128.0f; G.n_cus = h->n_cus; G.streams = h->streams;
     const int64_t frames = conv2_out(h, G.M1) - conv2_out(h, G.M0);
-    if (h->rds_alloc && any_rds_on(h) && G.J1 - G.J0 > RDS_BLK)
+    const bool rds_running = h->rds_alloc && h->needs.any_rds;       // (as of this piece's flush_mailbox)
+    if (rds_running && G.J1 - G.J0 > RDS_BLK)
         return fail(FMX_E_TOO_LARGE, "with RDS on, a call may cover at most 32000 fm samples (384000 input samples)");
     const bool piped = overlapped && !h->ola_mode && !env_switches().pieces_serial;
     hipStream_t sa = piped ? h->pipe_sA : s;
@@ -1239,13 +1193,13 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     G.stageb_form = h->stageb_form.load(); G.no_deemph = h->ola_mode ? 1 : 0;
     // a plain batch (no pre-pass, no RDS, no scope-tap rows: stage B as the whole kernel) runs stages B and C as two channel groups on two streams where it has
     // more channels than one round of stage-B workgroups (second_group_channels); FMX_TAIL_SPLIT=0: one group
-    const bool plain = !piped && !h->ola_mode && !h->B.w_iq && !h->cv_nt && !h->B.rows_on && !(h->rds_alloc && any_rds_on(h)) && !h->gain_pending && G.stageb_form == 0 &&
-                       G.J1 > G.J0 && G.M1 > G.M0;
+    const bool plain = plain_batch(PieceFlags{piped, h->ola_mode, h->B.w_iq != nullptr, h->cv_nt != 0, h->needs.rows_on, rds_running, h->gain_pending, G.stageb_form,
+                                              G.J1 > G.J0, G.M1 > G.M0});
     const int second = env_switches().tail_split && plain ? second_group_channels(h->channels, h->n_cus) : 0;
     if (second > 0 && (rc = ensure_pipe_streams(h))) return rc;
     h->last_second_group = second;
     if ((rc = stage_b(h, G, k, piped, second, s, sa))) return rc;
-    if (h->rds_alloc && any_rds_on(h) && (rc = stage_rds(h, G, s))) return rc;
+    if (rds_running && (rc = stage_rds(h, G, s))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[2], s));
     if ((rc = stage_c(h, G, d_pcm, frames, second, s))) return rc;
     if (!h->call_scan.empty() && frames > 0 && (rc = stage_scan_mute(h, d_pcm, G.pcm_stride, frames, s))) return rc;
@@ -1268,7 +1222,8 @@ int run_call(fmx_handle h, const void *d_iq, int32_t fmt, float s16_den, int64_t
     CallShape cs{};
     {   // (the settings as they stand now; the pieces' own decisions read what their flush_mailbox takes)
         std::lock_guard<std::mutex> lk(h->mtx);
-        for (auto &p : h->params) { cs.any_rds |= p.rds_mode != 0; cs.prepass |= p.decoder == 2 || p.decoder == 1 || p.squelch_mode != 0; cs.pllc |= p.decoder == 2 || p.decoder == 1; cs.am |= p.decoder == 1; }
+        const CallNeeds nd = summarize(h);
+        cs.any_rds = nd.any_rds; cs.prepass = nd.prepass; cs.pllc = nd.pllc; cs.am = nd.am;
     }
     // (the pre-pass's work arrays are allocated before the call is cut: the first call of such a batch runs in pieces too)
     if (!cs.any_rds && cs.prepass && !h->ola_mode && (rc = ensure_prepass_arrays(h))) return rc;
@@ -1403,7 +1358,7 @@ int init_channels(fmx_handle h, const fmx_config *cfg, int decim, const Conv2Des
         h->cv_p = cv.p; h->cv_q = cv.q; h->cv_nt = cv.nt;
         h->x48_stride = cv.nt + cfg->max_block / (4 * h->decim) + 96;
     }
-    h->ola_mode = h->channels <= OLA_MAX_CH;          // FMX_P_FILTER_RESTARTS = 0 (automatic)
+    h->ola_mode = filter_form(0, h->channels).ola_mode;          // FMX_P_FILTER_RESTARTS = 0 (automatic)
     h->user.assign(h->channels, ChanUser());
     h->params.assign(h->channels, ChanParams());
     for (int c = 0; c < h->channels; c++) {
@@ -1415,8 +1370,9 @@ int init_channels(fmx_handle h, const fmx_config *cfg, int decim, const Conv2Des
         // constructor defaults fm-processor.cpp:110-160 / fm-demodulator.cpp:66
         p.fm_mode = 0; p.sound_sel = 0; p.decoder = 3; p.auto_mono = 1; p.pss_active = 1; p.dc_remove = 1;
         p.rds_mode = 0; p.lo_freq = 0; p.lo_period = 0; p.att_l = 1.f; p.att_r = 1.f;
-        p.pll_seq = h->channels <= PLL_SEQ_AUTO_MAX ? 1 : 0;
-        p.squelch_mode = 0; p.squelch_thr = std::pow(10.0f, (float)(1 - 80) / 30.0f); p.squelch_nthr = 1.0f - 1 / 100.0f;
+        p.pll_seq = pll_seq(0, h->channels);
+        const SquelchThr t = squelch_thresholds(1);              // mySquelch (1, ...) fm-processor.cpp:87
+        p.squelch_mode = 0; p.squelch_thr = t.level; p.squelch_nthr = t.noise;
         refresh_derived(h, c);
     }
     std::vector<int> users((size_t)h->streams, 0);
@@ -1634,51 +1590,22 @@ int fmx_set_param(fmx_handle h, int32_t channel, int32_t id, double value) {
     if (!h) return fail(FMX_E_INVALID, "null handle");
     if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
     const int iv = (int)std::llround(value);
-    // validate once
-    switch (id) {
-    case FMX_P_FM_MODE: if (iv < 0 || iv > 2) return fail(FMX_E_INVALID, "fm mode must be 0..2"); break;
-    case FMX_P_FM_DECODER:
-        if (iv < 1 || iv > 6) return fail(FMX_E_INVALID, "decoder must be 1..6"); break;
-    case FMX_P_SOUND_MODE: if (iv < 0 || iv > 6) return fail(FMX_E_INVALID, "sound mode must be 0..6"); break;
-    case FMX_P_STEREO_PANORAMA: if (iv < 0 || iv > 200) return fail(FMX_E_INVALID, "panorama must be 0..200"); break;
-    case FMX_P_SOUND_BALANCE: if (iv < -100 || iv > 100) return fail(FMX_E_INVALID, "balance must be -100..100"); break;
-    case FMX_P_DEEMPHASIS: if (iv < 1) return fail(FMX_E_INVALID, "de-emphasis must be >= 1 us (Q_ASSERT fm-processor.cpp:293)"); break;
-    case FMX_P_BANDWIDTH: if (iv < 0 || iv > h->cfg.inputRate) return fail(FMX_E_INVALID, "bandwidth out of range"); break;
-    case FMX_P_RDS_MODE: if (iv < 0 || iv > 3) return fail(FMX_E_INVALID, "rds mode must be 0..3"); break;
-    case FMX_P_LOCAL_OSCILLATOR:
-        if (std::abs(iv) > h->cfg.inputRate) return fail(FMX_E_INVALID, "|lo| must be <= inputRate (oscillator.cpp:49-58)"); break;
-    case FMX_P_SQUELCH_MODE:
-        if (iv < 0 || iv > 2) return fail(FMX_E_INVALID, "squelch mode must be 0 (off), 1 (noise squelch) or 2 (level squelch)"); break;
-    case FMX_P_SQUELCH_VALUE: if (iv < 0 || iv > 100) return fail(FMX_E_INVALID, "squelch value must be 0..100"); break;
-    case FMX_P_PLL_SOLVER: if (iv < 0 || iv > 3) return fail(FMX_E_INVALID, "PLL solver must be 0 (automatic), 1 (sequential), 2 (Newton, sequential around lock decisions) or 3 (Newton always)"); break;
-    case FMX_P_FRONT_KERNEL:
-        if (iv < 0 || iv > 3 || iv == 2) return fail(FMX_E_INVALID, "front kernel must be 0 (automatic), 1 (four waves per channel, packed f32 FMAs) or 3 (the filter on the matrix pipe); 2 was round 5's six-wave kernel, now tools/experiments/fmx_front3.hip");
-        h->front_kernel.store(iv); return FMX_OK;
-    case FMX_P_SCOPE_TAPS:
-        if (iv < -1 || iv > 1) return fail(FMX_E_INVALID, "scope taps must be -1 (automatic), 0 (not kept) or 1 (kept)");
-        h->scope_taps.store(iv); return FMX_OK;
-    case FMX_P_CALL_PIECES:
-        if (iv < -1 || iv > (1 << 20)) return fail(FMX_E_INVALID, "call pieces must be -1 (automatic), 0 (never) or the fm samples per piece");
-        h->pipe_rows.store(iv); return FMX_OK;
-    case FMX_P_FRONT_PARTS:
-        if (iv < 0 || iv > 32) return fail(FMX_E_INVALID, "front parts must be 0 (automatic), 1 (one workgroup per channel) or 2..32");
-        h->front_parts.store(iv); return FMX_OK;
-    case FMX_P_STAGEB_FORM:
-        if (iv < 0 || iv > 2) return fail(FMX_E_INVALID, "stage B form must be 0 (automatic), 1 (one kernel) or 2 (two kernels)");
-        h->stageb_form.store(iv); return FMX_OK;
+    if (const ParamCheck pc = check_param(id, value, h->cfg.inputRate); pc.code) return fail(pc.code, pc.msg);
+    switch (id) {      // the handle-wide settings and scan mode's: nothing of ChanParams changes
+    case FMX_P_FRONT_KERNEL: h->front_kernel.store(iv); return FMX_OK;
+    case FMX_P_SCOPE_TAPS: h->scope_taps.store(iv); return FMX_OK;
+    case FMX_P_CALL_PIECES: h->pipe_rows.store(iv); return FMX_OK;
+    case FMX_P_FRONT_PARTS: h->front_parts.store(iv); return FMX_OK;
+    case FMX_P_STAGEB_FORM: h->stageb_form.store(iv); return FMX_OK;
     case FMX_P_FILTER_RESTARTS: {
-        if (iv < 0 || iv > 2) return fail(FMX_E_INVALID, "filter restarts must be 0 (automatic), 1 (the reference's block filters) or 2 (folded FIRs)");
         std::lock_guard<std::mutex> lk(h->mtx);
         if (h->g_total != 0) return fail(FMX_E_UNSUPPORTED, "the filter structure of a handle is fixed by its first call");
-        const bool want = iv == 1 || (iv == 0 && h->channels <= OLA_MAX_CH);
-        if (want != h->ola_mode) { h->ola_mode = want; h->sets_dirty = true; }
-        h->folded_pinned = iv == 2;
+        const FilterForm ff = filter_form(iv, h->channels);
+        if (ff.ola_mode != h->ola_mode) { h->ola_mode = ff.ola_mode; h->sets_dirty = true; }
+        h->folded_pinned = ff.folded_pinned;
         return FMX_OK; }
     case FMX_P_SCANNING:
     case FMX_P_SCAN_THRESHOLD: {
-        if (id == FMX_P_SCANNING && !(value == 0.0 || value == 1.0)) return fail(FMX_E_INVALID, "scanning must be 0 or 1");
-        if (id == FMX_P_SCAN_THRESHOLD && !(value >= -32768.0 && value <= 32767.0 && value == std::floor(value)))
-            return fail(FMX_E_INVALID, "scan threshold must be an integral number of dB in -32768..32767 (the reference's int16_t thresHold)");
         std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes both at the next call; nothing on the device changes)
         const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
         for (int c = c0; c < c1; c++) {
@@ -1686,12 +1613,7 @@ int fmx_set_param(fmx_handle h, int32_t channel, int32_t id, double value) {
             else h->user[(size_t)c].scan_thr = (int16_t)value;
         }
         return FMX_OK; }
-    case FMX_P_DISP_DELAY: if (iv < 0 || iv > 100000) return fail(FMX_E_INVALID, "display delay must be 0..100000 steps"); break;
-    case FMX_P_TEST_TONE:
-    case FMX_P_VOLUME_DB: case FMX_P_LF_CUTOFF: case FMX_P_ATTENUATION_L: case FMX_P_ATTENUATION_R:
-    case FMX_P_AUTO_MONO: case FMX_P_PSS: case FMX_P_DC_REMOVE:
-    case FMX_A_TRIGGER_FREQUENCY_CHANGE: case FMX_A_RESTART_PSS: case FMX_A_RESET_RDS: break;
-    default: return fail(FMX_E_INVALID, "unknown parameter id");
+    default: break;
     }
     std::lock_guard<std::mutex> lk(h->mtx);
     const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
@@ -1711,29 +1633,20 @@ int fmx_set_param(fmx_handle h, int32_t channel, int32_t id, double value) {
         case FMX_P_VOLUME_DB: u.volume_db = (float)value; u.ctor_volume = false; h->gain_dirty = true; break;
         case FMX_P_LF_CUTOFF: case FMX_P_BANDWIDTH: {
             if (id == FMX_P_LF_CUTOFF) { u.lf_cutoff = iv > 0 ? iv : 0; u.lf_event = iv > 0; } else { u.bandwidth = iv; u.bw_event = iv > 0; }
-            // a folded handle in mid-stream: the setter stays pending until the handle has kept enough of its streams to become a block-machine handle
-            // (promote); everywhere else -- before the first call, a block-machine handle, folded filters pinned -- it applies with the next call
-            const bool defer = !h->ola_mode && !h->folded_pinned && h->g_total > 0 && h->twins >= 1 && h->cfg.max_block >= 4096;
-            if (defer) { if (!h->promo_pending) { h->promo_pending = true; h->promo_have = 0; } }
+            // (deferred: pending until the handle has kept enough of its streams to become a block-machine handle, promote)
+            if (defer_filter_change(h->ola_mode, h->folded_pinned, h->g_total, h->twins, h->cfg.max_block)) { if (!h->promo_pending) { h->promo_pending = true; h->promo_have = 0; } }
             else { u.bw_applied = u.bandwidth; u.lf_applied = u.lf_cutoff; h->sets_dirty = true; }
             break; }
         case FMX_P_ATTENUATION_L: p.att_l = (float)value; h->promo_recapture = true; break;
         case FMX_P_ATTENUATION_R: p.att_r = (float)value; h->promo_recapture = true; break;
         case FMX_P_RDS_MODE: p.rds_mode = iv; break;
-        case FMX_P_LOCAL_OSCILLATOR: {
-            p.lo_freq = iv; h->promo_recapture = true;
-            int64_t a = iv < 0 ? -(int64_t)iv : iv, b = h->cfg.inputRate;
-            while (b) { const int64_t r = a % b; a = b; b = r; }                  // gcd(|lo|, inputRate)
-            const int64_t per = a ? h->cfg.inputRate / a : 0;
-            p.lo_period = (iv != 0 && per <= LO_LDS_MAX) ? (int32_t)per : 0;
-            break;
-        }
+        case FMX_P_LOCAL_OSCILLATOR: p.lo_freq = iv; p.lo_period = lo_period(iv, h->cfg.inputRate); h->promo_recapture = true; break;
         case FMX_P_AUTO_MONO: p.auto_mono = iv != 0; break;
         case FMX_P_PSS: p.pss_active = iv != 0; break;
         case FMX_P_SQUELCH_MODE: p.squelch_mode = iv; break;
         case FMX_P_SQUELCH_VALUE: u.squelch_value = iv; break;
         case FMX_P_TEST_TONE: p.test_tone = iv != 0; break;
-        case FMX_P_PLL_SOLVER: p.pll_seq = (iv == 1 || (iv == 0 && h->channels <= PLL_SEQ_AUTO_MAX)) ? 1 : (iv == 3 ? 2 : 0); break;
+        case FMX_P_PLL_SOLVER: p.pll_seq = pll_seq(iv, h->channels); break;
         case FMX_P_DISP_DELAY:                       // DelayLine::set_delay_steps fm-processor.h:60-63: resize keeps what is there
             u.delay.resize((size_t)iv + 1, make_float2(-40.0f, -40.0f)); u.delay_idx = 0; break;
         case FMX_P_DC_REMOVE: p.dc_remove = iv != 0; p.actions |= ACT_DC_RESET; h->promo_recapture = true; break;
@@ -1865,14 +1778,13 @@ int fmx_get_peaks(fmx_handle h, int32_t channel, float *lr_db, int32_t capacity,
     HIPCHK(hipMemcpy(&st, h->B.state + channel, sizeof(st), hipMemcpyDeviceToHost));
     std::lock_guard<std::mutex> lk(h->mtx);
     ChanUser &u = h->user[channel];
-    if (st.pk_events - u.pk_read > PK_RING) u.pk_read = st.pk_events - PK_RING;      // the caller fell behind: the oldest windows are gone
-    const int avail = st.pk_events - u.pk_read;
-    const int take = std::min(avail, (int)capacity);
+    const RingTake t = ring_take(st.pk_events, u.pk_read, PK_RING, capacity);      // (a caller that fell behind: the oldest windows are gone)
+    const int take = (int)t.count;
     if (take > 0) {
         std::vector<float2> ring((size_t)PK_RING);
         HIPCHK(hipMemcpy(ring.data(), h->B.pk_ring + (size_t)channel * PK_RING, sizeof(float2) * PK_RING, hipMemcpyDeviceToHost));
         for (int k = 0; k < take; k++) {
-            const float2 pk = ring[(size_t)((u.pk_read + k) & (PK_RING - 1))];
+            const float2 pk = ring[(size_t)ring_slot(t.from + k, PK_RING)];
             // fm-processor.cpp:785-794: float log10 (std::log10 of a float), -40 dB for silence, then the display delay line
             const float ldb = pk.x > 0.0f ? 20.0f * std::log10(pk.x) : -40.0f;
             const float rdb = pk.y > 0.0f ? 20.0f * std::log10(pk.y) : -40.0f;
@@ -1880,8 +1792,8 @@ int fmx_get_peaks(fmx_handle h, int32_t channel, float *lr_db, int32_t capacity,
             u.delay_idx = (u.delay_idx + 1) % (uint32_t)u.delay.size();
             lr_db[2 * k] = u.delay[u.delay_idx].x; lr_db[2 * k + 1] = u.delay[u.delay_idx].y;
         }
-        u.pk_read += take;
     }
+    u.pk_read = (int32_t)t.next();
     *n_events = take;
     return FMX_OK;
 }
@@ -1948,16 +1860,14 @@ int fmx_rds_bits(fmx_handle h, int32_t channel, uint8_t *bits, int32_t capacity,
     HIPCHK(hipDeviceSynchronize());
     RdsState st;
     HIPCHK(hipMemcpy(&st, h->R.state + channel, sizeof(st), hipMemcpyDeviceToHost));
-    int32_t have = st.nbits - h->rds_read[channel];
-    if (have > RDS_BITS_CAP) { h->rds_read[channel] = st.nbits - RDS_BITS_CAP; have = RDS_BITS_CAP; }   // ring overrun: oldest bits lost
-    const int32_t take = have < capacity ? have : capacity;
-    std::vector<uint8_t> ring((size_t)RDS_BITS_CAP);
-    if (take > 0 && bits) {
+    const RingTake t = ring_take(st.nbits, h->rds_read[channel], RDS_BITS_CAP, bits ? capacity : 0);   // (ring overrun: oldest bits lost)
+    if (t.count > 0) {
+        std::vector<uint8_t> ring((size_t)RDS_BITS_CAP);
         HIPCHK(hipMemcpy(ring.data(), h->R.bits + (size_t)channel * RDS_BITS_CAP, RDS_BITS_CAP, hipMemcpyDeviceToHost));
-        for (int32_t i = 0; i < take; i++) bits[i] = ring[(size_t)((h->rds_read[channel] + i) & (RDS_BITS_CAP - 1))];
-        h->rds_read[channel] += take;
+        for (int64_t i = 0; i < t.count; i++) bits[i] = ring[(size_t)ring_slot(t.from + i, RDS_BITS_CAP)];
     }
-    *n_bits = (take > 0 && bits) ? take : 0;
+    h->rds_read[channel] = (int32_t)t.next();
+    *n_bits = (int32_t)t.count;
     return FMX_OK;
 }
 
@@ -1971,20 +1881,15 @@ int fmx_rds_symbols(fmx_handle h, int32_t channel, float *iq, int32_t capacity, 
     RdsState st;
     HIPCHK(hipMemcpy(&st, h->R.state + channel, sizeof(st), hipMemcpyDeviceToHost));
     int32_t &rd = h->rds_read_sym[(size_t)channel];
-    if (h->rds_gen_sym.size() != (size_t)h->channels) h->rds_gen_sym.assign((size_t)h->channels, 0);
-    const int32_t gen = h->rds_gen.load();
-    if (h->rds_gen_sym[(size_t)channel] != gen) { h->rds_gen_sym[(size_t)channel] = gen; rd = 0; }   // (the generation moves with resetRds only)
-    int32_t have = st.nbits - rd;
-    if (have < 0) { rd = 0; have = st.nbits; }
-    if (have > RDS_SYM_CAP) { rd = st.nbits - RDS_SYM_CAP; have = RDS_SYM_CAP; }        // ring overrun: oldest symbols lost
-    const int32_t take = have < capacity ? have : capacity;
-    if (take > 0 && iq) {
+    if (st.nbits < rd) rd = 0;                  // (the count went backwards: start over)
+    const RingTake t = ring_take(st.nbits, rd, RDS_SYM_CAP, iq ? capacity : 0);        // (ring overrun: oldest symbols lost)
+    if (t.count > 0) {
         std::vector<float2> ring((size_t)RDS_SYM_CAP);
         HIPCHK(hipMemcpy(ring.data(), h->R.sym + (size_t)channel * RDS_SYM_CAP, sizeof(float2) * RDS_SYM_CAP, hipMemcpyDeviceToHost));
-        for (int32_t i = 0; i < take; i++) { const float2 v = ring[(size_t)((rd + i) & (RDS_SYM_CAP - 1))]; iq[2 * i] = v.x; iq[2 * i + 1] = v.y; }
-        rd += take;
-        *n_symbols = take;
+        for (int64_t i = 0; i < t.count; i++) { const float2 v = ring[(size_t)ring_slot(t.from + i, RDS_SYM_CAP)]; iq[2 * i] = v.x; iq[2 * i + 1] = v.y; }
+        *n_symbols = (int32_t)t.count;
     }
+    rd = (int32_t)t.next();
     return FMX_OK;
 }
 
@@ -1997,23 +1902,22 @@ int fmx_scan_results(fmx_handle h, int32_t channel, fmx_scan_result *out, int32_
     HIPCHK(hipDeviceSynchronize());
     std::lock_guard<std::mutex> lk(h->mtx);
     const size_t c = (size_t)channel;
-    const int64_t done = h->scan_blocks[c];
-    if (done - h->scan_read[c] > scan::RING) h->scan_read[c] = done - scan::RING;      // the caller fell behind: the oldest records are gone
-    const int take = (int)std::min<int64_t>(done - h->scan_read[c], capacity);
+    const RingTake t = ring_take(h->scan_blocks[c], h->scan_read[c], scan::RING, capacity);      // (a caller that fell behind: the oldest records are gone)
+    const int take = (int)t.count;
     if (take > 0) {
         std::vector<float2> ring((size_t)scan::RING);
         HIPCHK(hipMemcpy(ring.data(), h->d_scan_rec + c * scan::RING, sizeof(float2) * scan::RING, hipMemcpyDeviceToHost));
         for (int k = 0; k < take; k++) {
-            const int64_t b = h->scan_read[c] + k;
-            const size_t slot = (size_t)(b & (scan::RING - 1));
+            const int64_t b = t.from + k;
+            const size_t slot = (size_t)ring_slot(b, scan::RING);
             fmx_scan_result &r = out[k];
             r.block = b; r.end_sample = h->scan_end[c * scan::RING + slot];
             r.signal_db = ring[slot].x; r.noise_db = ring[slot].y;
             r.found = (r.signal_db - r.noise_db > (float)h->scan_rec_thr[c * scan::RING + slot]) ? 1 : 0;   // fm-processor.cpp:489 (float against int16_t)
             r.reserved = 0;
         }
-        h->scan_read[c] += take;
     }
+    h->scan_read[c] = t.next();
     *n_results = take;
     return FMX_OK;
 }
@@ -2062,24 +1966,20 @@ int fmx_rds_decode(fmx_handle h, int32_t channel, fmx_rds_info *info) {
         RdsState st;
         HIPCHK(hipMemcpy(&st, h->R.state + channel, sizeof(st), hipMemcpyDeviceToHost));
         int32_t &rd = h->rds_read_dec[(size_t)channel];
-        if (h->rds_gen_dec.size() != (size_t)h->channels) h->rds_gen_dec.assign((size_t)h->channels, 0);
-        const int32_t gen = h->rds_gen.load();
-        if (h->rds_gen_dec[(size_t)channel] != gen) { h->rds_gen_dec[(size_t)channel] = gen; rd = 0; D.reset_all(); }   // (the generation moves with resetRds only)
-        int32_t have = st.nbits - rd;
-        if (have < 0) { rd = 0; have = st.nbits; D.reset_all(); }
+        if (st.nbits < rd) { rd = 0; D.reset_all(); }      // (the count went backwards: start over)
         if (do_reset) {
             // rdsGroupDecoder::reset: PI / PTY / labels back to unknown.  The reference resets between two blocks of samples;
             // here the decoder runs behind the slicer, so the bits still pending belong to the time before the reset (the
             // old station after a retune) and are dropped.
-            D.reset_groups(); rd = st.nbits; have = 0;
+            D.reset_groups(); rd = st.nbits;
         }
-        if (have > RDS_BITS_CAP) { rd = st.nbits - RDS_BITS_CAP; have = RDS_BITS_CAP; }   // ring overrun: oldest bits lost
-        if (have > 0) {
+        const RingTake t = ring_take(st.nbits, rd, RDS_BITS_CAP, RDS_BITS_CAP);      // (ring overrun: oldest bits lost)
+        if (t.count > 0) {
             std::vector<uint8_t> ring((size_t)RDS_BITS_CAP);
             HIPCHK(hipMemcpy(ring.data(), h->R.bits + (size_t)channel * RDS_BITS_CAP, RDS_BITS_CAP, hipMemcpyDeviceToHost));
-            for (int32_t i = 0; i < have; i++) D.push_bit(ring[(size_t)((rd + i) & (RDS_BITS_CAP - 1))] != 0);
-            rd += have;
+            for (int64_t i = 0; i < t.count; i++) D.push_bit(ring[(size_t)ring_slot(t.from + i, RDS_BITS_CAP)] != 0);
         }
+        rd = (int32_t)t.next();
     }
     else if (do_reset) D.reset_groups();
     *info = D.info();
@@ -2353,9 +2253,7 @@ int wide_flush(fmx_wideband w, hipStream_t s) {
 }
 
 int wide_check_call(fmx_wideband w, int32_t fmt, float s16_den, int64_t wide_stride, int64_t n_wide, int64_t narrow_stride) {
-    if (fmt < 0 || fmt > 3) return fail(FMX_E_INVALID, "unknown IQ format");
-    int ex = 0;
-    if (fmt == 3 && (!(s16_den >= 1.0f) || std::frexp(s16_den, &ex) != 0.5f)) return fail(FMX_E_INVALID, "s16_denominator must be a power of two >= 1");
+    if (const ParamCheck pc = check_iq_format(fmt, s16_den); pc.code) return fail(pc.code, pc.msg);
     if (n_wide < 0 || n_wide % w->K != 0) return fail(FMX_E_INVALID, "n_wide must be a multiple of factor");
     if (n_wide > w->max_block) return fail(FMX_E_TOO_LARGE, "n_wide > max_block");
     if (wide_stride < n_wide) return fail(FMX_E_INVALID, "wide_stride < n_wide");

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fmx_plan.h"
+#include "fmx_needs.h"
 
 namespace fmx {
 
@@ -133,7 +134,6 @@ struct ChanState {
 // consecutive fm samples per channel.  A lane-per-channel recurrence kernel moves its 16 samples with four dwordx4
 // operations (64 contiguous bytes per lane), a time-parallel kernel maps threads as (row-in-tile fastest, channel next)
 // and stays fully coalesced (1 KB contiguous per 64 channels).
-constexpr int LO_LDS_MAX = 1024;       // LO phase periods up to this are tabulated in LDS by the input-FIR kernel
 constexpr int WT = 16;
 __host__ __device__ __forceinline__ size_t widx(int64_t r, int ch, int pitch) {
     return ((size_t)(r >> 4) * (size_t)pitch + (size_t)ch) * WT + (size_t)(r & 15);
@@ -296,7 +296,6 @@ __host__ __device__ __forceinline__ size_t tap_idx(const DeviceBuffers &B, int64
 }
 
 // ---- the reference's overlap-add filters as block machines (fmx_ola.hip; handles of few channels) ----------------------
-constexpr int OLA_MAX_CH = 64;              // FMX_P_FILTER_RESTARTS automatic: handles up to this many channels
 constexpr int OLA_MAX_TAPS = 768;           // >= 756 (fmAudioFilter) and 251 (inputFilter)
 struct OlaChan { int32_t off, len, inp; int16_t on, conv; };   // this step of one channel: samples [off, off + len) of the call enter the block at inp; conv: the block is complete behind them
 struct OlaStep { OlaChan ch[OLA_MAX_CH]; };
