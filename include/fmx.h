@@ -318,6 +318,31 @@ typedef struct fmx_rds_info {
  * since the last call into the channel's block synchroniser / group decoder and returns the current picture.
  * Independent of fmx_rds_bits (own read position). */
 int  fmx_rds_decode(fmx_handle h, int32_t channel, fmx_rds_info *info);
+/* One complete RDS group as the block synchroniser hands it to rdsGroupDecoder::decode (the reference's setGroup feed) */
+typedef struct fmx_rds_group {
+    int64_t  index;      /* the channel's group number since fmx_create, from 0 (a gap = records dropped) */
+    int64_t  end_bit;    /* slicer bit count (fmx_rds_bits' numbering) one past the group's last bit */
+    uint16_t block[4];   /* A..D as rdsGroupDecoder::decode receives them */
+} fmx_rds_group;
+/* fmx_rds_decode for the channels first_channel .. first_channel + n_channels - 1 at once, infos[k] for channel first_channel + k.  For a batch the
+ * block synchroniser runs on the GPU behind the bit slicers (every bit, in every call) and leaves the complete groups -- 11.4 per second and channel -- in a
+ * ring of 64 per channel; this call waits for the handle's last fmx_process_* call only (not for the device), reads the range's synchroniser states and
+ * group rings in two copies whatever the number of channels, and runs the group decoder (PI, PTY, PS name, radio text, AF) of each channel over its new
+ * groups on the host.  The picture is fmx_rds_decode's, field for field: the same synchroniser (tests/test_rdssync_cpu.py), the same group decoder.
+ * Own decoders and read positions: independent of fmx_rds_decode, fmx_rds_bits and fmx_rds_groups.  A channel that was read less often than every 5.6 s
+ * has lost its oldest groups (never a bit: the synchroniser does not wait for the reader).
+ * FMX_A_RESET_RDS / FMX_A_TRIGGER_FREQUENCY_CHANGE (a request of this path's own; fmx_rds_decode has its own) take effect at the next fmx_rds_decode_all:
+ * the group decoder goes back to unknown and the groups completed before that read-out are dropped; the synchroniser runs on, as the reference's does.
+ * The one difference from fmx_rds_decode: that call, whose synchroniser runs at read-out time, SKIPS the bits pending at a reset, so its synchroniser
+ * sees a gap in the stream (and resynchronises behind it); this path never skips a bit.  The two agree wherever fmx_rds_decode had nothing pending at
+ * the reset -- a caller that polls after every call.
+ * A handle on which no channel ever decoded RDS returns the fresh picture fmx_rds_decode returns there.  FMX_E_INVALID: a range outside the handle's
+ * channels, or infos NULL with n_channels > 0. */
+int  fmx_rds_decode_all(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rds_info *infos);
+/* The setGroup feed for a channel range: the groups completed since this export's last read of the channel (own read position, at most the last 64),
+ * oldest first, up to capacity_per_channel records per channel at out + k * capacity_per_channel, their number in n_groups[k]; what does not fit stays
+ * for the next read.  The same single read-out of the device as fmx_rds_decode_all. */
+int  fmx_rds_groups(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rds_group *out, int32_t capacity_per_channel, int32_t *n_groups);
 /* the same decoder over a caller-supplied bit array, from a fresh state (host only, needs no device): what a
  * recorded bit stream decodes to */
 int  fmx_rds_decode_bits(const uint8_t *bits, int32_t n_bits, fmx_rds_info *info);

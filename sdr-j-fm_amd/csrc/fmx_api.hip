@@ -163,6 +163,14 @@ struct fmx_handle_s {
     std::vector<int32_t> rds_read_dec;      // ... and by fmx_rds_decode
     std::vector<int32_t> rds_read_sym;      // ... symbols handed out by fmx_rds_symbols
     std::vector<fmx::RdsGroupDecoderHost> rds_dec;
+    // the batch read-outs (fmx_rds_decode_all, fmx_rds_groups): the synchroniser runs on the GPU (rds_sync), the host keeps a group decoder per channel
+    // and, per export, the number of the next group to take; reset requests of their own; an event behind the handle's last call, a stream and a
+    // pinned buffer for the two copies of a read-out
+    std::vector<fmx::RdsGroupDecoderHost> rds_dec_all;
+    std::vector<int64_t> rds_all_read, rds_grp_read;
+    std::vector<uint8_t> rds_reset_req_all;
+    hipEvent_t ev_call = nullptr; bool ev_call_set = false; hipStream_t rd_stream = nullptr;
+    char *rds_stage = nullptr;
     std::vector<int64_t> last_m0, last_m1;  // per channel: its 24 kS/s outputs of the last call
     // what a call needs of `params` beyond the device copy, taken under `mtx` by flush_mailbox: fmx_set_param may write `params` from another thread
     // while the processing thread enqueues the call
@@ -415,7 +423,7 @@ int ensure_rds_body(fmx_handle h);
 int ensure_rds(fmx_handle h) {
     if (h->rds_alloc) return FMX_OK;
     const int rc = ensure_rds_body(h);
-    if (rc) { h->rds_mem.release_all(); h->R = RdsBuffers{}; h->d_rds_nc0 = nullptr; }      // partial failure: give everything back, the next enable tries again
+    if (rc) { h->rds_mem.release_all(); h->R = RdsBuffers{}; h->d_rds_nc0 = nullptr; h->rds_stage = nullptr; }      // partial failure: give everything back, the next enable tries again
     return rc;
 }
 int ensure_rds_body(fmx_handle h) {
@@ -503,6 +511,9 @@ int ensure_rds_body(fmx_handle h) {
         for (int i = 0; i < 24000; i++) sc24[i] = make_float2((float)std::cos(2 * design::kPi * i / 24000), (float)std::sin(2 * design::kPi * i / 24000));
         FMXCHK(M.upload(R.sincos24, sc24));
     }
+    FMXCHK(M.alloc(R.sync, C, true));                                  // (all zero: rdsBlockSynchronizer::reset, nothing read, no group yet)
+    FMXCHK(M.alloc(R.groups, C * RDS_GROUP_RING, true));
+    if (!h->ev_call) HIPCHK(hipEventCreateWithFlags(&h->ev_call, hipEventDisableTiming));
     h->rds_read.assign(C, 0);
     {
         FMXCHK(M.alloc(h->d_rds_nc0, C, true));
@@ -1259,7 +1270,26 @@ int run_call(fmx_handle h, const void *d_iq, int32_t fmt, float s16_den, int64_t
         HIPCHK(hipEventRecord(h->pipe_evE, h->pipe_sB)); HIPCHK(hipStreamWaitEvent(s, h->pipe_evE, 0));
         h->last_pieces = (int)plan.lens.size();
     }
+    // what the batch RDS read-outs wait for instead of the whole device: the end of this call, on the stream it ran on
+    if (h->rds_alloc) { HIPCHK(hipEventRecord(h->ev_call, s)); h->ev_call_set = true; }
     if (n_frames) *n_frames = total;
+    return FMX_OK;
+}
+
+// One read-out of the device for the channels first .. first + n - 1: their synchroniser states and group rings, behind the handle's last call, in two
+// copies into the handle's pinned buffer.
+int rds_batch_fetch(fmx_handle h, int first, int n, const RdsSyncChan **st, const RdsGroupRec **grp) {
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t C = (size_t)h->channels;
+    if (!h->rd_stream) HIPCHK(hipStreamCreateWithFlags(&h->rd_stream, hipStreamNonBlocking));
+    if (!h->rds_stage) FMXCHK(h->rds_mem.alloc_pinned(h->rds_stage, C * (sizeof(RdsSyncChan) + sizeof(RdsGroupRec) * RDS_GROUP_RING)));
+    RdsGroupRec *g = reinterpret_cast<RdsGroupRec *>(h->rds_stage);                        // (the 16-byte records first: the buffer's alignment is theirs)
+    RdsSyncChan *c = reinterpret_cast<RdsSyncChan *>(h->rds_stage + C * sizeof(RdsGroupRec) * RDS_GROUP_RING);
+    if (h->ev_call_set) HIPCHK(hipStreamWaitEvent(h->rd_stream, h->ev_call, 0));
+    HIPCHK(hipMemcpyAsync(c, h->R.sync + first, sizeof(RdsSyncChan) * (size_t)n, hipMemcpyDeviceToHost, h->rd_stream));
+    HIPCHK(hipMemcpyAsync(g, h->R.groups + (size_t)first * RDS_GROUP_RING, sizeof(RdsGroupRec) * RDS_GROUP_RING * (size_t)n, hipMemcpyDeviceToHost, h->rd_stream));
+    HIPCHK(hipStreamSynchronize(h->rd_stream));
+    *st = c; *grp = g;
     return FMX_OK;
 }
 
@@ -1579,7 +1609,8 @@ int fmx_destroy(fmx_handle h) {
     for (hipStream_t st : {h->stream, h->pipe_sA, h->pipe_sP, h->pipe_sB}) if (st) (void)hipStreamSynchronize(st);
     for (auto &pr : h->prof) for (int i = 0; i < 4; i++) (void)hipEventDestroy(pr.e[i]);
     for (hipEvent_t e : h->step_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {h->ev_in, h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
+    if (h->rd_stream) { (void)hipStreamSynchronize(h->rd_stream); (void)hipStreamDestroy(h->rd_stream); }
+    for (hipEvent_t e : {h->ev_call, h->ev_in, h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
     for (hipStream_t st : {h->stream, h->pipe_sA, h->pipe_sP, h->pipe_sB}) if (st) (void)hipStreamDestroy(st);
     h->mem.release_all(); h->rds_mem.release_all();
     delete h;
@@ -1619,7 +1650,8 @@ int fmx_set_param(fmx_handle h, int32_t channel, int32_t id, double value) {
     const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
     if (id == FMX_A_RESET_RDS || id == FMX_A_TRIGGER_FREQUENCY_CHANGE) {
         if (h->rds_reset_req.size() != (size_t)h->channels) h->rds_reset_req.assign((size_t)h->channels, 0);
-        for (int c = c0; c < c1; c++) h->rds_reset_req[(size_t)c] = 1;      // resetRds (:862-864); triggerFrequencyChange calls it (:852)
+        if (h->rds_reset_req_all.size() != (size_t)h->channels) h->rds_reset_req_all.assign((size_t)h->channels, 0);
+        for (int c = c0; c < c1; c++) h->rds_reset_req[(size_t)c] = h->rds_reset_req_all[(size_t)c] = 1;      // resetRds (:862-864); triggerFrequencyChange calls it (:852); one flag per read-out path
     }
     for (int c = c0; c < c1; c++) {
         ChanUser &u = h->user[c]; ChanParams &p = h->params[c];
@@ -1983,6 +2015,64 @@ int fmx_rds_decode(fmx_handle h, int32_t channel, fmx_rds_info *info) {
     }
     else if (do_reset) D.reset_groups();
     *info = D.info();
+    return FMX_OK;
+}
+
+int fmx_rds_decode_all(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rds_info *infos) {
+    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || (n_channels > 0 && !infos)) return fail(FMX_E_INVALID, "bad argument");
+    if (n_channels == 0) return FMX_OK;
+    const size_t C = (size_t)h->channels;
+    if (h->rds_dec_all.size() != C) { h->rds_dec_all.assign(C, fmx::RdsGroupDecoderHost()); h->rds_all_read.assign(C, 0); }
+    std::vector<uint8_t> do_reset((size_t)n_channels, 0);
+    {
+        std::lock_guard<std::mutex> lk(h->mtx);
+        if (h->rds_reset_req_all.size() == C)
+            for (int k = 0; k < n_channels; k++) { do_reset[(size_t)k] = h->rds_reset_req_all[(size_t)(first_channel + k)]; h->rds_reset_req_all[(size_t)(first_channel + k)] = 0; }
+    }
+    const RdsSyncChan *st = nullptr; const RdsGroupRec *grp = nullptr;
+    if (h->rds_alloc) FMXCHK(rds_batch_fetch(h, first_channel, n_channels, &st, &grp));
+    for (int k = 0; k < n_channels; k++) {
+        const size_t c = (size_t)(first_channel + k);
+        fmx::RdsGroupDecoderHost &D = h->rds_dec_all[c];
+        if (!h->rds_alloc) { if (do_reset[(size_t)k]) D.reset_groups(); infos[k] = D.info(); continue; }
+        const RdsSyncChan &S = st[k];
+        int64_t &rd = h->rds_all_read[c];
+        // rdsGroupDecoder::reset: PI / PTY / labels back to unknown; the groups completed before this read-out belong to the time before the reset
+        // and are dropped.  The synchroniser runs on (fmx.h: where this differs from fmx_rds_decode)
+        if (do_reset[(size_t)k]) { D.reset_groups(); rd = S.groups; }
+        const RingTake t = ring_take(S.groups, rd, RDS_GROUP_RING, RDS_GROUP_RING);      // (a reader that fell behind: the oldest groups are lost)
+        for (int64_t i = 0; i < t.count; i++) {
+            int64_t end_bit; uint16_t b[4];
+            if (rds_group_read(S, grp + (size_t)k * RDS_GROUP_RING, t.from + i, &end_bit, b)) D.push_group(b);
+        }
+        rd = t.next();
+        D.set_sync_status(fmx::RdsSyncStatus{S.s.synced, S.s.n_crc_err, S.s.n_sync_err, S.s.ber_num, S.s.ber_den});
+        infos[k] = D.info();
+    }
+    return FMX_OK;
+}
+
+int fmx_rds_groups(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rds_group *out, int32_t capacity_per_channel, int32_t *n_groups) {
+    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || capacity_per_channel < 0 ||
+        (n_channels > 0 && (!n_groups || (capacity_per_channel > 0 && !out)))) return fail(FMX_E_INVALID, "bad argument");
+    for (int k = 0; k < n_channels; k++) n_groups[k] = 0;
+    if (n_channels == 0 || !h->rds_alloc) return FMX_OK;
+    const size_t C = (size_t)h->channels;
+    if (h->rds_grp_read.size() != C) h->rds_grp_read.assign(C, 0);
+    const RdsSyncChan *st = nullptr; const RdsGroupRec *grp = nullptr;
+    FMXCHK(rds_batch_fetch(h, first_channel, n_channels, &st, &grp));
+    for (int k = 0; k < n_channels; k++) {
+        int64_t &rd = h->rds_grp_read[(size_t)(first_channel + k)];
+        const RingTake t = ring_take(st[k].groups, rd, RDS_GROUP_RING, capacity_per_channel);   // (a reader that fell behind: the gap shows in `index`)
+        int32_t m = 0;
+        for (int64_t i = 0; i < t.count; i++) {
+            fmx_rds_group &r = out[(size_t)k * (size_t)capacity_per_channel + (size_t)m];
+            if (!rds_group_read(st[k], grp + (size_t)k * RDS_GROUP_RING, t.from + i, &r.end_bit, r.block)) continue;
+            r.index = t.from + i; m++;
+        }
+        rd = t.next();
+        n_groups[k] = m;
+    }
     return FMX_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "fmx_plan.h"
 #include "fmx_needs.h"
+#include "fmx_rdssync.h"
 
 namespace fmx {
 
@@ -395,6 +396,9 @@ struct RdsBuffers {
     // neighbours -- or off and on again -- has block boundaries, a /8 phase and filter contents of its own.
     const int64_t *nc0;           // [ch] samples the channel's path had processed in front of this call; < 0: the decoder is off in this call
     int *chlist;                  // [ch] scratch: the channels of one block phase (launch_rds_block)
+    // the block synchroniser behind the slicers (rds_sync, fmx_rdssync.h): its state, and the ring of the groups it completed
+    RdsSyncChan *sync;            // [ch]
+    RdsGroupRec *groups;          // [ch][RDS_GROUP_RING]
 };
 #define C_RDS_PITCH(Rb) ((Rb).pitch)
 // modes: bit k = some channel runs RDS_k; h_nc0: the host's copy of RdsBuffers::nc0

@@ -687,6 +687,25 @@ __global__ __launch_bounds__(64) void rds3_slicer(DeviceBuffers B, RdsBuffers Rb
     Rb.state[ch].nbits = s2.nbits;
 }
 
+// =================================================================================================
+// The block synchroniser (rdsBlockSynchronizer + rdsDecoder::processBit, restated in fmx_rdssync.h) behind whichever slicer ran   [lane per channel]
+// A lane takes its channel's bits from where it stopped up to RdsState::nbits through the synchroniser and leaves a record per complete group in
+// the channel's ring of 64; the host reads states and rings of every channel in one go (fmx_rds_decode_all, fmx_rds_groups) and runs only the group
+// decoder.  A channel whose decoder is off (or that sliced no bit in this launch) has nothing new and writes nothing.  Integer work, no LDS; the
+// state travels as a whole (72 bytes per lane in and out), a record is one 16-byte store.
+// Launched once per launch of the slicers, i.e. per piece of a call: a piece covers at most 32000 fm samples = 198 bits, the bit ring holds 8192, so
+// the bits a lane reads are always still there -- whatever the length of the call the pieces belong to.
+// =================================================================================================
+__global__ __launch_bounds__(64) void rds_sync(RdsBuffers Rb, int C) {
+    const int ch = blockIdx.x * 64 + threadIdx.x;
+    if (ch >= C) return;
+    const int32_t nbits = Rb.state[ch].nbits;
+    RdsSyncChan c = Rb.sync[ch];
+    if (nbits == c.rd) return;
+    rds_sync_walk(c, Rb.bits + (size_t)ch * RDS_BITS_CAP, (uint32_t)RDS_BITS_CAP, nbits, Rb.groups + (size_t)ch * RDS_GROUP_RING);
+    Rb.sync[ch] = c;
+}
+
 static void fft_fwd(const RdsBuffers &Rb, int nch, const int *chlist, hipStream_t s) {
     hipLaunchKernelGGL(rds_fft_step1, dim3(RN2 / S1C, nch), dim3(256), 0, s, Rb.U, Rb.V, nch, chlist, (const float *)nullptr, (size_t)0, 0);
     hipLaunchKernelGGL(rds_fft_step2<0>, dim3(RN1 / 16, nch), dim3(256), 0, s, Rb.V, Rb.U, nch, chlist, RdsEpi{});
@@ -819,6 +838,7 @@ void launch_rds(const DeviceBuffers &B, const RdsBuffers &Rb, const CallGeom &G,
         hipLaunchKernelGGL(rds1_slicer, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, B, Rb, C, (int)nj);
     }
     if (modes & (1 << 3)) hipLaunchKernelGGL(rds3_slicer, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, B, Rb, C, (int)nj);
+    if (modes & 0xE) hipLaunchKernelGGL(rds_sync, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, s, Rb, C);
 }
 
 }  // namespace fmx

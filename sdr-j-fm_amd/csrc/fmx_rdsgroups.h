@@ -1,5 +1,8 @@
 // fmx_rdsgroups.h -- host side of the RDS path behind the bit slicer: block synchronisation and group decoding.
-// Pure integer work at 1187.5 bit/s per channel: it stays on the host.  Behaviour follows
+// Pure integer work.  For ONE channel (fmx_rds_decode, fmx_rds_decode_bits) all of it runs here, at 1187.5 bit/s.  For a batch
+// (fmx_rds_decode_all, fmx_rds_groups) the per-bit half -- the block synchroniser -- runs on the GPU where the slicers leave their bits (fmx_rdssync.h,
+// kernel rds_sync in fmx_rds.hip), and this class takes what changes slowly: the complete groups (push_group, 11.4 per second and channel) and the
+// synchroniser's status (set_sync_status).  Its own synchroniser is what the GPU's is measured against (tests/rdssync_check.cpp).  Behaviour follows
 //   rdsDecoder::processBit          src/rds/rds-decoder.cpp:104-131
 //   rdsBlockSynchronizer            src/rds/rds-blocksynchronizer.cpp:57-336 (constants includes/rds/rds-blocksynchronizer.h:77-91)
 //   RDSGroup                        src/rds/rds-group.cpp:33-81
@@ -46,6 +49,9 @@ inline int rds_prepare_text(const uint8_t *v, int length, uint8_t *alfabet, uint
     return e - a;
 }
 
+// the block synchroniser's part of fmx_rds_info, when another synchroniser than the class's own has read the bits (fmx_rdssync.h)
+struct RdsSyncStatus { int32_t synchronized, crc_errors, sync_errors; uint32_t ber_num, ber_den; };
+
 class RdsGroupDecoderHost {
 public:
     RdsGroupDecoderHost() { reset_all(); }
@@ -63,6 +69,17 @@ public:
         case COMPLETE: decode_group(); blk_[0] = blk_[1] = blk_[2] = blk_[3] = 0; break;
         }
     }
+    // one complete group as rdsGroupDecoder::decode receives it (the group half of push_bit's COMPLETE case): for a decoder whose bits another
+    // synchroniser reads
+    void push_group(const uint16_t blk[4]) {
+        const uint16_t b[4] = {blk[0], blk[1], blk[2], blk[3]};
+        for (int i = 0; i < 4; i++) blk_[i] = b[i];
+        decode_group();
+        blk_[0] = blk_[1] = blk_[2] = blk_[3] = 0;
+    }
+    // ... and that synchroniser's status, laid over this one's in info () from now on.  The float is formed here from the two counts
+    // decode_block last divided (a zero denominator: it never has; the rate is its initial 0)
+    void set_sync_status(const RdsSyncStatus &st) { ext_ = st; ext_on_ = true; }
     const fmx_rds_info &info() { fill_info(); return info_; }
 
 private:
@@ -188,6 +205,10 @@ private:
         std::memcpy(info_.station_label, ps_, 9); std::memcpy(info_.radio_text, rt_shown_, 65);
         info_.af1_khz = af1_; info_.af2_khz = af2_; info_.music_speech = ms_; info_.di_code = di_;
         std::memcpy(info_.radio_text_ucs2, rt_u16_, sizeof(rt_u16_)); info_.radio_text_ucs2_len = (int16_t)rt_u16_len_;
+        if (ext_on_) {
+            info_.synchronized = ext_.synchronized; info_.crc_errors = ext_.crc_errors; info_.sync_errors = ext_.sync_errors;
+            info_.bit_error_rate = ext_.ber_den ? (float)ext_.ber_num / (float)ext_.ber_den : 0.f;
+        }
     }
     // synchroniser
     uint32_t stream_; bool synced_; int cur_; float ber_; uint32_t bits_in_blk_, bits_done_, bit_err_; int n_crc_err_, n_sync_err_;
@@ -197,6 +218,7 @@ private:
     char ps_[9], rt_[65], rt_shown_[65];
     uint16_t rt_u16_[65] = {0}; int rt_u16_len_ = 0; uint8_t alfabet_ = 0;
     fmx_rds_info info_;
+    RdsSyncStatus ext_{}; bool ext_on_ = false;
 };
 
 }  // namespace fmx

@@ -39,7 +39,7 @@ EXPORTS = [
     "fmx_abi_version", "fmx_last_error", "fmx_create", "fmx_destroy", "fmx_set_param", "fmx_frames_for", "fmx_filter_change_due",
     "fmx_process_host", "fmx_process_device", "fmx_process_host_raw", "fmx_process_device_raw", "fmx_synchronize",
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
-    "fmx_scan_results", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
+    "fmx_scan_results", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
     "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
 ]
 
@@ -100,6 +100,15 @@ SCAN_DTYPE = np.dtype([("block", np.int64), ("end_sample", np.int64), ("signal_d
 assert SCAN_DTYPE.itemsize == C.sizeof(FmxScanResult)
 
 
+class FmxRdsGroup(C.Structure):
+    _fields_ = [("index", C.c_int64), ("end_bit", C.c_int64), ("block", C.c_uint16 * 4)]
+
+
+# fmx_rds_group as a numpy record (Fmx.rds_groups)
+RDS_GROUP_DTYPE = np.dtype({"names": ["index", "end_bit", "block"], "formats": [np.int64, np.int64, (np.uint16, 4)], "offsets": [0, 8, 16],
+                            "itemsize": C.sizeof(FmxRdsGroup)})
+
+
 class FmxProfile(C.Structure):
     _fields_ = [("launches", C.c_int64 * 4), ("ms", C.c_double * 4), ("input_samples", C.c_int64),
                 ("channel_samples", C.c_int64)]
@@ -150,6 +159,10 @@ def load_library(path=None):
     L.fmx_get_peaks.argtypes = [vp, i32, f32p, i32, C.POINTER(i32)]
     L.fmx_rds_decode.restype = C.c_int
     L.fmx_rds_decode.argtypes = [vp, i32, C.POINTER(FmxRdsInfo)]
+    L.fmx_rds_decode_all.restype = C.c_int
+    L.fmx_rds_decode_all.argtypes = [vp, i32, i32, C.POINTER(FmxRdsInfo)]
+    L.fmx_rds_groups.restype = C.c_int
+    L.fmx_rds_groups.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
     L.fmx_rds_decode_bits.restype = C.c_int
     L.fmx_rds_decode_bits.argtypes = [C.POINTER(C.c_uint8), i32, C.POINTER(FmxRdsInfo)]
     L.fmx_rds_pty_name.restype = C.c_char_p
@@ -380,6 +393,23 @@ class Fmx:
         info = FmxRdsInfo()
         self._check(self.L.fmx_rds_decode(self.h, channel, C.byref(info)))
         return info
+
+    def rds_decode_all(self, first=0, count=None):
+        """rds_decode for the channels first .. first + count - 1 (default: up to the last) in one read-out of the device (fmx_rds_decode_all):
+        a list of FmxRdsInfo.  The block synchroniser has run on the GPU; own decoders, independent of rds_decode."""
+        count = self.channels - first if count is None else count
+        infos = (FmxRdsInfo * max(count, 1))()
+        self._check(self.L.fmx_rds_decode_all(self.h, first, count, infos))
+        return [infos[k] for k in range(count)]
+
+    def rds_groups(self, first=0, count=None, capacity=64):
+        """The complete RDS groups since the last read, per channel of the range, oldest first (fmx_rds_groups): a list of numpy structured
+        arrays (RDS_GROUP_DTYPE: index, end_bit, block[4]).  The library keeps the last 64 per channel."""
+        count = self.channels - first if count is None else count
+        out = np.zeros((max(count, 1), max(capacity, 1)), RDS_GROUP_DTYPE)
+        n = (C.c_int32 * max(count, 1))()
+        self._check(self.L.fmx_rds_groups(self.h, first, count, out.ctypes.data, capacity, n))
+        return [out[k, :n[k]].copy() for k in range(count)]
 
     def taps(self, which, channel=0):
         buf = np.zeros(1024, np.float32)

@@ -179,6 +179,9 @@ public:
         } while (n == 64);
         return total;
     }
+    // the RDS picture of this processor's channel(s) in one read-out of the device (fmx_rds_decode_all: the block synchroniser has run on the GPU,
+    // the group decoder runs here): what the rds classes' signals carried, infos[k] for channel first + k
+    bool poll_rds(fmx_rds_info *infos, int32_t first = 0, int32_t count = 1) { return h && check(fmx_rds_decode_all(h, first, count, infos)); }
     // the last block was processed while scanning: the GUI's scope feeds skip it, as the reference's loop does
     bool lastBlockScanned() const { return lastScan; }
 
