@@ -24,7 +24,11 @@ SOURCES = [
     ("fmx_promote.hip", ["-ffp-contract=off"]),
     ("fmx_scan.hip", []),
     ("fmx_wide.hip", []),
+    # the host files (fmx_host.h): they design filters through fmx_design.h, whose taps must not depend on contraction either
     ("fmx_api.hip", ["-ffp-contract=off"]),
+    ("fmx_readout.hip", ["-ffp-contract=off"]),
+    ("fmx_wide_api.hip", ["-ffp-contract=off"]),
+    ("fmx_diag.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -1,32 +1,22 @@
-// fmx_api.hip -- the C ABI of libfmx (include/fmx.h): handle, settings mailbox, table/tap
-// design + upload, per-call geometry and the three kernel launches.  A handle's device and pinned memory
-// has one owner (DevMem): fmx_destroy names no buffer.  What a handle's settings mean for its next call is decided
-// in fmx_needs.h, how the call becomes launches in fmx_plan.h (both pure, checked on the CPU); here are the locks,
-// allocations, uploads and launches.  No CPU fallback exists: every entry point fails when HIP is unavailable.
-#include "../../include/fmx.h"
-#include "../../include/fmx_debug.h"
-#include "fmx_internal.h"
-#include "fmx_scan.h"
+// fmx_api.hip -- the handle of libfmx's C ABI (include/fmx.h) and its call path: create / destroy, the settings mailbox, table/tap design + upload, the
+// block machines, promotion and demotion, per-call geometry and the kernel launches.  A handle's device and pinned memory has one owner (DevMem,
+// fmx_host.h): fmx_destroy names no buffer.  What a handle's settings mean for its next call is decided in fmx_needs.h, how the call becomes launches
+// in fmx_plan.h (both pure, checked on the CPU); here are the locks, allocations, uploads and launches.  The entry points that only read a handle are
+// in fmx_readout.hip, stage W's in fmx_wide_api.hip, the diagnostics in fmx_diag.hip.  No CPU fallback exists: every entry point fails when HIP is
+// unavailable.
+#include "fmx_host.h"
 #include "fmx_fftconv.h"
-#include "fmx_rdsgroups.h"
 #include "fmx_design.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
-#include <mutex>
-#include <string>
-#include <type_traits>
-#include <vector>
 
-using namespace fmx;
+thread_local std::string fmx::host::g_err;
 
 namespace {
 
-thread_local std::string g_err;
 int env_int(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
 // The FMX_* environment switches (diagnostics: the runs two GPU tests compare the default schedule with; none is needed by a user): read ONCE, by the
 // first fmx_create of the process -- nothing on the per-call path asks the environment.
@@ -38,200 +28,8 @@ const EnvSwitches &env_switches() {
     static const EnvSwitches sw{env_int("FMX_CALL_PIECES_SERIAL", 0) != 0, env_int("FMX_TAIL_SPLIT", 1) != 0};
     return sw;
 }
-int fail(int code, const std::string &msg) { g_err = msg; return code; }
-
-#define HIPCHK(expr)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(FMX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
-    } while (0)
-
-#define FMXCHK(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
-
-// The owner of a handle's device and pinned memory: every buffer is its own hipMalloc / hipHostMalloc, recorded the moment it exists, and given back
-// by release (one buffer, now) or release_all (fmx_destroy).  The only place of this library that allocates or frees GPU memory for a handle.
-struct DevMem {
-    std::vector<void *> dev, pinned;
-    template <class T> int alloc(T *&p, size_t n, bool zero = false) {
-        void *q = nullptr;
-        HIPCHK(hipMalloc(&q, sizeof(T) * n));
-        dev.push_back(q); p = static_cast<T *>(q);
-        if (zero) HIPCHK(hipMemset(q, 0, sizeof(T) * n));
-        return FMX_OK;
-    }
-    template <class T> int upload(T *&p, const std::vector<typename std::remove_const<T>::type> &src) {
-        FMXCHK(alloc(p, src.size()));
-        HIPCHK(hipMemcpy(dev.back(), src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
-        return FMX_OK;
-    }
-    template <class T> int alloc_pinned(T *&p, size_t n) {
-        void *q = nullptr;
-        HIPCHK(hipHostMalloc(&q, sizeof(T) * n, hipHostMallocDefault));
-        pinned.push_back(q); p = static_cast<T *>(q);
-        return FMX_OK;
-    }
-    template <class T> void release(T *&p) {          // (device or pinned; a null or unknown pointer is only nulled)
-        void *q = const_cast<void *>(static_cast<const void *>(p));
-        auto it = std::find(dev.begin(), dev.end(), q);
-        if (it != dev.end()) { dev.erase(it); (void)hipFree(q); }
-        else if ((it = std::find(pinned.begin(), pinned.end(), q)) != pinned.end()) { pinned.erase(it); (void)hipHostFree(q); }
-        p = nullptr;
-    }
-    void release_all() {
-        for (void *q : dev) (void)hipFree(q);
-        for (void *q : pinned) (void)hipHostFree(q);
-        dev.clear(); pinned.clear();
-    }
-};
 
 int next_pow2(int64_t v) { int64_t p = 1; while (p < v) p <<= 1; return (int)p; }
-
-// per-channel user-level settings (what the fmProcessor setters store)
-struct ChanUser {
-    int32_t bandwidth = 0;       // 0 = Off.  NB ctor default: inputFilterOn=false (fm-processor.cpp:149)
-    int32_t lf_cutoff = 0;       // <=0 = off. ctor default fmAudioFilterActive=false (:164)
-    int32_t bw_applied = 0, lf_applied = 0;    // what a FOLDED handle's tap sets are built from: the setter's value -- except while a mid-stream change of a batch
-                                 // is pending (fmx_handle_s::promo_pending): then the values in force when the setter arrived
-    bool bw_event = false, lf_event = false;   // setBandwidth / setlfcutoff CALLED with a value since the last call: the reference sets newInputFilter /
-                                 // newAudioFilter whatever the value (:232-239, :762-770), and its loop restarts the filter's block (:396-408)
-    int32_t deemph_us = 0;       // 0 = ctor default alpha (:174)
-    bool    ctor_volume = true;  // volumeFactor = 0.5f (:127) until setVolume
-    float   volume_db = 0.f;
-    int32_t balance = 0, panorama = 100;
-    int32_t squelch_value = 0, squelch_old = 0, squelch_level = 1;   // fm-processor.cpp:194-195; mySquelch (1, ...) :87
-    // peak meter, host half: DelayLine<DSPCOMPLEX> (fm-processor.h:54-75) over the dB pairs, windows already fetched
-    std::vector<float2> delay = std::vector<float2>(1, make_float2(-40.0f, -40.0f));
-    uint32_t delay_idx = 0;
-    int32_t pk_read = 0;
-    // scan mode (FMX_P_SCANNING, FMX_P_SCAN_THRESHOLD): startScanning / stopScanning, the constructor's thresHold (fm-processor.cpp:63,108,361-367)
-    bool    scanning = false;
-    int16_t scan_thr = 20;
-};
-
-struct ProfRec { hipEvent_t e[4]; int64_t in_samples, ch_samples; int n; };
-
-}  // namespace
-
-struct fmx_handle_s {
-    fmx_config cfg{};
-    int channels = 0, streams = 0;
-    bool streams_private = false;                                    // no two channels listen to the same stream
-    hipStream_t stream = nullptr;
-    int n_cus = 256; size_t lds_per_block = 65536;     // device limits the stage-A layout choice looks at
-    std::vector<int32_t> act_up;                                     // one-shot action bits uploaded with the last parameter upload
-    std::vector<uint8_t> rds_reset_req;                              // resetRds / triggerFrequencyChange asked for the group decoder's reset
-    hipEvent_t ev_in = nullptr;
-    std::mutex mtx;                          // guards the mailbox (set_param from any thread)
-    std::vector<ChanUser> user;
-    std::vector<ChanParams> params;          // host mirror
-    bool params_dirty = true, sets_dirty = true;
-    bool gain_dirty = true;                                          // volume / balance set since the last call (and before the first); under mtx
-    bool gain_pending = false;                                       // ... taken over by flush_mailbox together with the settings themselves (processing
-                                                                     // thread only): gain_fix_kernel runs in the first call that produces frames
-    DevMem mem;                              // every device / pinned buffer of the handle (the RDS path's: rds_mem)
-    // unique tap sets
-    std::vector<int32_t> front_keys, audio_keys;
-    int front_cap = 0, audio_cap = 0;
-    std::vector<float> h_front_taps, h_audio_taps, h_pss_taps, h_rs_taps, h_nsq, h_rds1;
-    std::vector<FrontSet> h_front_sets; std::vector<AudioSet> h_audio_sets;
-    // device: what the host writes again after the allocation (the kernels' views T.front_taps, T.front_sets, T.audio_taps, T.audio_sets, B.params are const)
-    float *d_front_taps = nullptr, *d_audio_taps = nullptr;
-    FrontSet *d_front_sets = nullptr; AudioSet *d_audio_sets = nullptr;
-    ChanParams *d_params = nullptr;
-    DeviceTables T{}; DeviceBuffers B{};
-    int ring = 0, dring = 0, sring = 0;
-    int decim = DECIM, twins = 1;            // the reference's total decimation for cfg.inputRate (12, 6 or 1) and 12 / decim (CallGeom::twins)
-    int64_t g_total = 0;                     // input samples consumed per stream
-    int64_t work_nj = 0;                     // rows of the sample-major work arrays
-    int pitch = 0;                           // their row pitch in elements
-    // staging for the host-pointer entry point
-    float2 *d_iq = nullptr, *d_pcm = nullptr;
-    // second converter (audioRate != workingRate, fm-processor.cpp:89-91,825-838)
-    int cv_p = 1, cv_q = 1, cv_nt = 0; float *d_cv_taps = nullptr; float2 *d_x48 = nullptr; int64_t x48_stride = 0;
-    // profiling
-    bool prof_on = false; std::vector<ProfRec> prof; fmx_profile prof_acc{};
-    int64_t last_J0 = 0, last_J1 = 0;
-    // RDS path (allocated when a channel first switches RDS on)
-    bool rds_alloc = false; RdsBuffers R{}; DevMem rds_mem;     // (an owner of its own: a partial failure gives the whole path back, ensure_rds)
-    // per channel: the fm samples its RDS path has processed (it stands still while the channel's decoder is off, as the reference's
-    // processor leaves its block filters, phase delay line and decimator alone then: fm-processor.cpp:733-754, :551-553), what RdsBuffers::nc0
-    // was in the last call, and the device copy of the latter
-    std::vector<int64_t> rds_nc, rds_nc0;
-    int64_t *d_rds_nc0 = nullptr;
-    std::vector<int32_t> rds_read;          // per channel: bits already handed out by fmx_rds_bits
-    std::vector<int32_t> rds_read_dec;      // ... and by fmx_rds_decode
-    std::vector<int32_t> rds_read_sym;      // ... symbols handed out by fmx_rds_symbols
-    std::vector<fmx::RdsGroupDecoderHost> rds_dec;
-    // the batch read-outs (fmx_rds_decode_all, fmx_rds_groups): the synchroniser runs on the GPU (rds_sync), the host keeps a group decoder per channel
-    // and, per export, the number of the next group to take; reset requests of their own; an event behind the handle's last call, a stream and a
-    // pinned buffer for the two copies of a read-out
-    std::vector<fmx::RdsGroupDecoderHost> rds_dec_all;
-    std::vector<int64_t> rds_all_read, rds_grp_read;
-    std::vector<uint8_t> rds_reset_req_all;
-    hipEvent_t ev_call = nullptr; bool ev_call_set = false; hipStream_t rd_stream = nullptr;
-    char *rds_stage = nullptr;
-    std::vector<int64_t> last_m0, last_m1;  // per channel: its 24 kS/s outputs of the last call
-    // what a call needs of `params` beyond the device copy, taken under `mtx` by flush_mailbox: fmx_set_param may write `params` from another thread
-    // while the processing thread enqueues the call
-    std::vector<int8_t> call_rds_mode;
-    CallNeeds needs{};                       // the summary of the settings the call's kernels and buffers are chosen from (fmx_needs.h)
-    // scan mode (fmx_scan.hip): the call's scanning channels and their thresholds (flush_mailbox); per channel the block being collected (fill), the blocks
-    // completed since fmx_create, the records handed out, and per record slot the fm sample behind the block and the threshold of the call that completed it
-    // (the device keeps (signal_db, noise_db) per slot); allocated by the first call in which a channel scans
-    std::vector<int32_t> call_scan; std::vector<int16_t> call_scan_thr;
-    bool scan_alloc = false;
-    float2 *d_scan_W = nullptr, *d_scan_carry = nullptr, *d_scan_rec = nullptr; ScanJob *d_scan_jobs = nullptr; int32_t *d_scan_mute = nullptr;
-    std::vector<ScanJob> scan_jobs;
-    std::vector<int32_t> scan_fill; std::vector<int64_t> scan_blocks, scan_read, scan_end; std::vector<int16_t> scan_rec_thr;
-    std::atomic<int> stageb_form{0};     // FMX_P_STAGEB_FORM
-    std::atomic<int> front_parts{0};     // FMX_P_FRONT_PARTS
-    std::atomic<int> front_kernel{0};    // FMX_P_FRONT_KERNEL
-    std::atomic<int> scope_taps{-1};     // FMX_P_SCOPE_TAPS
-    bool taps_kept = true;               // the last call kept the scope-tap rows (fmx_get_tap)
-    float *w_diff_mem = nullptr;         // the LR scope tap's rows (allocated when first wanted; DeviceBuffers::w_diff is null while the tap is off)
-    std::vector<std::pair<int32_t, int32_t>> hlo_key;   // per channel: the (bandwidth, oscillator) its ChanParams::hlo_* were computed for
-    int last_front_kernel = 1;           // what the last call's stage A was given (FMX_P_FRONT_KERNEL numbering): fmx_last_front_kernel
-    // a batch call whose channels need the demodulator pre-pass (a lone wave per 64 channels walking the call sample by sample: 6 % of the chip for
-    // most of the call's time) is made in pieces whose stages overlap: run_call
-    hipStream_t pipe_sA = nullptr, pipe_sP = nullptr, pipe_sB = nullptr;   // stage A (and the parallel part of the pre-pass) of piece k + 1, the recurrences of piece k, stage B / C of piece k - 1
-    hipEvent_t pipe_ev0 = nullptr, pipe_evA = nullptr, pipe_evD = nullptr, pipe_evP = nullptr, pipe_evE = nullptr, pipe_evB[2] = {nullptr, nullptr};
-    std::atomic<int> pipe_rows{-1};      // FMX_P_CALL_PIECES: fm samples per piece (-1 automatic, 0 never)
-    int last_pieces = 1;                 // overlapping pieces the last call was made in (fmx_last_call_pieces)
-    int last_second_group = 0;           // channels of the second stage-B / C group of the last call (fmx_last_second_group)
-    int my_count_host = 0;               // the reference's myCount (fm-processor.cpp:662-684) as stage B keeps it in every channel's state: the same in all of them
-    PreLook pre_look{};                  // pre_kernel's look-back buffers (ensure_ola)
-    char *hp_iq = nullptr; float2 *hp_pcm = nullptr;   // fmx_process_host: pinned, device-visible staging of small calls
-    // the reference's two overlap-add filters as the block machines they are (fmx_ola.hip): handles of up to OLA_MAX_CH channels
-    bool ola_mode = false;               // FMX_P_FILTER_RESTARTS resolved (fixed once the first call has been made)
-    struct OlaSide {
-        int L = 0, degree = 0;
-        float2 *A = nullptr, *C = nullptr, *over = nullptr, *over_new = nullptr; float *taps = nullptr;
-        std::vector<int32_t> inp, on, key;   // per channel: block position, Pass () in use, the setting the kernel was designed for (-1: none yet)
-    } ola_in, ola_au;
-    float2 *d_v = nullptr, *d_u = nullptr, *d2ring = nullptr;   // pre_kernel's output, the input filter's output ([channels][max_block]), the audio filter's output ring
-    // A batch (folded filters) whose filters are changed in mid-stream: the setter stays pending while the library keeps the streams' samples (fmx_promote.hip),
-    // then the handle switches to the block machines (promote).  FMX_P_FILTER_RESTARTS = 2 pins the folded filters (the change then applies at once, as
-    // rounds 1-5 applied it: a different glitch of one filter latency).
-    bool folded_pinned = false;          // FMX_P_FILTER_RESTARTS = 2 was asked for
-    bool promoted = false;               // a block-machine handle by promotion: goes back to the folded filters once its machines have been quiet (demote)
-    bool demo_capture = false;           // ... and is keeping its streams for that
-    int64_t last_filter_event_g = 0;     // stream position at which a filter setter was last applied (ola_take_settings)
-    std::vector<int64_t> origin_in, origin_au;   // per channel: the stream position (input samples / fm samples) at which the filter's block counter was last 0, as far as a
-                                         // FOLDED handle knows it (0 from fmx_create; the machines' own counters at a demotion)
-    bool promo_pending = false;          // a filter setter arrived behind the first call
-    bool promo_recapture = false;        // ... and a setter of what pre_kernel applies (RF DC removal, balance, oscillator) behind it: the kept samples start over
-    int64_t promo_have = 0, promo_g0 = 0;   // samples kept per stream, and the stream position of the first
-    float2 *tail_iq = nullptr; int64_t tail_cap = 0; FrontSnap *tail_snap = nullptr;
-    size_t old_sets_cap = 0;
-    ChanParams *d_params_replay = nullptr; FrontSet *d_old_sets = nullptr; int32_t *d_old_set_of = nullptr; float2 *d_au_tail = nullptr;
-    // the block machines' steps of a handle above OLA_MAX_CH channels: tables in device memory (the launchers take a step by value up to 64 channels),
-    // a ring of STEP_SLOTS tables, each copied from pinned host memory on the call's stream in front of the kernels that read it
-    static constexpr int STEP_SLOTS = 32;
-    OlaChan *step_dev = nullptr, *step_host = nullptr; hipEvent_t step_ev[STEP_SLOTS] = {}; bool step_used[STEP_SLOTS] = {}; int step_next = 0;
-};
-
-namespace {
 
 // ---- tap-set construction -----------------------------------------------------------------
 // Front end = inputFilter (optional) * fmBand_1 * fmBand_2 folded into one real polyphase FIR evaluated by stage A's /12 kernel.
@@ -306,7 +104,9 @@ void build_audio_set(int32_t lf, int32_t fmRate, const std::vector<float> &rs, f
     for (int kk = 0; kk < as->ntaps; kk++) taps[kk] = (float)g[as->ntaps - 1 - kk];   // reversed
 }
 
-int ensure_sets(fmx_handle h) {
+}  // namespace
+
+int fmx::host::ensure_sets(fmx_handle h) {
     // deduplicate bandwidth / lf-cutoff values into tap sets, upload when changed
     std::vector<int32_t> fk, ak;
     for (int c = 0; c < h->channels; c++) {
@@ -391,6 +191,8 @@ int ensure_sets(fmx_handle h) {
     h->sets_dirty = false;
     return FMX_OK;
 }
+
+namespace {
 
 void refresh_derived(fmx_handle h, int c) {
     // the arithmetic of the setters themselves
@@ -514,7 +316,7 @@ int ensure_rds_body(fmx_handle h) {
     FMXCHK(M.alloc(R.sync, C, true));                                  // (all zero: rdsBlockSynchronizer::reset, nothing read, no group yet)
     FMXCHK(M.alloc(R.groups, C * RDS_GROUP_RING, true));
     if (!h->ev_call) HIPCHK(hipEventCreateWithFlags(&h->ev_call, hipEventDisableTiming));
-    h->rds_read.assign(C, 0);
+    h->rd.bits.assign(C, 0);
     {
         FMXCHK(M.alloc(h->d_rds_nc0, C, true));
         FMXCHK(M.alloc(R.chlist, C, true));
@@ -822,7 +624,7 @@ int ensure_scan(fmx_handle h) {
     FMXCHK(h->mem.alloc(h->d_scan_rec, C * scan::RING, true));
     FMXCHK(h->mem.alloc(h->d_scan_jobs, C));
     FMXCHK(h->mem.alloc(h->d_scan_mute, C));
-    h->scan_fill.assign(C, 0); h->scan_blocks.assign(C, 0); h->scan_read.assign(C, 0);
+    h->scan_fill.assign(C, 0); h->scan_blocks.assign(C, 0); h->rd.scan.assign(C, 0);
     h->scan_end.assign(C * scan::RING, 0); h->scan_rec_thr.assign(C * scan::RING, 0);
     h->scan_alloc = true;
     return FMX_OK;
@@ -941,8 +743,6 @@ void frames_geom(const fmx_handle h, int64_t n, CallGeom *G) {
     // newConverter: 192 frames in -> 48 out (newconverter.cpp:55-80, inputLimit = fmRate/1000)
     G->M0 = 48 * (G->J0 / 192); G->M1 = 48 * (G->J1 / 192);
 }
-// frames the second converter has put out after `in` frames at the working rate: outputs m with m q < in p
-int64_t conv2_out(const fmx_handle h, int64_t in) { return h->cv_nt ? (in * h->cv_p + h->cv_q - 1) / h->cv_q : in; }
 // PCM frames a call of n input samples produces now
 int64_t call_frames(const fmx_handle h, int64_t n) { CallGeom G{}; frames_geom(h, n, &G); return conv2_out(h, G.M1) - conv2_out(h, G.M0); }
 
@@ -961,8 +761,6 @@ int ensure_pipe_streams(fmx_handle h) {
     for (hipEvent_t *e : {&h->pipe_ev0, &h->pipe_evA, &h->pipe_evD, &h->pipe_evP, &h->pipe_evE, &h->pipe_evB[0], &h->pipe_evB[1]}) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     return FMX_OK;
 }
-
-int bytes_per_sample(int32_t fmt) { return fmt == FMX_IQ_F32 ? 8 : (fmt == FMX_IQ_S16 ? 4 : 2); }
 
 // the arguments of an fmx_process_* call, checked once at its head (run_call; fmx_process_host_raw for the caller's PCM buffer)
 int check_call(fmx_handle h, int32_t fmt, float s16_den, int64_t n, int64_t pcm_stride) {
@@ -1276,65 +1074,8 @@ int run_call(fmx_handle h, const void *d_iq, int32_t fmt, float s16_den, int64_t
     return FMX_OK;
 }
 
-// One read-out of the device for the channels first .. first + n - 1: their synchroniser states and group rings, behind the handle's last call, in two
-// copies into the handle's pinned buffer.
-int rds_batch_fetch(fmx_handle h, int first, int n, const RdsSyncChan **st, const RdsGroupRec **grp) {
-    HIPCHK(hipSetDevice(h->cfg.device));
-    const size_t C = (size_t)h->channels;
-    if (!h->rd_stream) HIPCHK(hipStreamCreateWithFlags(&h->rd_stream, hipStreamNonBlocking));
-    if (!h->rds_stage) FMXCHK(h->rds_mem.alloc_pinned(h->rds_stage, C * (sizeof(RdsSyncChan) + sizeof(RdsGroupRec) * RDS_GROUP_RING)));
-    RdsGroupRec *g = reinterpret_cast<RdsGroupRec *>(h->rds_stage);                        // (the 16-byte records first: the buffer's alignment is theirs)
-    RdsSyncChan *c = reinterpret_cast<RdsSyncChan *>(h->rds_stage + C * sizeof(RdsGroupRec) * RDS_GROUP_RING);
-    if (h->ev_call_set) HIPCHK(hipStreamWaitEvent(h->rd_stream, h->ev_call, 0));
-    HIPCHK(hipMemcpyAsync(c, h->R.sync + first, sizeof(RdsSyncChan) * (size_t)n, hipMemcpyDeviceToHost, h->rd_stream));
-    HIPCHK(hipMemcpyAsync(g, h->R.groups + (size_t)first * RDS_GROUP_RING, sizeof(RdsGroupRec) * RDS_GROUP_RING * (size_t)n, hipMemcpyDeviceToHost, h->rd_stream));
-    HIPCHK(hipStreamSynchronize(h->rd_stream));
-    *st = c; *grp = g;
-    return FMX_OK;
-}
-
-int prof_drain(fmx_handle h) {
-    for (auto &pr : h->prof) {
-        HIPCHK(hipEventSynchronize(pr.e[3]));
-        for (int k = 0; k < 3; k++) {
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, pr.e[k], pr.e[k + 1]));
-            h->prof_acc.ms[k] += ms; h->prof_acc.launches[k] += 1;
-        }
-        h->prof_acc.input_samples += pr.in_samples; h->prof_acc.channel_samples += pr.ch_samples;
-        for (int i = 0; i < 4; i++) (void)hipEventDestroy(pr.e[i]);
-    }
-    h->prof.clear();
-    return FMX_OK;
-}
 
 }  // namespace
-
-// ---- diagnostics: the practical HBM ceiling (SURVEY 8d asks for the measured device-copy bandwidth next to the nominal 8 TB/s)
-namespace fmx {
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-// mode 0: dst[i] = src[i] (float2 copy, 16 B per lane per access);  mode 1: stage A's traffic shape: read 12 float2, write 1;  mode 2: the same reads and NO
-// write (a sum that is never the sentinel): what this GPU reads at when nothing is written -- the ceiling of `roofline.frac_read_only`.
-template <int MODE>
-__global__ __launch_bounds__(256) void stream_probe_kernel(const f32x4_t *__restrict__ src, f32x4_t *__restrict__ dst, size_t n16) {
-    const size_t stride = (size_t)gridDim.x * 256;
-    if (MODE == 0) {
-        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += stride) __builtin_nontemporal_store(__builtin_nontemporal_load(src + i), dst + i);
-    } else {
-        // each lane reads 6 x 16 B (12 float2) spaced a wave apart (coalesced), sums, and writes one float2 per 12 read
-        const size_t ngroups = n16 / (6 * 64);
-        const size_t wave = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = stride >> 6;
-        const int lane = threadIdx.x & 63;
-        for (size_t g = wave; g < ngroups; g += nwaves) {
-            f32x4_t a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int k = 0; k < 6; k++) a += __builtin_nontemporal_load(src + (g * 6 + k) * 64 + lane);
-            if (MODE == 2) { if (a.x + a.z == 1.2345e33f) reinterpret_cast<float2 *>(dst)[lane] = make_float2(a.y, a.w); }
-            else reinterpret_cast<float2 *>(dst)[g * 64 + lane] = make_float2(a.x + a.z, a.y + a.w);
-        }
-    }
-}
-}  // namespace fmx
 
 namespace {
 
@@ -1390,6 +1131,7 @@ int init_channels(fmx_handle h, const fmx_config *cfg, int decim, const Conv2Des
     }
     h->ola_mode = filter_form(0, h->channels).ola_mode;          // FMX_P_FILTER_RESTARTS = 0 (automatic)
     h->user.assign(h->channels, ChanUser());
+    h->rd.init((size_t)h->channels);
     h->params.assign(h->channels, ChanParams());
     for (int c = 0; c < h->channels; c++) {
         ChanParams &p = h->params[c];
@@ -1649,9 +1391,7 @@ int fmx_set_param(fmx_handle h, int32_t channel, int32_t id, double value) {
     std::lock_guard<std::mutex> lk(h->mtx);
     const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
     if (id == FMX_A_RESET_RDS || id == FMX_A_TRIGGER_FREQUENCY_CHANGE) {
-        if (h->rds_reset_req.size() != (size_t)h->channels) h->rds_reset_req.assign((size_t)h->channels, 0);
-        if (h->rds_reset_req_all.size() != (size_t)h->channels) h->rds_reset_req_all.assign((size_t)h->channels, 0);
-        for (int c = c0; c < c1; c++) h->rds_reset_req[(size_t)c] = h->rds_reset_req_all[(size_t)c] = 1;      // resetRds (:862-864); triggerFrequencyChange calls it (:852); one flag per read-out path
+        for (int c = c0; c < c1; c++) h->rd.reset_dec[(size_t)c] = h->rd.reset_dec_all[(size_t)c] = 1;      // resetRds (:862-864); triggerFrequencyChange calls it (:852); one flag per read-out path
     }
     for (int c = c0; c < c1; c++) {
         ChanUser &u = h->user[c]; ChanParams &p = h->params[c];
@@ -1780,680 +1520,6 @@ int fmx_synchronize(fmx_handle h) {
     if (!h) return fail(FMX_E_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->cfg.device));
     HIPCHK(hipDeviceSynchronize());
-    return FMX_OK;
-}
-
-int fmx_get_meta(fmx_handle h, int32_t channel, fmx_meta *m) {
-    if (!h || !m || channel < 0 || channel >= h->channels) return fail(FMX_E_INVALID, "bad argument");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipDeviceSynchronize());
-    ChanState st;
-    HIPCHK(hipMemcpy(&st, h->B.state + channel, sizeof(st), hipMemcpyDeviceToHost));
-    m->DcValRf = st.meta_dc_rf; m->DcValIf = st.meta_dc_if; m->PssPhaseShiftDegree = st.meta_pss_deg;
-    m->PssPhaseChange = st.meta_pss_change; m->PssState = st.meta_pss_state;
-    m->PilotPllLockStrength = st.meta_lock_strength; m->PilotPllLocked = st.meta_locked;
-    m->live_pilot_locked = (h->params[channel].fm_mode != 2) ? st.pil_locked : 0;
-    m->live_lock_strength = (h->params[channel].fm_mode != 2) ? st.pil_lock : 0.f;
-    m->live_dc_if = st.fm_afc; m->squelch_active = (h->params[channel].squelch_mode != 0) ? st.sq_suppress : 0;
-    m->fm_samples = h->g_total / h->decim; m->pcm_frames = conv2_out(h, 48 * ((h->g_total / h->decim) / 192));
-    m->live_rf_dc_re = st.dc_re; m->live_rf_dc_im = st.dc_im;
-    return FMX_OK;
-}
-
-int fmx_get_peaks(fmx_handle h, int32_t channel, float *lr_db, int32_t capacity, int32_t *n_events) {
-    if (!h || !n_events || channel < 0 || channel >= h->channels || capacity < 0 || (capacity > 0 && !lr_db))
-        return fail(FMX_E_INVALID, "bad argument");
-    if (!h->taps_kept) return fail(FMX_E_UNSUPPORTED, "this handle does not run the peak-level meter: a display feed, automatic only up to 64 channels -- fmx_set_param (h, -1, FMX_P_SCOPE_TAPS, 1) and one call switch it on");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipDeviceSynchronize());
-    ChanState st;
-    HIPCHK(hipMemcpy(&st, h->B.state + channel, sizeof(st), hipMemcpyDeviceToHost));
-    std::lock_guard<std::mutex> lk(h->mtx);
-    ChanUser &u = h->user[channel];
-    const RingTake t = ring_take(st.pk_events, u.pk_read, PK_RING, capacity);      // (a caller that fell behind: the oldest windows are gone)
-    const int take = (int)t.count;
-    if (take > 0) {
-        std::vector<float2> ring((size_t)PK_RING);
-        HIPCHK(hipMemcpy(ring.data(), h->B.pk_ring + (size_t)channel * PK_RING, sizeof(float2) * PK_RING, hipMemcpyDeviceToHost));
-        for (int k = 0; k < take; k++) {
-            const float2 pk = ring[(size_t)ring_slot(t.from + k, PK_RING)];
-            // fm-processor.cpp:785-794: float log10 (std::log10 of a float), -40 dB for silence, then the display delay line
-            const float ldb = pk.x > 0.0f ? 20.0f * std::log10(pk.x) : -40.0f;
-            const float rdb = pk.y > 0.0f ? 20.0f * std::log10(pk.y) : -40.0f;
-            u.delay[u.delay_idx] = make_float2(ldb, rdb);
-            u.delay_idx = (u.delay_idx + 1) % (uint32_t)u.delay.size();
-            lr_db[2 * k] = u.delay[u.delay_idx].x; lr_db[2 * k + 1] = u.delay[u.delay_idx].y;
-        }
-    }
-    u.pk_read = (int32_t)t.next();
-    *n_events = take;
-    return FMX_OK;
-}
-
-int fmx_get_tap(fmx_handle h, int32_t channel, int32_t tap, float *dst, int64_t n) {
-    if (!h || !dst || channel < 0 || channel >= h->channels || n < 0) return fail(FMX_E_INVALID, "bad argument");
-    const int64_t J1 = h->g_total / h->decim;
-    if (tap != 4 && (n > J1 || n > (h->last_J1 - h->last_J0))) return fail(FMX_E_INVALID, "n exceeds the samples produced by the last call");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipDeviceSynchronize());
-    const char *base; int64_t cap, elem, delay = 0;
-    switch (tap) {
-    case FMX_TAP_FM_IQ: base = (const char *)(h->B.zring + (size_t)channel * h->ring); cap = h->ring; elem = sizeof(float2);
-        delay = h->h_front_sets[h->params[channel].front_set].delay_fm; break;
-    case FMX_TAP_DEMOD: case FMX_TAP_LR_RAW: case FMX_TAP_PILOT_PHASE: {
-        // these taps are read back from the last call's work arrays (channel-major rows of the call), rows [nj - n, nj)
-        const int64_t nj = h->last_J1 - h->last_J0, r0 = nj - n;
-        if (!h->taps_kept) return fail(FMX_E_UNSUPPORTED, "this handle does not keep the demodulator / LR / pilot-phase scope taps: display feeds, automatic only up to 64 channels -- fmx_set_param (h, -1, FMX_P_SCOPE_TAPS, 1) and one call switch them on");
-        if (n == 0) return FMX_OK;
-        {                            // this call's rows are contiguous per channel
-            const size_t off = (size_t)channel * (size_t)h->work_nj + (size_t)r0;
-            std::vector<float> a((size_t)n), b;
-            HIPCHK(hipMemcpy(a.data(), (tap == FMX_TAP_PILOT_PHASE ? h->B.w_cur : h->B.w_dem) + off, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-            if (tap == FMX_TAP_LR_RAW) {
-                b.resize((size_t)n);
-                HIPCHK(hipMemcpy(b.data(), h->B.w_diff + off, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-                for (int64_t i = 0; i < n; i++) { dst[2 * i] = a[(size_t)i]; dst[2 * i + 1] = b[(size_t)i]; }
-            } else std::memcpy(dst, a.data(), sizeof(float) * (size_t)n);
-        }
-        return FMX_OK; }
-    case FMX_TAP_PRE_RESAMPLER: base = (const char *)((h->ola_mode && h->d2ring ? h->d2ring : h->B.dring) + (size_t)channel * h->dring); cap = h->dring; elem = sizeof(float2); break;
-    case 4: {   // FMX_TAP_RDS_IQ: complex @24 kS/s after rdsDecimator (:553): the last n outputs of the last call
-        if (!h->rds_alloc) return fail(FMX_E_INVALID, "RDS is off");
-        const int64_t lm0 = h->last_m0[(size_t)channel], lm1 = h->last_m1[(size_t)channel];      // (the channel's own count: fmx_last_rds_samples_of)
-        if (n > lm1 - lm0) return fail(FMX_E_INVALID, "n exceeds the RDS samples the channel produced in the last call");
-        char *o = (char *)dst;
-        for (int64_t m = lm1 - n; m < lm1;) {
-            const int64_t pos = m & (RDS24_RING - 1);
-            const int64_t run = std::min<int64_t>(RDS24_RING - pos, lm1 - m);
-            HIPCHK(hipMemcpy(o, (const char *)(h->R.rds24 + (size_t)channel * RDS24_RING) + pos * sizeof(float2), (size_t)run * sizeof(float2), hipMemcpyDeviceToHost));
-            o += run * sizeof(float2); m += run;
-        }
-        return FMX_OK; }
-    default: return fail(FMX_E_INVALID, "unknown tap id");
-    }
-    // samples j in [J1-n, J1) live at ring index (j - delay) & (cap-1); before the stream start they are 0
-    char *out = (char *)dst;
-    for (int64_t j = J1 - n; j < J1;) {
-        const int64_t jv = j - delay;
-        if (jv < 0) { std::memset(out, 0, elem); out += elem; j++; continue; }
-        const int64_t pos = jv & (cap - 1);
-        const int64_t run = std::min<int64_t>(cap - pos, J1 - j);
-        HIPCHK(hipMemcpy(out, base + pos * elem, (size_t)(run * elem), hipMemcpyDeviceToHost));
-        out += run * elem; j += run;
-    }
-    return FMX_OK;
-}
-
-int fmx_rds_bits(fmx_handle h, int32_t channel, uint8_t *bits, int32_t capacity, int32_t *n_bits) {
-    if (!h || channel < 0 || channel >= h->channels || !n_bits || capacity < 0) return fail(FMX_E_INVALID, "bad argument");
-    *n_bits = 0;
-    if (!h->rds_alloc) return FMX_OK;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipDeviceSynchronize());
-    RdsState st;
-    HIPCHK(hipMemcpy(&st, h->R.state + channel, sizeof(st), hipMemcpyDeviceToHost));
-    const RingTake t = ring_take(st.nbits, h->rds_read[channel], RDS_BITS_CAP, bits ? capacity : 0);   // (ring overrun: oldest bits lost)
-    if (t.count > 0) {
-        std::vector<uint8_t> ring((size_t)RDS_BITS_CAP);
-        HIPCHK(hipMemcpy(ring.data(), h->R.bits + (size_t)channel * RDS_BITS_CAP, RDS_BITS_CAP, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < t.count; i++) bits[i] = ring[(size_t)ring_slot(t.from + i, RDS_BITS_CAP)];
-    }
-    h->rds_read[channel] = (int32_t)t.next();
-    *n_bits = (int32_t)t.count;
-    return FMX_OK;
-}
-
-int fmx_rds_symbols(fmx_handle h, int32_t channel, float *iq, int32_t capacity, int32_t *n_symbols) {
-    if (!h || channel < 0 || channel >= h->channels || !n_symbols || capacity < 0) return fail(FMX_E_INVALID, "bad argument");
-    *n_symbols = 0;
-    if (!h->rds_alloc) return FMX_OK;
-    if ((int)h->rds_read_sym.size() != h->channels) h->rds_read_sym.assign((size_t)h->channels, 0);
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipDeviceSynchronize());
-    RdsState st;
-    HIPCHK(hipMemcpy(&st, h->R.state + channel, sizeof(st), hipMemcpyDeviceToHost));
-    int32_t &rd = h->rds_read_sym[(size_t)channel];
-    if (st.nbits < rd) rd = 0;                  // (the count went backwards: start over)
-    const RingTake t = ring_take(st.nbits, rd, RDS_SYM_CAP, iq ? capacity : 0);        // (ring overrun: oldest symbols lost)
-    if (t.count > 0) {
-        std::vector<float2> ring((size_t)RDS_SYM_CAP);
-        HIPCHK(hipMemcpy(ring.data(), h->R.sym + (size_t)channel * RDS_SYM_CAP, sizeof(float2) * RDS_SYM_CAP, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < t.count; i++) { const float2 v = ring[(size_t)ring_slot(t.from + i, RDS_SYM_CAP)]; iq[2 * i] = v.x; iq[2 * i + 1] = v.y; }
-        *n_symbols = (int32_t)t.count;
-    }
-    rd = (int32_t)t.next();
-    return FMX_OK;
-}
-
-int64_t fmx_last_fm_samples(fmx_handle h) { return h ? (int64_t)(h->last_J1 - h->last_J0) : 0; }
-int fmx_scan_results(fmx_handle h, int32_t channel, fmx_scan_result *out, int32_t capacity, int32_t *n_results) {
-    if (!h || !n_results || channel < 0 || channel >= h->channels || capacity < 0 || (capacity > 0 && !out)) return fail(FMX_E_INVALID, "bad argument");
-    *n_results = 0;
-    if (!h->scan_alloc) return FMX_OK;
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipDeviceSynchronize());
-    std::lock_guard<std::mutex> lk(h->mtx);
-    const size_t c = (size_t)channel;
-    const RingTake t = ring_take(h->scan_blocks[c], h->scan_read[c], scan::RING, capacity);      // (a caller that fell behind: the oldest records are gone)
-    const int take = (int)t.count;
-    if (take > 0) {
-        std::vector<float2> ring((size_t)scan::RING);
-        HIPCHK(hipMemcpy(ring.data(), h->d_scan_rec + c * scan::RING, sizeof(float2) * scan::RING, hipMemcpyDeviceToHost));
-        for (int k = 0; k < take; k++) {
-            const int64_t b = t.from + k;
-            const size_t slot = (size_t)ring_slot(b, scan::RING);
-            fmx_scan_result &r = out[k];
-            r.block = b; r.end_sample = h->scan_end[c * scan::RING + slot];
-            r.signal_db = ring[slot].x; r.noise_db = ring[slot].y;
-            r.found = (r.signal_db - r.noise_db > (float)h->scan_rec_thr[c * scan::RING + slot]) ? 1 : 0;   // fm-processor.cpp:489 (float against int16_t)
-            r.reserved = 0;
-        }
-    }
-    h->scan_read[c] = t.next();
-    *n_results = take;
-    return FMX_OK;
-}
-
-int64_t fmx_pll_replays(fmx_handle h, int32_t channel) {
-    if (!h || channel >= h->channels) return (int64_t)fail(FMX_E_INVALID, "bad argument");
-    if (hipSetDevice(h->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return (int64_t)fail(FMX_E_HIP, "device error");
-    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
-    std::vector<ChanState> st((size_t)(c1 - c0));
-    if (hipMemcpy(st.data(), h->B.state + c0, sizeof(ChanState) * st.size(), hipMemcpyDeviceToHost) != hipSuccess) return (int64_t)fail(FMX_E_HIP, "device error");
-    int64_t n = 0;
-    for (auto &s : st) n += s.pll_replays;
-    return n;
-}
-int64_t fmx_pll_exact_segments(fmx_handle h, int32_t channel) {
-    if (!h || channel >= h->channels) return (int64_t)fail(FMX_E_INVALID, "bad argument");
-    if (hipSetDevice(h->cfg.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return (int64_t)fail(FMX_E_HIP, "device error");
-    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
-    std::vector<ChanState> st((size_t)(c1 - c0));
-    if (hipMemcpy(st.data(), h->B.state + c0, sizeof(ChanState) * st.size(), hipMemcpyDeviceToHost) != hipSuccess) return (int64_t)fail(FMX_E_HIP, "device error");
-    int64_t n = 0;
-    for (auto &s : st) n += s.pll_exact_segs;
-    return n;
-}
-int32_t fmx_last_front_kernel(fmx_handle h) { return h ? h->last_front_kernel : 0; }
-int32_t fmx_last_call_pieces(fmx_handle h) { return h ? h->last_pieces : 0; }
-int32_t fmx_last_second_group(fmx_handle h) { return h ? h->last_second_group : 0; }
-int64_t fmx_last_rds_samples_of(fmx_handle h, int32_t channel) {
-    if (!h || !h->rds_alloc || channel < 0 || channel >= h->channels) return 0;
-    return h->last_m1[(size_t)channel] - h->last_m0[(size_t)channel];
-}
-int64_t fmx_last_rds_samples(fmx_handle h) { return fmx_last_rds_samples_of(h, 0); }
-
-int fmx_rds_decode(fmx_handle h, int32_t channel, fmx_rds_info *info) {
-    if (!h || channel < 0 || channel >= h->channels || !info) return fail(FMX_E_INVALID, "bad argument");
-    if ((int)h->rds_dec.size() != h->channels) { h->rds_dec.assign((size_t)h->channels, fmx::RdsGroupDecoderHost()); h->rds_read_dec.assign((size_t)h->channels, 0); }
-    fmx::RdsGroupDecoderHost &D = h->rds_dec[(size_t)channel];
-    bool do_reset = false;
-    {
-        std::lock_guard<std::mutex> lk(h->mtx);
-        if (h->rds_reset_req.size() == (size_t)h->channels && h->rds_reset_req[(size_t)channel]) { h->rds_reset_req[(size_t)channel] = 0; do_reset = true; }
-    }
-    if (h->rds_alloc) {
-        HIPCHK(hipSetDevice(h->cfg.device));
-        HIPCHK(hipDeviceSynchronize());
-        RdsState st;
-        HIPCHK(hipMemcpy(&st, h->R.state + channel, sizeof(st), hipMemcpyDeviceToHost));
-        int32_t &rd = h->rds_read_dec[(size_t)channel];
-        if (st.nbits < rd) { rd = 0; D.reset_all(); }      // (the count went backwards: start over)
-        if (do_reset) {
-            // rdsGroupDecoder::reset: PI / PTY / labels back to unknown.  The reference resets between two blocks of samples;
-            // here the decoder runs behind the slicer, so the bits still pending belong to the time before the reset (the
-            // old station after a retune) and are dropped.
-            D.reset_groups(); rd = st.nbits;
-        }
-        const RingTake t = ring_take(st.nbits, rd, RDS_BITS_CAP, RDS_BITS_CAP);      // (ring overrun: oldest bits lost)
-        if (t.count > 0) {
-            std::vector<uint8_t> ring((size_t)RDS_BITS_CAP);
-            HIPCHK(hipMemcpy(ring.data(), h->R.bits + (size_t)channel * RDS_BITS_CAP, RDS_BITS_CAP, hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < t.count; i++) D.push_bit(ring[(size_t)ring_slot(t.from + i, RDS_BITS_CAP)] != 0);
-        }
-        rd = (int32_t)t.next();
-    }
-    else if (do_reset) D.reset_groups();
-    *info = D.info();
-    return FMX_OK;
-}
-
-int fmx_rds_decode_all(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rds_info *infos) {
-    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || (n_channels > 0 && !infos)) return fail(FMX_E_INVALID, "bad argument");
-    if (n_channels == 0) return FMX_OK;
-    const size_t C = (size_t)h->channels;
-    if (h->rds_dec_all.size() != C) { h->rds_dec_all.assign(C, fmx::RdsGroupDecoderHost()); h->rds_all_read.assign(C, 0); }
-    std::vector<uint8_t> do_reset((size_t)n_channels, 0);
-    {
-        std::lock_guard<std::mutex> lk(h->mtx);
-        if (h->rds_reset_req_all.size() == C)
-            for (int k = 0; k < n_channels; k++) { do_reset[(size_t)k] = h->rds_reset_req_all[(size_t)(first_channel + k)]; h->rds_reset_req_all[(size_t)(first_channel + k)] = 0; }
-    }
-    const RdsSyncChan *st = nullptr; const RdsGroupRec *grp = nullptr;
-    if (h->rds_alloc) FMXCHK(rds_batch_fetch(h, first_channel, n_channels, &st, &grp));
-    for (int k = 0; k < n_channels; k++) {
-        const size_t c = (size_t)(first_channel + k);
-        fmx::RdsGroupDecoderHost &D = h->rds_dec_all[c];
-        if (!h->rds_alloc) { if (do_reset[(size_t)k]) D.reset_groups(); infos[k] = D.info(); continue; }
-        const RdsSyncChan &S = st[k];
-        int64_t &rd = h->rds_all_read[c];
-        // rdsGroupDecoder::reset: PI / PTY / labels back to unknown; the groups completed before this read-out belong to the time before the reset
-        // and are dropped.  The synchroniser runs on (fmx.h: where this differs from fmx_rds_decode)
-        if (do_reset[(size_t)k]) { D.reset_groups(); rd = S.groups; }
-        const RingTake t = ring_take(S.groups, rd, RDS_GROUP_RING, RDS_GROUP_RING);      // (a reader that fell behind: the oldest groups are lost)
-        for (int64_t i = 0; i < t.count; i++) {
-            int64_t end_bit; uint16_t b[4];
-            if (rds_group_read(S, grp + (size_t)k * RDS_GROUP_RING, t.from + i, &end_bit, b)) D.push_group(b);
-        }
-        rd = t.next();
-        D.set_sync_status(fmx::RdsSyncStatus{S.s.synced, S.s.n_crc_err, S.s.n_sync_err, S.s.ber_num, S.s.ber_den});
-        infos[k] = D.info();
-    }
-    return FMX_OK;
-}
-
-int fmx_rds_groups(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rds_group *out, int32_t capacity_per_channel, int32_t *n_groups) {
-    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || capacity_per_channel < 0 ||
-        (n_channels > 0 && (!n_groups || (capacity_per_channel > 0 && !out)))) return fail(FMX_E_INVALID, "bad argument");
-    for (int k = 0; k < n_channels; k++) n_groups[k] = 0;
-    if (n_channels == 0 || !h->rds_alloc) return FMX_OK;
-    const size_t C = (size_t)h->channels;
-    if (h->rds_grp_read.size() != C) h->rds_grp_read.assign(C, 0);
-    const RdsSyncChan *st = nullptr; const RdsGroupRec *grp = nullptr;
-    FMXCHK(rds_batch_fetch(h, first_channel, n_channels, &st, &grp));
-    for (int k = 0; k < n_channels; k++) {
-        int64_t &rd = h->rds_grp_read[(size_t)(first_channel + k)];
-        const RingTake t = ring_take(st[k].groups, rd, RDS_GROUP_RING, capacity_per_channel);   // (a reader that fell behind: the gap shows in `index`)
-        int32_t m = 0;
-        for (int64_t i = 0; i < t.count; i++) {
-            fmx_rds_group &r = out[(size_t)k * (size_t)capacity_per_channel + (size_t)m];
-            if (!rds_group_read(st[k], grp + (size_t)k * RDS_GROUP_RING, t.from + i, &r.end_bit, r.block)) continue;
-            r.index = t.from + i; m++;
-        }
-        rd = t.next();
-        n_groups[k] = m;
-    }
-    return FMX_OK;
-}
-
-// host-only entry (no device needed): run a fresh block synchroniser / group decoder over a bit array
-int fmx_rds_decode_bits(const uint8_t *bits, int32_t n_bits, fmx_rds_info *info) {
-    if ((!bits && n_bits > 0) || n_bits < 0 || !info) return fail(FMX_E_INVALID, "bad argument");
-    fmx::RdsGroupDecoderHost D;
-    for (int32_t i = 0; i < n_bits; i++) D.push_bit(bits[i] != 0);
-    *info = D.info();
-    return FMX_OK;
-}
-
-const char *fmx_rds_pty_name(int32_t pty_code, int32_t pty_locale) { return fmx::rds_pty_name(pty_code, pty_locale); }
-uint16_t fmx_rds_map_char(uint8_t alfabet, uint8_t character) { return fmx::rds_map_char(alfabet, character); }
-int32_t fmx_rds_prepare_text(const uint8_t *v, int32_t length, uint8_t *alfabet, uint16_t *out, int32_t capacity) {
-    if (!v || !out || length < 0 || capacity < 0) { (void)fail(FMX_E_INVALID, "bad argument"); return -1; }
-    return fmx::rds_prepare_text(v, length, alfabet, out, capacity);
-}
-
-int fmx_get_taps(fmx_handle h, int32_t channel, int32_t which, float *dst, int32_t capacity, int32_t *n) {
-    if (!h || !dst || !n || channel < 0 || channel >= h->channels) return fail(FMX_E_INVALID, "bad argument");
-    {   // the tap sets of the CURRENT settings; nothing is uploaded and no pending action is touched (introspection)
-        std::lock_guard<std::mutex> lk(h->mtx);
-        if (h->sets_dirty) { HIPCHK(hipSetDevice(h->cfg.device)); int rc = ensure_sets(h); if (rc) return rc; h->params_dirty = true; }
-    }
-    const float *src = nullptr; int cnt = 0;
-    std::vector<float> tmp;
-    switch (which) {
-    case 0: {   // front-end taps back in FIR order G[k], k = 12 d + off - r
-        const FrontSet &fs = h->h_front_sets[h->params[channel].front_set];
-        const float *t = &h->h_front_taps[(size_t)h->params[channel].front_set * A_TAPS_STRIDE];
-        int NT = 0;
-        tmp.assign(A_TAPS_STRIDE, 0.f);
-        for (int d = 0; d < fs.nd; d++) for (int r = 0; r < DECIM; r++) {
-            int k = 12 * d + fs.off - r;
-            if (k >= 0 && k < A_TAPS_STRIDE) { tmp[k] = t[(d + 1) * DECIM + r]; if (t[(d + 1) * DECIM + r] != 0.f) NT = std::max(NT, k + 1); }
-        }
-        src = tmp.data(); cnt = NT; break; }
-    case 1: src = h->h_pss_taps.data(); cnt = PSS_TAPS; break;
-    case 2: {
-        const AudioSet &as = h->h_audio_sets[h->params[channel].audio_set];
-        const float *t = &h->h_audio_taps[(size_t)h->params[channel].audio_set * C_TAPS_STRIDE];
-        tmp.resize(as.ntaps);
-        for (int k = 0; k < as.ntaps; k++) tmp[k] = t[as.ntaps - 1 - k];
-        src = tmp.data(); cnt = as.ntaps; break; }
-    case 3: src = h->h_rs_taps.data(); cnt = RS_TAPS; break;
-    case 4: {   // noise-squelch filters as the kernel holds them: [2][10][A1 A2 B1 B2], then the two gains (high-pass first)
-        const design::Iir hp = design::iir_chebyshev_lowhigh(true, 20, 70000 - 100, h->cfg.fmRate);
-        const design::Iir lp = design::iir_chebyshev_lowhigh(false, 20, 70000, h->cfg.fmRate);
-        tmp.assign(2 * NSQ_QUADS * 4 + 2, 0.f);
-        for (int f = 0; f < 2; f++) {
-            const design::Iir &F = f ? lp : hp;
-            for (int i = 0; i < NSQ_QUADS; i++) { tmp[(f * NSQ_QUADS + i) * 4] = F.q[i][1]; tmp[(f * NSQ_QUADS + i) * 4 + 1] = F.q[i][2]; tmp[(f * NSQ_QUADS + i) * 4 + 2] = F.q[i][4]; tmp[(f * NSQ_QUADS + i) * 4 + 3] = F.q[i][5]; }
-            tmp[2 * NSQ_QUADS * 4 + f] = F.gain;
-        }
-        src = tmp.data(); cnt = (int)tmp.size(); break; }
-    case 5: {   // RDS_1 constants as the kernels hold them: rdsFilter taps [21], Match kernel [43], sharpFilter [8][A1 A2 B1 B2], gain
-        tmp = design::lowpass(RDS1_FIR, 2 * 2400, 24000);
-        const std::vector<float> mk = design::rds1_match_kernel(24000);
-        tmp.insert(tmp.end(), mk.begin(), mk.end());
-        const design::Iir bp = design::iir_butterworth_bandpass(7, (int32_t)(1187.5 - 6), (int32_t)(1187.5 + 6), 24000);
-        for (int i = 0; i < bp.nq; i++) { tmp.push_back(bp.q[i][1]); tmp.push_back(bp.q[i][2]); tmp.push_back(bp.q[i][4]); tmp.push_back(bp.q[i][5]); }
-        tmp.push_back(bp.gain);
-        src = tmp.data(); cnt = (int)tmp.size(); break; }
-    default: return fail(FMX_E_INVALID, "unknown tap-set id");
-    }
-    if (cnt > capacity) return fail(FMX_E_TOO_LARGE, "capacity too small");
-    std::memcpy(dst, src, sizeof(float) * cnt);
-    *n = cnt;
-    return FMX_OK;
-}
-
-// diagnostics (include/fmx_debug.h): streaming bandwidth of this GPU in GB/s over `bytes` of float2 data, the mean of
-// `iters` launches timed with HIP events.  mode 0: copy (counts bytes read + written); mode 1: read 12, write 1 (stage A's shape).
-int fmx_debug_stream_bandwidth(int32_t device, int32_t mode, int64_t bytes, int32_t iters, double *gbps) {
-    if (!gbps || bytes < (1 << 20) || iters < 1 || mode < 0 || mode > 2) return fail(FMX_E_INVALID, "bad argument");
-    HIPCHK(hipSetDevice(device));
-    const size_t n16 = (size_t)bytes / 16 / (6 * 64) * (6 * 64);
-    fmx::f32x4_t *src = nullptr, *dst = nullptr;
-    HIPCHK(hipMalloc(&src, n16 * 16));
-    if (hipMalloc(&dst, mode == 0 ? n16 * 16 : n16 * 16 / 12 + 64) != hipSuccess) { (void)hipFree(src); return fail(FMX_E_HIP, "hipMalloc"); }
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipMemset(src, 0, n16 * 16));
-    const int grid = 256 * 8;
-    for (int it = -2; it < iters; it++) {
-        if (it == 0) HIPCHK(hipEventRecord(e0, 0));
-        if (mode == 0) hipLaunchKernelGGL(fmx::stream_probe_kernel<0>, dim3(grid), dim3(256), 0, 0, src, dst, n16);
-        else if (mode == 1) hipLaunchKernelGGL(fmx::stream_probe_kernel<1>, dim3(grid), dim3(256), 0, 0, src, dst, n16);
-        else hipLaunchKernelGGL(fmx::stream_probe_kernel<2>, dim3(grid), dim3(256), 0, 0, src, dst, n16);
-    }
-    HIPCHK(hipEventRecord(e1, 0));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    const double moved = mode == 0 ? 2.0 * n16 * 16 : (mode == 1 ? n16 * 16 * (1.0 + 1.0 / 12) : (double)n16 * 16);
-    *gbps = moved * iters / (ms * 1e-3) * 1e-9;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(src); (void)hipFree(dst);
-    return FMX_OK;
-}
-
-// diagnostics (include/fmx_debug.h): per-phase shader-cycle counters of front_kernel, summed over channels
-int fmx_debug_phase_cycles(fmx_handle h, int32_t enable, unsigned long long *out /*[DBG_SLOTS = 96], may be null*/) {
-    if (!h) return fail(FMX_E_INVALID, "null handle");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    HIPCHK(hipDeviceSynchronize());
-    const size_t nb = sizeof(unsigned long long) * DBG_SLOTS * (size_t)h->channels;
-    if (out && h->B.dbg) {
-        std::vector<unsigned long long> tmp(DBG_SLOTS * (size_t)h->channels);
-        HIPCHK(hipMemcpy(tmp.data(), h->B.dbg, nb, hipMemcpyDeviceToHost));
-        for (int k = 0; k < DBG_SLOTS; k++) { out[k] = 0; for (int c = 0; c < h->channels; c++) out[k] += tmp[(size_t)c * DBG_SLOTS + k]; }
-    }
-    if (enable && !h->B.dbg) FMXCHK(h->mem.alloc(h->B.dbg, DBG_SLOTS * (size_t)h->channels));
-    if (h->B.dbg) HIPCHK(hipMemset(h->B.dbg, 0, nb));
-    if (!enable) h->mem.release(h->B.dbg);
-    return FMX_OK;
-}
-
-int fmx_profile_enable(fmx_handle h, int32_t on) {
-    if (!h) return fail(FMX_E_INVALID, "null handle");
-    h->prof_on = on != 0;
-    return FMX_OK;
-}
-int fmx_profile_read(fmx_handle h, fmx_profile *out, int32_t reset) {
-    if (!h || !out) return fail(FMX_E_INVALID, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device));
-    int rc = prof_drain(h);
-    if (rc) return rc;
-    *out = h->prof_acc;
-    if (reset) std::memset(&h->prof_acc, 0, sizeof(h->prof_acc));
-    return FMX_OK;
-}
-
-}  // extern "C"
-
-// ---- stage W: wide-band ingest (fmx_wide.hip; DESIGN.md "Stage W") ------------------------------------------------------------------
-// One object = `streams` inputs at K * 2 304 000 S/s and `outputs` stations at 2 304 000 S/s.  Everything an output's oscillator needs
-// is integer arithmetic the host can do: the device holds, per output, the runs of samples mixed with one offset (WideOut) and the
-// folded taps; both are uploaded only when an offset changes.  The samples' history has two buffers, swapped per call, because the
-// workgroup that writes the new one runs beside the ones that read the old one.
-struct fmx_wideband_s {
-    int device = 0, streams = 0, K = 0, outputs = 0, T = 0;
-    int64_t max_block = 0, Rw = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    DevMem mem;
-    std::mutex mtx;                          // guards `want` (fmx_wideband_set_offset from any thread)
-    std::vector<int32_t> want, cur;          // the offsets asked for / in force
-    std::vector<WideOut> outs;               // host mirror
-    std::vector<float> h;                    // the low-pass, T taps
-    int64_t g0 = 0;                          // wide samples per stream so far
-    int parity = 0;                          // which history buffer the next call reads
-    bool outs_dirty = true;
-    int multi = 0;                           // outputs with more than one run inside a window
-    float2 *d_hist[2] = {nullptr, nullptr}, *d_taps = nullptr, *d_rot = nullptr, *d_out = nullptr;
-    float *d_h = nullptr;
-    WideOut *d_outs = nullptr;
-    int32_t *d_first = nullptr, *d_list = nullptr;
-    char *d_in = nullptr;                    // fmx_wideband_process_host_raw's staging buffers: d_in, d_out
-};
-
-namespace {
-
-int64_t pmod(int64_t a, int64_t m) { const int64_t r = a % m; return r < 0 ? r + m : r; }
-
-std::vector<float> wide_lowpass(int K) { return design::lowpass(16 * K + 1, 400000, K * W_RATE0); }
-
-// the folded taps of one output: g[i] = h[i] O((i f) mod Rw), the products formed in f64 and rounded once
-void wide_fold_taps(const fmx_wideband_s *w, int32_t f, float2 *g) {
-    const int64_t fm = pmod(f, w->Rw);
-    for (int i = 0; i < w->T; i++) {
-        const double ang = 2.0 * design::kPi * (double)((i * fm) % w->Rw) / (double)w->Rw;
-        g[i] = make_float2((float)((double)w->h[i] * std::cos(ang)), (float)((double)w->h[i] * std::sin(ang)));
-    }
-}
-
-int wide_check_config(const fmx_wideband_config *cfg) {
-    if (cfg->struct_size != (int32_t)sizeof(fmx_wideband_config)) return fail(FMX_E_INVALID, "fmx_wideband_config.struct_size mismatch");
-    if (cfg->factor < W_MIN_K || cfg->factor > W_MAX_K) return fail(FMX_E_INVALID, "factor must be in [2, 16]");
-    if (cfg->streams < 1 || cfg->streams > 65535) return fail(FMX_E_INVALID, "streams must be in [1, 65535]");
-    if (cfg->outputs < 1 || !cfg->stream_of_output) return fail(FMX_E_INVALID, "outputs must be >= 1, with a stream each");
-    if (cfg->max_block < cfg->factor || cfg->max_block % cfg->factor != 0) return fail(FMX_E_INVALID, "max_block must be a positive multiple of factor");
-    const int64_t lim = (int64_t)cfg->factor * W_RATE0 / 2 - 150000;
-    for (int m = 0; m < cfg->outputs; m++) {
-        if (cfg->stream_of_output[m] < 0 || cfg->stream_of_output[m] >= cfg->streams) return fail(FMX_E_INVALID, "stream_of_output entry out of range");
-        const int64_t f = cfg->offset_hz ? cfg->offset_hz[m] : 0;
-        if (f > lim || f < -lim) return fail(FMX_E_INVALID, "offset_hz: |f| must be <= factor * 1152000 - 150000");
-    }
-    return FMX_OK;
-}
-
-int wide_init(fmx_wideband w, const fmx_wideband_config *cfg) {
-    w->device = cfg->device; w->streams = cfg->streams; w->K = cfg->factor; w->outputs = cfg->outputs;
-    w->T = 16 * w->K + 1; w->max_block = cfg->max_block; w->Rw = (int64_t)w->K * W_RATE0;
-    w->h = wide_lowpass(w->K);
-    w->cur.assign((size_t)w->outputs, 0);
-    for (int m = 0; m < w->outputs; m++) w->cur[m] = cfg->offset_hz ? cfg->offset_hz[m] : 0;
-    w->want = w->cur;
-    w->outs.assign((size_t)w->outputs, WideOut{});
-    std::vector<int32_t> first((size_t)w->streams + 1, 0), list((size_t)w->outputs);
-    for (int m = 0; m < w->outputs; m++) first[(size_t)cfg->stream_of_output[m] + 1]++;
-    for (int s = 0; s < w->streams; s++) first[s + 1] += first[s];
-    std::vector<int32_t> fill(first.begin(), first.end() - 1);
-    std::vector<float2> taps((size_t)w->outputs * w->T);
-    for (int m = 0; m < w->outputs; m++) {
-        WideOut &o = w->outs[m];
-        o.stream = cfg->stream_of_output[m]; o.nseg = 1;
-        o.seg[0] = WideSeg{0, 0, (int32_t)pmod(w->cur[m], w->Rw)};      // P starts at 0
-        list[(size_t)fill[o.stream]++] = m;
-        wide_fold_taps(w, w->cur[m], taps.data() + (size_t)m * w->T);
-    }
-    std::vector<float2> rot((size_t)W_RATE0);                            // the oscillator table at the narrow rate (oscillator.cpp:26-35)
-    for (int i = 0; i < W_RATE0; i++) rot[i] = make_float2((float)std::cos(2.0 * design::kPi * i / W_RATE0), (float)std::sin(2.0 * design::kPi * i / W_RATE0));
-    HIPCHK(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&w->ev_out, hipEventDisableTiming));
-    DevMem &M = w->mem;
-    FMXCHK(M.alloc(w->d_hist[0], (size_t)w->streams * W_HIST, true));    // samples before the first call are zero
-    FMXCHK(M.alloc(w->d_hist[1], (size_t)w->streams * W_HIST, true));
-    FMXCHK(M.upload(w->d_taps, taps));
-    FMXCHK(M.upload(w->d_h, w->h));
-    FMXCHK(M.upload(w->d_rot, rot));
-    FMXCHK(M.upload(w->d_first, first));
-    FMXCHK(M.upload(w->d_list, list));
-    FMXCHK(M.alloc(w->d_outs, (size_t)w->outputs));
-    return FMX_OK;
-}
-
-// the head of a call: offsets that changed since the last one begin a new run at this call's first sample; runs that have left every window go
-int wide_flush(fmx_wideband w, hipStream_t s) {
-    std::vector<int32_t> want;
-    { std::lock_guard<std::mutex> lk(w->mtx); want = w->want; }
-    const int64_t c = w->g0;
-    if (w->multi > 0) {
-        w->multi = 0;
-        for (auto &o : w->outs) {
-            if (o.nseg <= 1) continue;
-            while (o.nseg > 1 && o.seg[o.nseg - 2].nbase <= c - (w->T - 1)) { o.nseg--; w->outs_dirty = true; }
-            if (o.nseg > 1) w->multi++;
-        }
-    }
-    std::vector<float2> g((size_t)w->T);
-    for (int m = 0; m < w->outputs; m++) {
-        if (want[m] == w->cur[m]) continue;
-        WideOut &o = w->outs[m];
-        const int32_t fm = (int32_t)pmod(want[m], w->Rw);
-        if (o.seg[0].nbase == c) o.seg[0].f = fm;                        // no sample was mixed with the offset it replaces
-        else {
-            const WideSeg &z = o.seg[0];
-            const int64_t p = pmod((int64_t)z.pbase - pmod(c - z.nbase, w->Rw) * (int64_t)z.f, w->Rw);    // P [c - 1]: the phase is kept
-            if (o.nseg == 1) w->multi++;
-            if (o.nseg < W_MAX_SEG) o.nseg++;
-            for (int k = o.nseg - 1; k > 0; k--) o.seg[k] = o.seg[k - 1];
-            o.seg[0] = WideSeg{c, (int32_t)p, fm};
-        }
-        w->cur[m] = want[m];
-        wide_fold_taps(w, want[m], g.data());
-        HIPCHK(hipMemcpyAsync(w->d_taps + (size_t)m * w->T, g.data(), sizeof(float2) * g.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));                                 // (g is reused; an offset change is a rare event)
-        w->outs_dirty = true;
-    }
-    if (w->outs_dirty) {
-        HIPCHK(hipMemcpyAsync(w->d_outs, w->outs.data(), sizeof(WideOut) * w->outs.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));                                 // (the mirror may change at the next call's head)
-        w->outs_dirty = false;
-    }
-    return FMX_OK;
-}
-
-int wide_check_call(fmx_wideband w, int32_t fmt, float s16_den, int64_t wide_stride, int64_t n_wide, int64_t narrow_stride) {
-    if (const ParamCheck pc = check_iq_format(fmt, s16_den); pc.code) return fail(pc.code, pc.msg);
-    if (n_wide < 0 || n_wide % w->K != 0) return fail(FMX_E_INVALID, "n_wide must be a multiple of factor");
-    if (n_wide > w->max_block) return fail(FMX_E_TOO_LARGE, "n_wide > max_block");
-    if (wide_stride < n_wide) return fail(FMX_E_INVALID, "wide_stride < n_wide");
-    if (narrow_stride < n_wide / w->K) return fail(FMX_E_INVALID, "narrow_stride < n_wide / factor");
-    return FMX_OK;
-}
-
-int wide_run(fmx_wideband w, const void *d_wide, int32_t fmt, float s16_den, int64_t wide_stride, int64_t n_wide, float2 *d_narrow,
-             int64_t narrow_stride, hipStream_t s) {
-    if (n_wide == 0) return FMX_OK;
-    FMXCHK(wide_flush(w, s));
-    WideArgs A{};
-    A.src = d_wide; A.fmt = fmt; A.qs = fmt == 3 ? 1.0f / s16_den : 1.0f / 128.0f;
-    A.src_stride = wide_stride; A.n_wide = n_wide; A.n_out = n_wide / w->K; A.g0 = w->g0;
-    A.dst = d_narrow; A.dst_stride = narrow_stride;
-    A.hist_in = w->d_hist[w->parity]; A.hist_out = w->d_hist[w->parity ^ 1];
-    A.taps = w->d_taps; A.h = w->d_h; A.rot = w->d_rot; A.outs = w->d_outs; A.first = w->d_first; A.list = w->d_list;
-    g_launch_err = hipSuccess;
-    launch_wide(A, w->K, w->streams, s);
-    if (g_launch_err != hipSuccess) return fail(FMX_E_HIP, std::string("wide_kernel: ") + hipGetErrorString(g_launch_err));
-    w->g0 += n_wide; w->parity ^= 1;
-    return FMX_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int fmx_wideband_taps(int32_t factor, float *dst, int32_t capacity, int32_t *n) {
-    if (factor < W_MIN_K || factor > W_MAX_K) return fail(FMX_E_INVALID, "factor must be in [2, 16]");
-    if (!dst && capacity > 0) return fail(FMX_E_INVALID, "null argument");
-    const std::vector<float> h = wide_lowpass(factor);
-    if (n) *n = (int32_t)h.size();
-    if (capacity < (int32_t)h.size()) return fail(FMX_E_TOO_LARGE, "capacity < 16 * factor + 1");
-    std::copy(h.begin(), h.end(), dst);
-    return FMX_OK;
-}
-
-int fmx_wideband_create(const fmx_wideband_config *cfg, fmx_wideband *out) {
-    if (!cfg || !out) return fail(FMX_E_INVALID, "null argument");
-    FMXCHK(wide_check_config(cfg));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(FMX_E_NO_DEVICE, "no HIP device visible: libfmx has no CPU fallback");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(FMX_E_INVALID, "device ordinal out of range");
-    HIPCHK(hipSetDevice(cfg->device));
-    fmx_wideband w = new (std::nothrow) fmx_wideband_s();
-    if (!w) return fail(FMX_E_NOMEM, "out of host memory");
-    if (const int rc = wide_init(w, cfg)) { const std::string msg = g_err; (void)fmx_wideband_destroy(w); g_err = msg; return rc; }
-    *out = w;
-    return FMX_OK;
-}
-
-int fmx_wideband_destroy(fmx_wideband w) {
-    if (!w) return FMX_OK;
-    (void)hipSetDevice(w->device);
-    if (w->stream) (void)hipStreamSynchronize(w->stream);
-    for (hipEvent_t e : {w->ev_in, w->ev_out}) if (e) (void)hipEventDestroy(e);
-    if (w->stream) (void)hipStreamDestroy(w->stream);
-    w->mem.release_all();
-    delete w;
-    return FMX_OK;
-}
-
-int fmx_wideband_set_offset(fmx_wideband w, int32_t output, int32_t hz) {
-    if (!w) return fail(FMX_E_INVALID, "null handle");
-    if (output < 0 || output >= w->outputs) return fail(FMX_E_INVALID, "output out of range");
-    const int64_t lim = w->Rw / 2 - 150000;
-    if (hz > lim || hz < -lim) return fail(FMX_E_INVALID, "offset: |f| must be <= factor * 1152000 - 150000");
-    std::lock_guard<std::mutex> lk(w->mtx);
-    w->want[(size_t)output] = hz;
-    return FMX_OK;
-}
-
-int fmx_wideband_process_device_raw(fmx_wideband w, const void *d_wide, int32_t format, float s16_denominator, int64_t wide_stride, int64_t n_wide,
-                                    float *d_narrow, int64_t narrow_stride, int64_t *n_narrow, void *hip_stream) {
-    if (!w || !d_wide || !d_narrow) return fail(FMX_E_INVALID, "null argument");
-    FMXCHK(wide_check_call(w, format, s16_denominator, wide_stride, n_wide, narrow_stride));
-    HIPCHK(hipSetDevice(w->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : w->stream;
-    if (!hip_stream) {                          // as fmx_process_device: behind what HIP's default stream holds now ...
-        HIPCHK(hipEventRecord(w->ev_in, nullptr));
-        HIPCHK(hipStreamWaitEvent(w->stream, w->ev_in, 0));
-    }
-    FMXCHK(wide_run(w, d_wide, format, s16_denominator, wide_stride, n_wide, reinterpret_cast<float2 *>(d_narrow), narrow_stride, s));
-    if (!hip_stream) {                          // ... and the default stream behind this call, so that an fmx_process_device (.., NULL) that follows finds its input
-        HIPCHK(hipEventRecord(w->ev_out, w->stream));
-        HIPCHK(hipStreamWaitEvent(nullptr, w->ev_out, 0));
-    }
-    if (n_narrow) *n_narrow = n_wide / w->K;
-    return FMX_OK;
-}
-
-int fmx_wideband_process_host_raw(fmx_wideband w, const void *wide, int32_t format, float s16_denominator, int64_t wide_stride, int64_t n_wide,
-                                  float *narrow, int64_t narrow_stride, int64_t *n_narrow) {
-    if (!w || !wide || !narrow) return fail(FMX_E_INVALID, "null argument");
-    FMXCHK(wide_check_call(w, format, s16_denominator, wide_stride, n_wide, narrow_stride));
-    HIPCHK(hipSetDevice(w->device));
-    const int64_t cap = w->max_block / w->K;
-    if (!w->d_in) {
-        FMXCHK(w->mem.alloc(w->d_in, (size_t)w->streams * (size_t)w->max_block * 8));    // sized for the widest format
-        FMXCHK(w->mem.alloc(w->d_out, (size_t)w->outputs * (size_t)cap));
-    }
-    if (n_narrow) *n_narrow = n_wide / w->K;
-    if (n_wide == 0) return FMX_OK;
-    const size_t bps = (size_t)bytes_per_sample(format);
-    HIPCHK(hipMemcpy2DAsync(w->d_in, bps * w->max_block, wide, bps * wide_stride, bps * n_wide, w->streams, hipMemcpyHostToDevice, w->stream));
-    FMXCHK(wide_run(w, w->d_in, format, s16_denominator, w->max_block, n_wide, w->d_out, cap, w->stream));
-    HIPCHK(hipMemcpy2DAsync(narrow, sizeof(float2) * narrow_stride, w->d_out, sizeof(float2) * cap, sizeof(float2) * (n_wide / w->K), w->outputs,
-                            hipMemcpyDeviceToHost, w->stream));
-    HIPCHK(hipStreamSynchronize(w->stream));
     return FMX_OK;
 }
 

@@ -1,4 +1,4 @@
-// fmx_internal.h -- structures shared by the host side (fmx_api.hip) and the gfx950 kernels.
+// fmx_internal.h -- structures shared by the host side (fmx_host.h and the four files that include it) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,0 +1,378 @@
+// fmx_readout.hip -- the entry points of include/fmx.h that only read a handle: metaData, peak levels, scope taps, tap sets, the RDS bits, symbols, groups
+// and decoders, scan records, the PLL counters, the facts about the last call; and the host-only RDS helpers.  A per-channel read-out waits for the device,
+// asks its ring's producer for the count, and takes [from, from + count) out of one copy of the ring (read_ring); where each reader stands is in the
+// handle's Readers (fmx_host.h).  The two batch RDS read-outs wait for the handle's last call only and copy every channel's ring at once (rds_batch_fetch).
+#include "fmx_host.h"
+#include "fmx_design.h"
+
+#include <cmath>
+#include <cstring>
+
+namespace {
+
+// the head of a read-out: this handle's device, and everything enqueued on it done
+int device_idle(fmx_handle h) {
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipDeviceSynchronize());
+    return FMX_OK;
+}
+// ... followed by the state of the channels [c0, c1) / by a channel's RDS state
+int fetch_chan_states(fmx_handle h, int c0, int c1, ChanState *st) {
+    FMXCHK(device_idle(h));
+    HIPCHK(hipMemcpy(st, h->B.state + c0, sizeof(ChanState) * (size_t)(c1 - c0), hipMemcpyDeviceToHost));
+    return FMX_OK;
+}
+int fetch_rds_state(fmx_handle h, int channel, RdsState *st) {
+    FMXCHK(device_idle(h));
+    HIPCHK(hipMemcpy(st, h->R.state + channel, sizeof(RdsState), hipMemcpyDeviceToHost));
+    return FMX_OK;
+}
+
+// The items [t.from, t.from + t.count) of a channel's ring of `ring` entries at d_ring, oldest first: visit (k, item) for k = 0 .. t.count - 1, out of one
+// copy of the ring.  Nothing is copied when there is nothing to take.
+template <class T, class F> int read_ring(const T *d_ring, int ring, RingTake t, F &&visit) {
+    if (t.count <= 0) return FMX_OK;
+    std::vector<T> items((size_t)ring);
+    HIPCHK(hipMemcpy(items.data(), d_ring, sizeof(T) * (size_t)ring, hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < t.count; k++) visit(k, items[(size_t)ring_slot(t.from + k, ring)]);
+    return FMX_OK;
+}
+
+// fmx_pll_replays / fmx_pll_exact_segments: a counter of ChanState, of one channel or (channel < 0) summed over all
+template <class F> int64_t sum_chan_states(fmx_handle h, int32_t channel, F counter) {
+    if (!h || channel >= h->channels) return (int64_t)fail(FMX_E_INVALID, "bad argument");
+    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
+    std::vector<ChanState> st((size_t)(c1 - c0));
+    if (fetch_chan_states(h, c0, c1, st.data()) != FMX_OK) return (int64_t)fail(FMX_E_HIP, "device error");
+    int64_t n = 0;
+    for (auto &s : st) n += counter(s);
+    return n;
+}
+
+// One read-out of the device for the channels first .. first + n - 1: their synchroniser states and group rings, behind the handle's last call, in two
+// copies into the handle's pinned buffer.
+int rds_batch_fetch(fmx_handle h, int first, int n, const RdsSyncChan **st, const RdsGroupRec **grp) {
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t C = (size_t)h->channels;
+    if (!h->rd_stream) HIPCHK(hipStreamCreateWithFlags(&h->rd_stream, hipStreamNonBlocking));
+    if (!h->rds_stage) FMXCHK(h->rds_mem.alloc_pinned(h->rds_stage, C * (sizeof(RdsSyncChan) + sizeof(RdsGroupRec) * RDS_GROUP_RING)));
+    RdsGroupRec *g = reinterpret_cast<RdsGroupRec *>(h->rds_stage);                        // (the 16-byte records first: the buffer's alignment is theirs)
+    RdsSyncChan *c = reinterpret_cast<RdsSyncChan *>(h->rds_stage + C * sizeof(RdsGroupRec) * RDS_GROUP_RING);
+    if (h->ev_call_set) HIPCHK(hipStreamWaitEvent(h->rd_stream, h->ev_call, 0));
+    HIPCHK(hipMemcpyAsync(c, h->R.sync + first, sizeof(RdsSyncChan) * (size_t)n, hipMemcpyDeviceToHost, h->rd_stream));
+    HIPCHK(hipMemcpyAsync(g, h->R.groups + (size_t)first * RDS_GROUP_RING, sizeof(RdsGroupRec) * RDS_GROUP_RING * (size_t)n, hipMemcpyDeviceToHost, h->rd_stream));
+    HIPCHK(hipStreamSynchronize(h->rd_stream));
+    *st = c; *grp = g;
+    return FMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmx_get_meta(fmx_handle h, int32_t channel, fmx_meta *m) {
+    if (!h || !m || channel < 0 || channel >= h->channels) return fail(FMX_E_INVALID, "bad argument");
+    ChanState st;
+    FMXCHK(fetch_chan_states(h, channel, channel + 1, &st));
+    m->DcValRf = st.meta_dc_rf; m->DcValIf = st.meta_dc_if; m->PssPhaseShiftDegree = st.meta_pss_deg;
+    m->PssPhaseChange = st.meta_pss_change; m->PssState = st.meta_pss_state;
+    m->PilotPllLockStrength = st.meta_lock_strength; m->PilotPllLocked = st.meta_locked;
+    m->live_pilot_locked = (h->params[channel].fm_mode != 2) ? st.pil_locked : 0;
+    m->live_lock_strength = (h->params[channel].fm_mode != 2) ? st.pil_lock : 0.f;
+    m->live_dc_if = st.fm_afc; m->squelch_active = (h->params[channel].squelch_mode != 0) ? st.sq_suppress : 0;
+    m->fm_samples = h->g_total / h->decim; m->pcm_frames = conv2_out(h, 48 * ((h->g_total / h->decim) / 192));
+    m->live_rf_dc_re = st.dc_re; m->live_rf_dc_im = st.dc_im;
+    return FMX_OK;
+}
+
+int fmx_get_peaks(fmx_handle h, int32_t channel, float *lr_db, int32_t capacity, int32_t *n_events) {
+    if (!h || !n_events || channel < 0 || channel >= h->channels || capacity < 0 || (capacity > 0 && !lr_db))
+        return fail(FMX_E_INVALID, "bad argument");
+    if (!h->taps_kept) return fail(FMX_E_UNSUPPORTED, "this handle does not run the peak-level meter: a display feed, automatic only up to 64 channels -- fmx_set_param (h, -1, FMX_P_SCOPE_TAPS, 1) and one call switch it on");
+    ChanState st;
+    FMXCHK(fetch_chan_states(h, channel, channel + 1, &st));
+    std::lock_guard<std::mutex> lk(h->mtx);
+    ChanUser &u = h->user[channel];
+    const RingTake t = ring_take(st.pk_events, h->rd.peaks[channel], PK_RING, capacity);      // (a caller that fell behind: the oldest windows are gone)
+    FMXCHK(read_ring(h->B.pk_ring + (size_t)channel * PK_RING, PK_RING, t, [&](int64_t k, float2 pk) {
+        // fm-processor.cpp:785-794: float log10 (std::log10 of a float), -40 dB for silence, then the display delay line
+        const float ldb = pk.x > 0.0f ? 20.0f * std::log10(pk.x) : -40.0f;
+        const float rdb = pk.y > 0.0f ? 20.0f * std::log10(pk.y) : -40.0f;
+        u.delay[u.delay_idx] = make_float2(ldb, rdb);
+        u.delay_idx = (u.delay_idx + 1) % (uint32_t)u.delay.size();
+        lr_db[2 * k] = u.delay[u.delay_idx].x; lr_db[2 * k + 1] = u.delay[u.delay_idx].y;
+    }));
+    h->rd.peaks[channel] = (int32_t)t.next();
+    *n_events = (int32_t)t.count;
+    return FMX_OK;
+}
+
+int fmx_get_tap(fmx_handle h, int32_t channel, int32_t tap, float *dst, int64_t n) {
+    if (!h || !dst || channel < 0 || channel >= h->channels || n < 0) return fail(FMX_E_INVALID, "bad argument");
+    const int64_t J1 = h->g_total / h->decim;
+    if (tap != 4 && (n > J1 || n > (h->last_J1 - h->last_J0))) return fail(FMX_E_INVALID, "n exceeds the samples produced by the last call");
+    FMXCHK(device_idle(h));
+    const char *base; int64_t cap, elem, delay = 0;
+    switch (tap) {
+    case FMX_TAP_FM_IQ: base = (const char *)(h->B.zring + (size_t)channel * h->ring); cap = h->ring; elem = sizeof(float2);
+        delay = h->h_front_sets[h->params[channel].front_set].delay_fm; break;
+    case FMX_TAP_DEMOD: case FMX_TAP_LR_RAW: case FMX_TAP_PILOT_PHASE: {
+        // these taps are read back from the last call's work arrays (channel-major rows of the call), rows [nj - n, nj)
+        const int64_t nj = h->last_J1 - h->last_J0, r0 = nj - n;
+        if (!h->taps_kept) return fail(FMX_E_UNSUPPORTED, "this handle does not keep the demodulator / LR / pilot-phase scope taps: display feeds, automatic only up to 64 channels -- fmx_set_param (h, -1, FMX_P_SCOPE_TAPS, 1) and one call switch them on");
+        if (n == 0) return FMX_OK;
+        {                            // this call's rows are contiguous per channel
+            const size_t off = (size_t)channel * (size_t)h->work_nj + (size_t)r0;
+            std::vector<float> a((size_t)n), b;
+            HIPCHK(hipMemcpy(a.data(), (tap == FMX_TAP_PILOT_PHASE ? h->B.w_cur : h->B.w_dem) + off, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+            if (tap == FMX_TAP_LR_RAW) {
+                b.resize((size_t)n);
+                HIPCHK(hipMemcpy(b.data(), h->B.w_diff + off, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+                for (int64_t i = 0; i < n; i++) { dst[2 * i] = a[(size_t)i]; dst[2 * i + 1] = b[(size_t)i]; }
+            } else std::memcpy(dst, a.data(), sizeof(float) * (size_t)n);
+        }
+        return FMX_OK; }
+    case FMX_TAP_PRE_RESAMPLER: base = (const char *)((h->ola_mode && h->d2ring ? h->d2ring : h->B.dring) + (size_t)channel * h->dring); cap = h->dring; elem = sizeof(float2); break;
+    case 4: {   // FMX_TAP_RDS_IQ: complex @24 kS/s after rdsDecimator (:553): the last n outputs of the last call
+        if (!h->rds_alloc) return fail(FMX_E_INVALID, "RDS is off");
+        const int64_t lm0 = h->last_m0[(size_t)channel], lm1 = h->last_m1[(size_t)channel];      // (the channel's own count: fmx_last_rds_samples_of)
+        if (n > lm1 - lm0) return fail(FMX_E_INVALID, "n exceeds the RDS samples the channel produced in the last call");
+        char *o = (char *)dst;
+        for (int64_t m = lm1 - n; m < lm1;) {
+            const int64_t pos = m & (RDS24_RING - 1);
+            const int64_t run = std::min<int64_t>(RDS24_RING - pos, lm1 - m);
+            HIPCHK(hipMemcpy(o, (const char *)(h->R.rds24 + (size_t)channel * RDS24_RING) + pos * sizeof(float2), (size_t)run * sizeof(float2), hipMemcpyDeviceToHost));
+            o += run * sizeof(float2); m += run;
+        }
+        return FMX_OK; }
+    default: return fail(FMX_E_INVALID, "unknown tap id");
+    }
+    // samples j in [J1-n, J1) live at ring index (j - delay) & (cap-1); before the stream start they are 0
+    char *out = (char *)dst;
+    for (int64_t j = J1 - n; j < J1;) {
+        const int64_t jv = j - delay;
+        if (jv < 0) { std::memset(out, 0, elem); out += elem; j++; continue; }
+        const int64_t pos = jv & (cap - 1);
+        const int64_t run = std::min<int64_t>(cap - pos, J1 - j);
+        HIPCHK(hipMemcpy(out, base + pos * elem, (size_t)(run * elem), hipMemcpyDeviceToHost));
+        out += run * elem; j += run;
+    }
+    return FMX_OK;
+}
+
+int fmx_rds_bits(fmx_handle h, int32_t channel, uint8_t *bits, int32_t capacity, int32_t *n_bits) {
+    if (!h || channel < 0 || channel >= h->channels || !n_bits || capacity < 0) return fail(FMX_E_INVALID, "bad argument");
+    *n_bits = 0;
+    if (!h->rds_alloc) return FMX_OK;
+    RdsState st;
+    FMXCHK(fetch_rds_state(h, channel, &st));
+    const RingTake t = ring_take(st.nbits, h->rd.bits[channel], RDS_BITS_CAP, bits ? capacity : 0);   // (ring overrun: oldest bits lost)
+    FMXCHK(read_ring(h->R.bits + (size_t)channel * RDS_BITS_CAP, RDS_BITS_CAP, t, [&](int64_t k, uint8_t b) { bits[k] = b; }));
+    h->rd.bits[channel] = (int32_t)t.next();
+    *n_bits = (int32_t)t.count;
+    return FMX_OK;
+}
+
+int fmx_rds_symbols(fmx_handle h, int32_t channel, float *iq, int32_t capacity, int32_t *n_symbols) {
+    if (!h || channel < 0 || channel >= h->channels || !n_symbols || capacity < 0) return fail(FMX_E_INVALID, "bad argument");
+    *n_symbols = 0;
+    if (!h->rds_alloc) return FMX_OK;
+    RdsState st;
+    FMXCHK(fetch_rds_state(h, channel, &st));
+    int32_t &rd = h->rd.symbols[(size_t)channel];
+    if (st.nbits < rd) rd = 0;                  // (the count went backwards: start over)
+    const RingTake t = ring_take(st.nbits, rd, RDS_SYM_CAP, iq ? capacity : 0);        // (ring overrun: oldest symbols lost)
+    FMXCHK(read_ring(h->R.sym + (size_t)channel * RDS_SYM_CAP, RDS_SYM_CAP, t, [&](int64_t k, float2 v) { iq[2 * k] = v.x; iq[2 * k + 1] = v.y; }));
+    *n_symbols = (int32_t)t.count;
+    rd = (int32_t)t.next();
+    return FMX_OK;
+}
+
+int64_t fmx_last_fm_samples(fmx_handle h) { return h ? (int64_t)(h->last_J1 - h->last_J0) : 0; }
+int fmx_scan_results(fmx_handle h, int32_t channel, fmx_scan_result *out, int32_t capacity, int32_t *n_results) {
+    if (!h || !n_results || channel < 0 || channel >= h->channels || capacity < 0 || (capacity > 0 && !out)) return fail(FMX_E_INVALID, "bad argument");
+    *n_results = 0;
+    if (!h->scan_alloc) return FMX_OK;
+    FMXCHK(device_idle(h));
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const size_t c = (size_t)channel;
+    const RingTake t = ring_take(h->scan_blocks[c], h->rd.scan[c], scan::RING, capacity);      // (a caller that fell behind: the oldest records are gone)
+    FMXCHK(read_ring(h->d_scan_rec + c * scan::RING, scan::RING, t, [&](int64_t k, float2 rec) {
+        const int64_t b = t.from + k;
+        const size_t slot = c * scan::RING + (size_t)ring_slot(b, scan::RING);
+        fmx_scan_result &r = out[k];
+        r.block = b; r.end_sample = h->scan_end[slot];
+        r.signal_db = rec.x; r.noise_db = rec.y;
+        r.found = (r.signal_db - r.noise_db > (float)h->scan_rec_thr[slot]) ? 1 : 0;   // fm-processor.cpp:489 (float against int16_t)
+        r.reserved = 0;
+    }));
+    h->rd.scan[c] = t.next();
+    *n_results = (int32_t)t.count;
+    return FMX_OK;
+}
+
+int64_t fmx_pll_replays(fmx_handle h, int32_t channel) { return sum_chan_states(h, channel, [](const ChanState &s) { return s.pll_replays; }); }
+int64_t fmx_pll_exact_segments(fmx_handle h, int32_t channel) { return sum_chan_states(h, channel, [](const ChanState &s) { return s.pll_exact_segs; }); }
+int32_t fmx_last_front_kernel(fmx_handle h) { return h ? h->last_front_kernel : 0; }
+int32_t fmx_last_call_pieces(fmx_handle h) { return h ? h->last_pieces : 0; }
+int32_t fmx_last_second_group(fmx_handle h) { return h ? h->last_second_group : 0; }
+int64_t fmx_last_rds_samples_of(fmx_handle h, int32_t channel) {
+    if (!h || !h->rds_alloc || channel < 0 || channel >= h->channels) return 0;
+    return h->last_m1[(size_t)channel] - h->last_m0[(size_t)channel];
+}
+int64_t fmx_last_rds_samples(fmx_handle h) { return fmx_last_rds_samples_of(h, 0); }
+
+int fmx_rds_decode(fmx_handle h, int32_t channel, fmx_rds_info *info) {
+    if (!h || channel < 0 || channel >= h->channels || !info) return fail(FMX_E_INVALID, "bad argument");
+    if ((int)h->rd.dec.size() != h->channels) h->rd.dec.assign((size_t)h->channels, fmx::RdsGroupDecoderHost());
+    fmx::RdsGroupDecoderHost &D = h->rd.dec[(size_t)channel];
+    bool do_reset = false;
+    {
+        std::lock_guard<std::mutex> lk(h->mtx);
+        if (h->rd.reset_dec[(size_t)channel]) { h->rd.reset_dec[(size_t)channel] = 0; do_reset = true; }
+    }
+    if (h->rds_alloc) {
+        RdsState st;
+        FMXCHK(fetch_rds_state(h, channel, &st));
+        int32_t &rd = h->rd.dec_bits[(size_t)channel];
+        if (st.nbits < rd) { rd = 0; D.reset_all(); }      // (the count went backwards: start over)
+        if (do_reset) {
+            // rdsGroupDecoder::reset: PI / PTY / labels back to unknown.  The reference resets between two blocks of samples;
+            // here the decoder runs behind the slicer, so the bits still pending belong to the time before the reset (the
+            // old station after a retune) and are dropped.
+            D.reset_groups(); rd = st.nbits;
+        }
+        const RingTake t = ring_take(st.nbits, rd, RDS_BITS_CAP, RDS_BITS_CAP);      // (ring overrun: oldest bits lost)
+        FMXCHK(read_ring(h->R.bits + (size_t)channel * RDS_BITS_CAP, RDS_BITS_CAP, t, [&](int64_t, uint8_t b) { D.push_bit(b != 0); }));
+        rd = (int32_t)t.next();
+    }
+    else if (do_reset) D.reset_groups();
+    *info = D.info();
+    return FMX_OK;
+}
+
+int fmx_rds_decode_all(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rds_info *infos) {
+    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || (n_channels > 0 && !infos)) return fail(FMX_E_INVALID, "bad argument");
+    if (n_channels == 0) return FMX_OK;
+    const size_t C = (size_t)h->channels;
+    if (h->rd.dec_all.size() != C) h->rd.dec_all.assign(C, fmx::RdsGroupDecoderHost());
+    std::vector<uint8_t> do_reset((size_t)n_channels, 0);
+    {
+        std::lock_guard<std::mutex> lk(h->mtx);
+        for (int k = 0; k < n_channels; k++) { do_reset[(size_t)k] = h->rd.reset_dec_all[(size_t)(first_channel + k)]; h->rd.reset_dec_all[(size_t)(first_channel + k)] = 0; }
+    }
+    const RdsSyncChan *st = nullptr; const RdsGroupRec *grp = nullptr;
+    if (h->rds_alloc) FMXCHK(rds_batch_fetch(h, first_channel, n_channels, &st, &grp));
+    for (int k = 0; k < n_channels; k++) {
+        const size_t c = (size_t)(first_channel + k);
+        fmx::RdsGroupDecoderHost &D = h->rd.dec_all[c];
+        if (!h->rds_alloc) { if (do_reset[(size_t)k]) D.reset_groups(); infos[k] = D.info(); continue; }
+        const RdsSyncChan &S = st[k];
+        int64_t &rd = h->rd.dec_groups[c];
+        // rdsGroupDecoder::reset: PI / PTY / labels back to unknown; the groups completed before this read-out belong to the time before the reset
+        // and are dropped.  The synchroniser runs on (fmx.h: where this differs from fmx_rds_decode)
+        if (do_reset[(size_t)k]) { D.reset_groups(); rd = S.groups; }
+        const RingTake t = ring_take(S.groups, rd, RDS_GROUP_RING, RDS_GROUP_RING);      // (a reader that fell behind: the oldest groups are lost)
+        for (int64_t i = 0; i < t.count; i++) {
+            int64_t end_bit; uint16_t b[4];
+            if (rds_group_read(S, grp + (size_t)k * RDS_GROUP_RING, t.from + i, &end_bit, b)) D.push_group(b);
+        }
+        rd = t.next();
+        D.set_sync_status(fmx::RdsSyncStatus{S.s.synced, S.s.n_crc_err, S.s.n_sync_err, S.s.ber_num, S.s.ber_den});
+        infos[k] = D.info();
+    }
+    return FMX_OK;
+}
+
+int fmx_rds_groups(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rds_group *out, int32_t capacity_per_channel, int32_t *n_groups) {
+    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || capacity_per_channel < 0 ||
+        (n_channels > 0 && (!n_groups || (capacity_per_channel > 0 && !out)))) return fail(FMX_E_INVALID, "bad argument");
+    for (int k = 0; k < n_channels; k++) n_groups[k] = 0;
+    if (n_channels == 0 || !h->rds_alloc) return FMX_OK;
+    const RdsSyncChan *st = nullptr; const RdsGroupRec *grp = nullptr;
+    FMXCHK(rds_batch_fetch(h, first_channel, n_channels, &st, &grp));
+    for (int k = 0; k < n_channels; k++) {
+        int64_t &rd = h->rd.groups[(size_t)(first_channel + k)];
+        const RingTake t = ring_take(st[k].groups, rd, RDS_GROUP_RING, capacity_per_channel);   // (a reader that fell behind: the gap shows in `index`)
+        int32_t m = 0;
+        for (int64_t i = 0; i < t.count; i++) {
+            fmx_rds_group &r = out[(size_t)k * (size_t)capacity_per_channel + (size_t)m];
+            if (!rds_group_read(st[k], grp + (size_t)k * RDS_GROUP_RING, t.from + i, &r.end_bit, r.block)) continue;
+            r.index = t.from + i; m++;
+        }
+        rd = t.next();
+        n_groups[k] = m;
+    }
+    return FMX_OK;
+}
+
+// host-only entry (no device needed): run a fresh block synchroniser / group decoder over a bit array
+int fmx_rds_decode_bits(const uint8_t *bits, int32_t n_bits, fmx_rds_info *info) {
+    if ((!bits && n_bits > 0) || n_bits < 0 || !info) return fail(FMX_E_INVALID, "bad argument");
+    fmx::RdsGroupDecoderHost D;
+    for (int32_t i = 0; i < n_bits; i++) D.push_bit(bits[i] != 0);
+    *info = D.info();
+    return FMX_OK;
+}
+
+const char *fmx_rds_pty_name(int32_t pty_code, int32_t pty_locale) { return fmx::rds_pty_name(pty_code, pty_locale); }
+uint16_t fmx_rds_map_char(uint8_t alfabet, uint8_t character) { return fmx::rds_map_char(alfabet, character); }
+int32_t fmx_rds_prepare_text(const uint8_t *v, int32_t length, uint8_t *alfabet, uint16_t *out, int32_t capacity) {
+    if (!v || !out || length < 0 || capacity < 0) { (void)fail(FMX_E_INVALID, "bad argument"); return -1; }
+    return fmx::rds_prepare_text(v, length, alfabet, out, capacity);
+}
+
+int fmx_get_taps(fmx_handle h, int32_t channel, int32_t which, float *dst, int32_t capacity, int32_t *n) {
+    if (!h || !dst || !n || channel < 0 || channel >= h->channels) return fail(FMX_E_INVALID, "bad argument");
+    {   // the tap sets of the CURRENT settings; nothing is uploaded and no pending action is touched (introspection)
+        std::lock_guard<std::mutex> lk(h->mtx);
+        if (h->sets_dirty) { HIPCHK(hipSetDevice(h->cfg.device)); int rc = ensure_sets(h); if (rc) return rc; h->params_dirty = true; }
+    }
+    const float *src = nullptr; int cnt = 0;
+    std::vector<float> tmp;
+    switch (which) {
+    case 0: {   // front-end taps back in FIR order G[k], k = 12 d + off - r
+        const FrontSet &fs = h->h_front_sets[h->params[channel].front_set];
+        const float *t = &h->h_front_taps[(size_t)h->params[channel].front_set * A_TAPS_STRIDE];
+        int NT = 0;
+        tmp.assign(A_TAPS_STRIDE, 0.f);
+        for (int d = 0; d < fs.nd; d++) for (int r = 0; r < DECIM; r++) {
+            int k = 12 * d + fs.off - r;
+            if (k >= 0 && k < A_TAPS_STRIDE) { tmp[k] = t[(d + 1) * DECIM + r]; if (t[(d + 1) * DECIM + r] != 0.f) NT = std::max(NT, k + 1); }
+        }
+        src = tmp.data(); cnt = NT; break; }
+    case 1: src = h->h_pss_taps.data(); cnt = PSS_TAPS; break;
+    case 2: {
+        const AudioSet &as = h->h_audio_sets[h->params[channel].audio_set];
+        const float *t = &h->h_audio_taps[(size_t)h->params[channel].audio_set * C_TAPS_STRIDE];
+        tmp.resize(as.ntaps);
+        for (int k = 0; k < as.ntaps; k++) tmp[k] = t[as.ntaps - 1 - k];
+        src = tmp.data(); cnt = as.ntaps; break; }
+    case 3: src = h->h_rs_taps.data(); cnt = RS_TAPS; break;
+    case 4: {   // noise-squelch filters as the kernel holds them: [2][10][A1 A2 B1 B2], then the two gains (high-pass first)
+        const design::Iir hp = design::iir_chebyshev_lowhigh(true, 20, 70000 - 100, h->cfg.fmRate);
+        const design::Iir lp = design::iir_chebyshev_lowhigh(false, 20, 70000, h->cfg.fmRate);
+        tmp.assign(2 * NSQ_QUADS * 4 + 2, 0.f);
+        for (int f = 0; f < 2; f++) {
+            const design::Iir &F = f ? lp : hp;
+            for (int i = 0; i < NSQ_QUADS; i++) { tmp[(f * NSQ_QUADS + i) * 4] = F.q[i][1]; tmp[(f * NSQ_QUADS + i) * 4 + 1] = F.q[i][2]; tmp[(f * NSQ_QUADS + i) * 4 + 2] = F.q[i][4]; tmp[(f * NSQ_QUADS + i) * 4 + 3] = F.q[i][5]; }
+            tmp[2 * NSQ_QUADS * 4 + f] = F.gain;
+        }
+        src = tmp.data(); cnt = (int)tmp.size(); break; }
+    case 5: {   // RDS_1 constants as the kernels hold them: rdsFilter taps [21], Match kernel [43], sharpFilter [8][A1 A2 B1 B2], gain
+        tmp = design::lowpass(RDS1_FIR, 2 * 2400, 24000);
+        const std::vector<float> mk = design::rds1_match_kernel(24000);
+        tmp.insert(tmp.end(), mk.begin(), mk.end());
+        const design::Iir bp = design::iir_butterworth_bandpass(7, (int32_t)(1187.5 - 6), (int32_t)(1187.5 + 6), 24000);
+        for (int i = 0; i < bp.nq; i++) { tmp.push_back(bp.q[i][1]); tmp.push_back(bp.q[i][2]); tmp.push_back(bp.q[i][4]); tmp.push_back(bp.q[i][5]); }
+        tmp.push_back(bp.gain);
+        src = tmp.data(); cnt = (int)tmp.size(); break; }
+    default: return fail(FMX_E_INVALID, "unknown tap-set id");
+    }
+    if (cnt > capacity) return fail(FMX_E_TOO_LARGE, "capacity too small");
+    std::memcpy(dst, src, sizeof(float) * cnt);
+    *n = cnt;
+    return FMX_OK;
+}
+
+}  // extern "C"

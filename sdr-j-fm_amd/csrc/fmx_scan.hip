@@ -3,7 +3,7 @@
 // noise_db); the samples left over become the new carry.  And the mute of the scanning channels' PCM behind stage C.
 //
 // One workgroup per scanning channel, four waves, one block per wave at a time.  A channel's samples of the call are read from stage A's
-// fm-rate ring as every reader of it does: fm sample j at ring position j - delay_fm, zero while j < delay_fm (fmx_api.hip fmx_get_tap).
+// fm-rate ring as every reader of it does: fm sample j at ring position j - delay_fm, zero while j < delay_fm (fmx_readout.hip fmx_get_tap).
 // The carry is read by the wave of block 0 only and rewritten behind a barrier.
 #include "fmx_internal.h"
 #include "fmx_scan.h"

@@ -1,0 +1,257 @@
+// fmx_wide_api.hip -- the host half of stage W, wide-band ingest (fmx_wideband_* of include/fmx.h; the kernel is in fmx_wide.hip).  It shares nothing with
+// fmx_handle but the error, the checking macros and the memory owner of fmx_host.h.
+#include "fmx_host.h"
+#include "fmx_design.h"
+
+#include <cmath>
+
+// ---- stage W: wide-band ingest (fmx_wide.hip; DESIGN.md "Stage W") ------------------------------------------------------------------
+// One object = `streams` inputs at K * 2 304 000 S/s and `outputs` stations at 2 304 000 S/s.  Everything an output's oscillator needs
+// is integer arithmetic the host can do: the device holds, per output, the runs of samples mixed with one offset (WideOut) and the
+// folded taps; both are uploaded only when an offset changes.  The samples' history has two buffers, swapped per call, because the
+// workgroup that writes the new one runs beside the ones that read the old one.
+struct fmx_wideband_s {
+    int device = 0, streams = 0, K = 0, outputs = 0, T = 0;
+    int64_t max_block = 0, Rw = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    DevMem mem;
+    std::mutex mtx;                          // guards `want` (fmx_wideband_set_offset from any thread)
+    std::vector<int32_t> want, cur;          // the offsets asked for / in force
+    std::vector<WideOut> outs;               // host mirror
+    std::vector<float> h;                    // the low-pass, T taps
+    int64_t g0 = 0;                          // wide samples per stream so far
+    int parity = 0;                          // which history buffer the next call reads
+    bool outs_dirty = true;
+    int multi = 0;                           // outputs with more than one run inside a window
+    float2 *d_hist[2] = {nullptr, nullptr}, *d_taps = nullptr, *d_rot = nullptr, *d_out = nullptr;
+    float *d_h = nullptr;
+    WideOut *d_outs = nullptr;
+    int32_t *d_first = nullptr, *d_list = nullptr;
+    char *d_in = nullptr;                    // fmx_wideband_process_host_raw's staging buffers: d_in, d_out
+};
+
+namespace {
+
+int64_t pmod(int64_t a, int64_t m) { const int64_t r = a % m; return r < 0 ? r + m : r; }
+
+std::vector<float> wide_lowpass(int K) { return design::lowpass(16 * K + 1, 400000, K * W_RATE0); }
+
+// the folded taps of one output: g[i] = h[i] O((i f) mod Rw), the products formed in f64 and rounded once
+void wide_fold_taps(const fmx_wideband_s *w, int32_t f, float2 *g) {
+    const int64_t fm = pmod(f, w->Rw);
+    for (int i = 0; i < w->T; i++) {
+        const double ang = 2.0 * design::kPi * (double)((i * fm) % w->Rw) / (double)w->Rw;
+        g[i] = make_float2((float)((double)w->h[i] * std::cos(ang)), (float)((double)w->h[i] * std::sin(ang)));
+    }
+}
+
+int wide_check_config(const fmx_wideband_config *cfg) {
+    if (cfg->struct_size != (int32_t)sizeof(fmx_wideband_config)) return fail(FMX_E_INVALID, "fmx_wideband_config.struct_size mismatch");
+    if (cfg->factor < W_MIN_K || cfg->factor > W_MAX_K) return fail(FMX_E_INVALID, "factor must be in [2, 16]");
+    if (cfg->streams < 1 || cfg->streams > 65535) return fail(FMX_E_INVALID, "streams must be in [1, 65535]");
+    if (cfg->outputs < 1 || !cfg->stream_of_output) return fail(FMX_E_INVALID, "outputs must be >= 1, with a stream each");
+    if (cfg->max_block < cfg->factor || cfg->max_block % cfg->factor != 0) return fail(FMX_E_INVALID, "max_block must be a positive multiple of factor");
+    const int64_t lim = (int64_t)cfg->factor * W_RATE0 / 2 - 150000;
+    for (int m = 0; m < cfg->outputs; m++) {
+        if (cfg->stream_of_output[m] < 0 || cfg->stream_of_output[m] >= cfg->streams) return fail(FMX_E_INVALID, "stream_of_output entry out of range");
+        const int64_t f = cfg->offset_hz ? cfg->offset_hz[m] : 0;
+        if (f > lim || f < -lim) return fail(FMX_E_INVALID, "offset_hz: |f| must be <= factor * 1152000 - 150000");
+    }
+    return FMX_OK;
+}
+
+int wide_init(fmx_wideband w, const fmx_wideband_config *cfg) {
+    w->device = cfg->device; w->streams = cfg->streams; w->K = cfg->factor; w->outputs = cfg->outputs;
+    w->T = 16 * w->K + 1; w->max_block = cfg->max_block; w->Rw = (int64_t)w->K * W_RATE0;
+    w->h = wide_lowpass(w->K);
+    w->cur.assign((size_t)w->outputs, 0);
+    for (int m = 0; m < w->outputs; m++) w->cur[m] = cfg->offset_hz ? cfg->offset_hz[m] : 0;
+    w->want = w->cur;
+    w->outs.assign((size_t)w->outputs, WideOut{});
+    std::vector<int32_t> first((size_t)w->streams + 1, 0), list((size_t)w->outputs);
+    for (int m = 0; m < w->outputs; m++) first[(size_t)cfg->stream_of_output[m] + 1]++;
+    for (int s = 0; s < w->streams; s++) first[s + 1] += first[s];
+    std::vector<int32_t> fill(first.begin(), first.end() - 1);
+    std::vector<float2> taps((size_t)w->outputs * w->T);
+    for (int m = 0; m < w->outputs; m++) {
+        WideOut &o = w->outs[m];
+        o.stream = cfg->stream_of_output[m]; o.nseg = 1;
+        o.seg[0] = WideSeg{0, 0, (int32_t)pmod(w->cur[m], w->Rw)};      // P starts at 0
+        list[(size_t)fill[o.stream]++] = m;
+        wide_fold_taps(w, w->cur[m], taps.data() + (size_t)m * w->T);
+    }
+    std::vector<float2> rot((size_t)W_RATE0);                            // the oscillator table at the narrow rate (oscillator.cpp:26-35)
+    for (int i = 0; i < W_RATE0; i++) rot[i] = make_float2((float)std::cos(2.0 * design::kPi * i / W_RATE0), (float)std::sin(2.0 * design::kPi * i / W_RATE0));
+    HIPCHK(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&w->ev_out, hipEventDisableTiming));
+    DevMem &M = w->mem;
+    FMXCHK(M.alloc(w->d_hist[0], (size_t)w->streams * W_HIST, true));    // samples before the first call are zero
+    FMXCHK(M.alloc(w->d_hist[1], (size_t)w->streams * W_HIST, true));
+    FMXCHK(M.upload(w->d_taps, taps));
+    FMXCHK(M.upload(w->d_h, w->h));
+    FMXCHK(M.upload(w->d_rot, rot));
+    FMXCHK(M.upload(w->d_first, first));
+    FMXCHK(M.upload(w->d_list, list));
+    FMXCHK(M.alloc(w->d_outs, (size_t)w->outputs));
+    return FMX_OK;
+}
+
+// the head of a call: offsets that changed since the last one begin a new run at this call's first sample; runs that have left every window go
+int wide_flush(fmx_wideband w, hipStream_t s) {
+    std::vector<int32_t> want;
+    { std::lock_guard<std::mutex> lk(w->mtx); want = w->want; }
+    const int64_t c = w->g0;
+    if (w->multi > 0) {
+        w->multi = 0;
+        for (auto &o : w->outs) {
+            if (o.nseg <= 1) continue;
+            while (o.nseg > 1 && o.seg[o.nseg - 2].nbase <= c - (w->T - 1)) { o.nseg--; w->outs_dirty = true; }
+            if (o.nseg > 1) w->multi++;
+        }
+    }
+    std::vector<float2> g((size_t)w->T);
+    for (int m = 0; m < w->outputs; m++) {
+        if (want[m] == w->cur[m]) continue;
+        WideOut &o = w->outs[m];
+        const int32_t fm = (int32_t)pmod(want[m], w->Rw);
+        if (o.seg[0].nbase == c) o.seg[0].f = fm;                        // no sample was mixed with the offset it replaces
+        else {
+            const WideSeg &z = o.seg[0];
+            const int64_t p = pmod((int64_t)z.pbase - pmod(c - z.nbase, w->Rw) * (int64_t)z.f, w->Rw);    // P [c - 1]: the phase is kept
+            if (o.nseg == 1) w->multi++;
+            if (o.nseg < W_MAX_SEG) o.nseg++;
+            for (int k = o.nseg - 1; k > 0; k--) o.seg[k] = o.seg[k - 1];
+            o.seg[0] = WideSeg{c, (int32_t)p, fm};
+        }
+        w->cur[m] = want[m];
+        wide_fold_taps(w, want[m], g.data());
+        HIPCHK(hipMemcpyAsync(w->d_taps + (size_t)m * w->T, g.data(), sizeof(float2) * g.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));                                 // (g is reused; an offset change is a rare event)
+        w->outs_dirty = true;
+    }
+    if (w->outs_dirty) {
+        HIPCHK(hipMemcpyAsync(w->d_outs, w->outs.data(), sizeof(WideOut) * w->outs.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));                                 // (the mirror may change at the next call's head)
+        w->outs_dirty = false;
+    }
+    return FMX_OK;
+}
+
+int wide_check_call(fmx_wideband w, int32_t fmt, float s16_den, int64_t wide_stride, int64_t n_wide, int64_t narrow_stride) {
+    if (const ParamCheck pc = check_iq_format(fmt, s16_den); pc.code) return fail(pc.code, pc.msg);
+    if (n_wide < 0 || n_wide % w->K != 0) return fail(FMX_E_INVALID, "n_wide must be a multiple of factor");
+    if (n_wide > w->max_block) return fail(FMX_E_TOO_LARGE, "n_wide > max_block");
+    if (wide_stride < n_wide) return fail(FMX_E_INVALID, "wide_stride < n_wide");
+    if (narrow_stride < n_wide / w->K) return fail(FMX_E_INVALID, "narrow_stride < n_wide / factor");
+    return FMX_OK;
+}
+
+int wide_run(fmx_wideband w, const void *d_wide, int32_t fmt, float s16_den, int64_t wide_stride, int64_t n_wide, float2 *d_narrow,
+             int64_t narrow_stride, hipStream_t s) {
+    if (n_wide == 0) return FMX_OK;
+    FMXCHK(wide_flush(w, s));
+    WideArgs A{};
+    A.src = d_wide; A.fmt = fmt; A.qs = fmt == 3 ? 1.0f / s16_den : 1.0f / 128.0f;
+    A.src_stride = wide_stride; A.n_wide = n_wide; A.n_out = n_wide / w->K; A.g0 = w->g0;
+    A.dst = d_narrow; A.dst_stride = narrow_stride;
+    A.hist_in = w->d_hist[w->parity]; A.hist_out = w->d_hist[w->parity ^ 1];
+    A.taps = w->d_taps; A.h = w->d_h; A.rot = w->d_rot; A.outs = w->d_outs; A.first = w->d_first; A.list = w->d_list;
+    g_launch_err = hipSuccess;
+    launch_wide(A, w->K, w->streams, s);
+    if (g_launch_err != hipSuccess) return fail(FMX_E_HIP, std::string("wide_kernel: ") + hipGetErrorString(g_launch_err));
+    w->g0 += n_wide; w->parity ^= 1;
+    return FMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmx_wideband_taps(int32_t factor, float *dst, int32_t capacity, int32_t *n) {
+    if (factor < W_MIN_K || factor > W_MAX_K) return fail(FMX_E_INVALID, "factor must be in [2, 16]");
+    if (!dst && capacity > 0) return fail(FMX_E_INVALID, "null argument");
+    const std::vector<float> h = wide_lowpass(factor);
+    if (n) *n = (int32_t)h.size();
+    if (capacity < (int32_t)h.size()) return fail(FMX_E_TOO_LARGE, "capacity < 16 * factor + 1");
+    std::copy(h.begin(), h.end(), dst);
+    return FMX_OK;
+}
+
+int fmx_wideband_create(const fmx_wideband_config *cfg, fmx_wideband *out) {
+    if (!cfg || !out) return fail(FMX_E_INVALID, "null argument");
+    FMXCHK(wide_check_config(cfg));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(FMX_E_NO_DEVICE, "no HIP device visible: libfmx has no CPU fallback");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(FMX_E_INVALID, "device ordinal out of range");
+    HIPCHK(hipSetDevice(cfg->device));
+    fmx_wideband w = new (std::nothrow) fmx_wideband_s();
+    if (!w) return fail(FMX_E_NOMEM, "out of host memory");
+    if (const int rc = wide_init(w, cfg)) { const std::string msg = g_err; (void)fmx_wideband_destroy(w); g_err = msg; return rc; }
+    *out = w;
+    return FMX_OK;
+}
+
+int fmx_wideband_destroy(fmx_wideband w) {
+    if (!w) return FMX_OK;
+    (void)hipSetDevice(w->device);
+    if (w->stream) (void)hipStreamSynchronize(w->stream);
+    for (hipEvent_t e : {w->ev_in, w->ev_out}) if (e) (void)hipEventDestroy(e);
+    if (w->stream) (void)hipStreamDestroy(w->stream);
+    w->mem.release_all();
+    delete w;
+    return FMX_OK;
+}
+
+int fmx_wideband_set_offset(fmx_wideband w, int32_t output, int32_t hz) {
+    if (!w) return fail(FMX_E_INVALID, "null handle");
+    if (output < 0 || output >= w->outputs) return fail(FMX_E_INVALID, "output out of range");
+    const int64_t lim = w->Rw / 2 - 150000;
+    if (hz > lim || hz < -lim) return fail(FMX_E_INVALID, "offset: |f| must be <= factor * 1152000 - 150000");
+    std::lock_guard<std::mutex> lk(w->mtx);
+    w->want[(size_t)output] = hz;
+    return FMX_OK;
+}
+
+int fmx_wideband_process_device_raw(fmx_wideband w, const void *d_wide, int32_t format, float s16_denominator, int64_t wide_stride, int64_t n_wide,
+                                    float *d_narrow, int64_t narrow_stride, int64_t *n_narrow, void *hip_stream) {
+    if (!w || !d_wide || !d_narrow) return fail(FMX_E_INVALID, "null argument");
+    FMXCHK(wide_check_call(w, format, s16_denominator, wide_stride, n_wide, narrow_stride));
+    HIPCHK(hipSetDevice(w->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : w->stream;
+    if (!hip_stream) {                          // as fmx_process_device: behind what HIP's default stream holds now ...
+        HIPCHK(hipEventRecord(w->ev_in, nullptr));
+        HIPCHK(hipStreamWaitEvent(w->stream, w->ev_in, 0));
+    }
+    FMXCHK(wide_run(w, d_wide, format, s16_denominator, wide_stride, n_wide, reinterpret_cast<float2 *>(d_narrow), narrow_stride, s));
+    if (!hip_stream) {                          // ... and the default stream behind this call, so that an fmx_process_device (.., NULL) that follows finds its input
+        HIPCHK(hipEventRecord(w->ev_out, w->stream));
+        HIPCHK(hipStreamWaitEvent(nullptr, w->ev_out, 0));
+    }
+    if (n_narrow) *n_narrow = n_wide / w->K;
+    return FMX_OK;
+}
+
+int fmx_wideband_process_host_raw(fmx_wideband w, const void *wide, int32_t format, float s16_denominator, int64_t wide_stride, int64_t n_wide,
+                                  float *narrow, int64_t narrow_stride, int64_t *n_narrow) {
+    if (!w || !wide || !narrow) return fail(FMX_E_INVALID, "null argument");
+    FMXCHK(wide_check_call(w, format, s16_denominator, wide_stride, n_wide, narrow_stride));
+    HIPCHK(hipSetDevice(w->device));
+    const int64_t cap = w->max_block / w->K;
+    if (!w->d_in) {
+        FMXCHK(w->mem.alloc(w->d_in, (size_t)w->streams * (size_t)w->max_block * 8));    // sized for the widest format
+        FMXCHK(w->mem.alloc(w->d_out, (size_t)w->outputs * (size_t)cap));
+    }
+    if (n_narrow) *n_narrow = n_wide / w->K;
+    if (n_wide == 0) return FMX_OK;
+    const size_t bps = (size_t)bytes_per_sample(format);
+    HIPCHK(hipMemcpy2DAsync(w->d_in, bps * w->max_block, wide, bps * wide_stride, bps * n_wide, w->streams, hipMemcpyHostToDevice, w->stream));
+    FMXCHK(wide_run(w, w->d_in, format, s16_denominator, w->max_block, n_wide, w->d_out, cap, w->stream));
+    HIPCHK(hipMemcpy2DAsync(narrow, sizeof(float2) * narrow_stride, w->d_out, sizeof(float2) * cap, sizeof(float2) * (n_wide / w->K), w->outputs,
+                            hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(hipStreamSynchronize(w->stream));
+    return FMX_OK;
+}
+
+}  // extern "C"

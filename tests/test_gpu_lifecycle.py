@@ -1,4 +1,4 @@
-"""A handle gives back the device memory of every subsystem it allocated lazily (fmx_api.hip: DevMem, fmx_destroy)."""
+"""A handle gives back the device memory of every subsystem it allocated lazily (fmx_host.h: DevMem; fmx_api.hip: fmx_destroy)."""
 
 import ctypes as C
 

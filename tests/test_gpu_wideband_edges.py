@@ -1,4 +1,4 @@
-"""Stage W (fmx_wide.hip, fmx_wideband_* in fmx_api.hip) sample by sample on the GPU: every factor, the edges of tiles, groups and the run
+"""Stage W (fmx_wide.hip, fmx_wideband_* in fmx_wide_api.hip) sample by sample on the GPU: every factor, the edges of tiles, groups and the run
 list, strides, positions beyond 2^31 and 2^32 samples, the raw formats' extreme codes, and the C++ wrapper.
 
 Every comparison goes through wideband_model.check_per_sample against the float64 model: each sample of each output within 2 x the worst
