@@ -443,6 +443,56 @@ int  fmx_wideband_process_host_raw(fmx_wideband w, const void *wide, int32_t for
 /* The T = 16 K + 1 taps h for a factor (host only, needs no device); *n = T, FMX_E_TOO_LARGE when capacity < T. */
 int  fmx_wideband_taps(int32_t factor, float *dst, int32_t capacity, int32_t *n);
 
+/* ---- The band survey of a wide-band object (contract: DESIGN.md 4.9): where are the stations of a stream?  While a survey is on, every call
+ * also feeds each wide stream -- the very values stage W converts -- into an averaged power spectrum on the GPU; stage W's outputs are bit for
+ * bit what they are without it, and an object that never enables it allocates and launches nothing for it.
+ *   blocks   survey sample 0 of a stream is the first sample of the first call behind the enable; block b = survey samples [4096 b, 4096 (b + 1)),
+ *            no overlap; the 0 .. 4095 samples a call leaves over are carried, so the records do not depend on how a stream is cut into calls
+ *            (bit for bit)
+ *   window   w [i] = 0.5 - 0.5 cos (2 pi i / 4096), evaluated in f64, rounded to f32
+ *   power    p_b [k] = |sum_i w [i] x [4096 b + i] exp (-2 pi i ik / 4096)|^2 in f32
+ *   record   r covers blocks r B .. r B + B - 1 (B = blocks_per_record): P_r [k] = c * (the f32 sum of p_b [k] in block order),
+ *            c = 1 / (B sum w^2) formed in f64 and rounded to f32 -- white noise of power s^2 reads s^2 in every bin.  Bin k lies at k' Rw / 4096 Hz
+ *            from the stream's centre, k' = k for k < 2048 and k - 4096 otherwise.  The device keeps the last 4 records of every stream.
+ * A record sees the band for B * 4096 / Rw seconds: it should span the slowest modulation one cares about (a record shorter than a period of
+ * the modulating tone sees a carrier's instantaneous frequency and may put a station one raster line off).
+ * Both calls below belong to the processing thread. */
+/* blocks_per_record 1 .. 4096: a new survey begins at the next call (carry empty, sums zero, no records, index from 0), also while one is
+ * running.  0 ends the survey; its memory stays allocated.  Other values: FMX_E_INVALID. */
+int  fmx_wideband_survey_enable(fmx_wideband w, int32_t blocks_per_record);
+typedef struct fmx_survey_record {
+    int64_t index;       /* record number of the stream since the survey was enabled, from 0 (a gap = records dropped) */
+    int64_t end_sample;  /* wide-sample index since fmx_wideband_create, one past the record's last sample */
+    int32_t blocks;      /* B */
+    int32_t reserved;
+} fmx_survey_record;
+/* The records of `stream` completed since the last read of that stream, oldest first, at most `capacity` (and at most the 4 the device keeps):
+ * recs [i] and power [4096 i .. 4096 i + 4095], *n_records of them.  Waits for the object's last call only.  With the survey off, or before a
+ * record is complete: FMX_OK and 0 records.  FMX_E_INVALID: stream out of range; recs or power NULL with capacity > 0. */
+int  fmx_wideband_survey_read(fmx_wideband w, int32_t stream, fmx_survey_record *recs, float *power, int32_t capacity, int32_t *n_records);
+/* The stations of a record (host only, needs no device; all sums in f64, a bin's membership in a window decided in integers):
+ *   candidates  f_j = origin_hz + j raster_hz for every j with |f_j| <= Rw / 2 - 150 000: what fmx_wideband_set_offset accepts
+ *   usable bins |f_k| >= dc_guard_hz (a zero-IF receiver's LO leak sits at bin 0)
+ *   level       c_j = the mean of P over the usable bins with |f_k - f_j| <= 100 000 Hz, the whole channel
+ *   floor       F = the element at index n / 10 of the n usable bins with |f_k| <= Rw / 2 - 50 000, sorted ascending; *floor_db = 10 log10 F
+ *               (a lower decile of an average of B periodograms: it reads below the true noise, 3.6 dB at B = 4, 1.6 dB at B = 16)
+ *   station     snr_db = 10 log10 (c_j / F) > threshold_db, and c_j >= c_j' for every earlier and c_j > c_j' for every later candidate j'
+ *               with |f_j' - f_j| < 200 000
+ * Stations ascending in offset_hz, level_db = 10 log10 c_j; *n_stations = the number found; FMX_E_TOO_LARGE when capacity is smaller (nothing is
+ * written beyond it).  A record whose F is 0 has no stations.  FMX_E_INVALID: struct_size mismatch, factor outside 2 .. 16, raster_hz outside
+ * 50 000 .. 1 000 000, |origin_hz| >= raster_hz, dc_guard_hz outside 0 .. 99 999, a power entry that is negative or not finite. */
+typedef struct fmx_survey_find {
+    int32_t struct_size;       /* sizeof(fmx_survey_find) */
+    int32_t factor;            /* K of the stream the record is of */
+    int32_t raster_hz;         /* the broadcast raster, e.g. 100 000 */
+    int32_t origin_hz;         /* the offset of any raster line from the stream's centre */
+    int32_t dc_guard_hz;
+    float   threshold_db;
+} fmx_survey_find;
+typedef struct fmx_survey_station { int32_t offset_hz; float level_db, snr_db; int32_t reserved; } fmx_survey_station;
+int  fmx_wideband_survey_stations(const fmx_survey_find *cfg, const float *power, fmx_survey_station *out, int32_t capacity, int32_t *n_stations,
+                                  float *floor_db);
+
 #ifdef __cplusplus
 }
 #endif

@@ -446,6 +446,26 @@ struct WideArgs {
 };
 void launch_wide(const WideArgs &A, int K, int streams, hipStream_t s);
 
+// ---- stage W's band survey (fmx_survey.hip, fmx_survey.h) ---------------------------------------------------------
+// One call: the streams' samples behind their carries through the windowed 4096-point transform, block by block into `power`; the blocks
+// summed in order into `acc` and, at record boundaries, into the ring; the samples left over into the carry.
+struct SurveyArgs {
+    const void *src; int32_t fmt; float qs;    // the call's input, as WideArgs'
+    int64_t src_stride, n_wide;
+    int64_t blocks;                            // blocks the call completes (survey::Plan)
+    int32_t fill, fill_after;                  // samples in the carry in front of / behind the call
+    int32_t phase, B, slot0, fresh;            // blocks of the current record summed so far, blocks per record, the ring slot of the current
+                                               // record, != 0: a survey's first call (the accumulator starts at zero)
+    float scale;                               // 1 / (B sum w^2)
+    int64_t power_stride;                      // blocks `power` holds per stream
+    const float *window; const float2 *W;      // [4096] each
+    float2 *carry;                             // [streams][4096] converted samples
+    float *power;                              // [streams][power_stride][4096] the call's blocks
+    float *acc;                                // [streams][4096]
+    float *ring;                               // [streams][survey::RING][4096]
+};
+void launch_survey(const SurveyArgs &A, int streams, hipStream_t s);
+
 void launch_front(const DeviceTables &T, const DeviceBuffers &B, const CallGeom &G, const void *iq,
                   int channels, hipStream_t s);
 // fmx_front4.hip: whole tiles of the call front4_kernel can take (0: none), and its launch over that many

@@ -1,7 +1,9 @@
-// fmx_wide_api.hip -- the host half of stage W, wide-band ingest (fmx_wideband_* of include/fmx.h; the kernel is in fmx_wide.hip).  It shares nothing with
+// fmx_wide_api.hip -- the host half of stage W, wide-band ingest (fmx_wideband_* of include/fmx.h; the kernel is in fmx_wide.hip), and of its band
+// survey (fmx_wideband_survey_*; kernels in fmx_survey.hip, bookkeeping and station finder in fmx_survey.h).  It shares nothing with
 // fmx_handle but the error, the checking macros and the memory owner of fmx_host.h.
 #include "fmx_host.h"
 #include "fmx_design.h"
+#include "fmx_survey.h"
 
 #include <cmath>
 
@@ -29,6 +31,18 @@ struct fmx_wideband_s {
     WideOut *d_outs = nullptr;
     int32_t *d_first = nullptr, *d_list = nullptr;
     char *d_in = nullptr;                    // fmx_wideband_process_host_raw's staging buffers: d_in, d_out
+    // the band survey (fmx_survey.hip; allocated by the first fmx_wideband_survey_enable).  Every stream takes the same samples per call, so one
+    // set of counters serves them all; the device keeps none.
+    int32_t sv_B = 0, sv_fill = 0;           // blocks per record (0: off), samples in the carries
+    int64_t sv_blocks = 0, sv_g0 = 0;        // blocks completed since the survey began, and the wide sample (of g0's count) it began at
+    int64_t sv_cap = 0;                      // blocks of a call d_sv_power has room for, per stream
+    bool sv_fresh = false;                   // no call since the survey began: the accumulators start at zero
+    float sv_scale = 0.f;
+    std::vector<float> sv_win;
+    std::vector<int64_t> sv_read;            // per stream: the next record fmx_wideband_survey_read hands out
+    float *d_sv_win = nullptr, *d_sv_power = nullptr, *d_sv_acc = nullptr, *d_sv_ring = nullptr;
+    float2 *d_sv_W = nullptr, *d_sv_carry = nullptr;
+    hipEvent_t ev_sv = nullptr; bool ev_sv_set = false; hipStream_t rd_stream = nullptr;   // behind the last call's survey kernels; the read-out's copies
 };
 
 namespace {
@@ -148,6 +162,26 @@ int wide_check_call(fmx_wideband w, int32_t fmt, float s16_den, int64_t wide_str
     return FMX_OK;
 }
 
+// the band survey's share of a call, behind wide_kernel on the call's stream: which blocks and records the call completes is survey::plan's
+// integer arithmetic; the event is what fmx_wideband_survey_read waits on
+int survey_run(fmx_wideband w, const WideArgs &W, hipStream_t s) {
+    const survey::Plan p = survey::plan(w->sv_fill, W.n_wide, w->sv_blocks, w->sv_B);
+    if (p.blocks > w->sv_cap) return fail(FMX_E_TOO_LARGE, "survey: the call completes more blocks than max_block allows");
+    SurveyArgs A{};
+    A.src = W.src; A.fmt = W.fmt; A.qs = W.qs; A.src_stride = W.src_stride; A.n_wide = W.n_wide;
+    A.blocks = p.blocks; A.fill = w->sv_fill; A.fill_after = p.fill;
+    A.phase = p.phase; A.B = w->sv_B; A.slot0 = (int32_t)(p.record0 % survey::RING); A.fresh = w->sv_fresh ? 1 : 0;
+    A.scale = w->sv_scale; A.power_stride = w->sv_cap;
+    A.window = w->d_sv_win; A.W = w->d_sv_W; A.carry = w->d_sv_carry; A.power = w->d_sv_power; A.acc = w->d_sv_acc; A.ring = w->d_sv_ring;
+    g_launch_err = hipSuccess;
+    launch_survey(A, w->streams, s);
+    if (g_launch_err != hipSuccess) return fail(FMX_E_HIP, std::string("survey kernels: ") + hipGetErrorString(g_launch_err));
+    HIPCHK(hipEventRecord(w->ev_sv, s));
+    w->ev_sv_set = true;
+    w->sv_fill = p.fill; w->sv_blocks += p.blocks; w->sv_fresh = false;
+    return FMX_OK;
+}
+
 int wide_run(fmx_wideband w, const void *d_wide, int32_t fmt, float s16_den, int64_t wide_stride, int64_t n_wide, float2 *d_narrow,
              int64_t narrow_stride, hipStream_t s) {
     if (n_wide == 0) return FMX_OK;
@@ -161,6 +195,7 @@ int wide_run(fmx_wideband w, const void *d_wide, int32_t fmt, float s16_den, int
     g_launch_err = hipSuccess;
     launch_wide(A, w->K, w->streams, s);
     if (g_launch_err != hipSuccess) return fail(FMX_E_HIP, std::string("wide_kernel: ") + hipGetErrorString(g_launch_err));
+    if (w->sv_B > 0) FMXCHK(survey_run(w, A, s));
     w->g0 += n_wide; w->parity ^= 1;
     return FMX_OK;
 }
@@ -197,7 +232,8 @@ int fmx_wideband_destroy(fmx_wideband w) {
     if (!w) return FMX_OK;
     (void)hipSetDevice(w->device);
     if (w->stream) (void)hipStreamSynchronize(w->stream);
-    for (hipEvent_t e : {w->ev_in, w->ev_out}) if (e) (void)hipEventDestroy(e);
+    if (w->rd_stream) { (void)hipStreamSynchronize(w->rd_stream); (void)hipStreamDestroy(w->rd_stream); }
+    for (hipEvent_t e : {w->ev_in, w->ev_out, w->ev_sv}) if (e) (void)hipEventDestroy(e);
     if (w->stream) (void)hipStreamDestroy(w->stream);
     w->mem.release_all();
     delete w;
@@ -252,6 +288,67 @@ int fmx_wideband_process_host_raw(fmx_wideband w, const void *wide, int32_t form
                             hipMemcpyDeviceToHost, w->stream));
     HIPCHK(hipStreamSynchronize(w->stream));
     return FMX_OK;
+}
+
+int fmx_wideband_survey_enable(fmx_wideband w, int32_t blocks_per_record) {
+    if (!w) return fail(FMX_E_INVALID, "null handle");
+    if (blocks_per_record < 0 || blocks_per_record > survey::MAX_B) return fail(FMX_E_INVALID, "blocks_per_record must be in [0, 4096]");
+    if (blocks_per_record > 0 && !w->d_sv_ring) {
+        HIPCHK(hipSetDevice(w->device));
+        w->sv_win.resize(survey::N);
+        survey::make_window(w->sv_win.data());
+        std::vector<float2> W(survey::N);
+        survey::make_twiddles(W.data());
+        w->sv_cap = (w->max_block + survey::N - 1) / survey::N;          // (a carry of at most 4095 samples and max_block more)
+        w->sv_read.assign((size_t)w->streams, 0);
+        if (!w->ev_sv) HIPCHK(hipEventCreateWithFlags(&w->ev_sv, hipEventDisableTiming));
+        if (!w->rd_stream) HIPCHK(hipStreamCreateWithFlags(&w->rd_stream, hipStreamNonBlocking));
+        DevMem &M = w->mem;
+        FMXCHK(M.upload(w->d_sv_win, w->sv_win));
+        FMXCHK(M.upload(w->d_sv_W, W));
+        FMXCHK(M.alloc(w->d_sv_carry, (size_t)w->streams * survey::N));
+        FMXCHK(M.alloc(w->d_sv_power, (size_t)w->streams * (size_t)w->sv_cap * survey::N));
+        FMXCHK(M.alloc(w->d_sv_acc, (size_t)w->streams * survey::N));
+        FMXCHK(M.alloc(w->d_sv_ring, (size_t)w->streams * survey::RING * survey::N));   // (the last allocation: the test above)
+    }
+    w->sv_B = blocks_per_record;
+    if (blocks_per_record > 0) {                                          // a new survey from the next call on
+        w->sv_fill = 0; w->sv_blocks = 0; w->sv_g0 = w->g0; w->sv_fresh = true;
+        w->sv_scale = survey::record_scale(w->sv_win.data(), blocks_per_record);
+        std::fill(w->sv_read.begin(), w->sv_read.end(), 0);
+    }
+    return FMX_OK;
+}
+
+int fmx_wideband_survey_read(fmx_wideband w, int32_t stream, fmx_survey_record *recs, float *power, int32_t capacity, int32_t *n_records) {
+    if (!w || !n_records) return fail(FMX_E_INVALID, "null argument");
+    *n_records = 0;
+    if (stream < 0 || stream >= w->streams) return fail(FMX_E_INVALID, "stream out of range");
+    if (capacity < 0 || (capacity > 0 && (!recs || !power))) return fail(FMX_E_INVALID, "null argument");
+    if (w->sv_B <= 0) return FMX_OK;
+    const int64_t done = w->sv_blocks / w->sv_B;
+    const int64_t first = std::max(w->sv_read[(size_t)stream], done - survey::RING);   // (older ones were overwritten: the gap shows in `index`)
+    const int64_t n = std::min<int64_t>(capacity, done - first);
+    if (n <= 0) return FMX_OK;
+    HIPCHK(hipSetDevice(w->device));
+    if (w->ev_sv_set) HIPCHK(hipStreamWaitEvent(w->rd_stream, w->ev_sv, 0));          // the object's last call, not the device
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t r = first + i;
+        recs[i] = fmx_survey_record{r, w->sv_g0 + (r + 1) * (int64_t)w->sv_B * survey::N, w->sv_B, 0};
+        HIPCHK(hipMemcpyAsync(power + (size_t)i * survey::N, w->d_sv_ring + ((size_t)stream * survey::RING + (size_t)(r % survey::RING)) * survey::N,
+                              sizeof(float) * survey::N, hipMemcpyDeviceToHost, w->rd_stream));
+    }
+    HIPCHK(hipStreamSynchronize(w->rd_stream));
+    w->sv_read[(size_t)stream] = first + n;
+    *n_records = (int32_t)n;
+    return FMX_OK;
+}
+
+int fmx_wideband_survey_stations(const fmx_survey_find *cfg, const float *power, fmx_survey_station *out, int32_t capacity, int32_t *n_stations,
+                                 float *floor_db) {
+    const char *why = "";
+    const int rc = survey::find(cfg, power, out, capacity, n_stations, floor_db, &why);
+    return rc == FMX_OK ? FMX_OK : fail(rc, why);
 }
 
 }  // extern "C"

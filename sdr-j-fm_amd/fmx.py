@@ -41,6 +41,7 @@ EXPORTS = [
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
     "fmx_scan_results", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
     "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
+    "fmx_wideband_survey_enable", "fmx_wideband_survey_read", "fmx_wideband_survey_stations",
 ]
 
 
@@ -64,6 +65,26 @@ class FmxWidebandConfig(C.Structure):
         ("struct_size", C.c_int32), ("device", C.c_int32), ("streams", C.c_int32), ("factor", C.c_int32), ("outputs", C.c_int32),
         ("stream_of_output", C.POINTER(C.c_int32)), ("offset_hz", C.POINTER(C.c_int32)), ("max_block", C.c_int32),
     ]
+
+
+class FmxSurveyRecord(C.Structure):
+    _fields_ = [("index", C.c_int64), ("end_sample", C.c_int64), ("blocks", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FmxSurveyFind(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("factor", C.c_int32), ("raster_hz", C.c_int32), ("origin_hz", C.c_int32),
+                ("dc_guard_hz", C.c_int32), ("threshold_db", C.c_float)]
+
+
+class FmxSurveyStation(C.Structure):
+    _fields_ = [("offset_hz", C.c_int32), ("level_db", C.c_float), ("snr_db", C.c_float), ("reserved", C.c_int32)]
+
+
+# fmx_survey_record / fmx_survey_station as numpy records (Wideband.survey_read, survey_stations)
+SURVEY_RECORD_DTYPE = np.dtype([("index", np.int64), ("end_sample", np.int64), ("blocks", np.int32), ("reserved", np.int32)])
+SURVEY_STATION_DTYPE = np.dtype([("offset_hz", np.int32), ("level_db", np.float32), ("snr_db", np.float32), ("reserved", np.int32)])
+assert SURVEY_RECORD_DTYPE.itemsize == C.sizeof(FmxSurveyRecord) and SURVEY_STATION_DTYPE.itemsize == C.sizeof(FmxSurveyStation)
+SURVEY_BINS = 4096
 
 
 class FmxMeta(C.Structure):
@@ -213,6 +234,12 @@ def load_library(path=None):
     L.fmx_wideband_process_host_raw.argtypes = [vp, vp, i32, C.c_float, i64, i64, f32p, i64, C.POINTER(i64)]
     L.fmx_wideband_taps.restype = C.c_int
     L.fmx_wideband_taps.argtypes = [i32, f32p, i32, C.POINTER(i32)]
+    L.fmx_wideband_survey_enable.restype = C.c_int
+    L.fmx_wideband_survey_enable.argtypes = [vp, i32]
+    L.fmx_wideband_survey_read.restype = C.c_int
+    L.fmx_wideband_survey_read.argtypes = [vp, i32, vp, f32p, i32, C.POINTER(i32)]
+    L.fmx_wideband_survey_stations.restype = C.c_int
+    L.fmx_wideband_survey_stations.argtypes = [C.POINTER(FmxSurveyFind), f32p, vp, i32, C.POINTER(i32), f32p]
     if path is None:
         _lib = L
     return L
@@ -438,6 +465,22 @@ def wideband_taps(factor):
     return h[:n.value].copy()
 
 
+def survey_stations(power, factor, raster_hz=100000, origin_hz=0, threshold_db=10.0, dc_guard_hz=0):
+    """The stations of one survey record (include/fmx.h fmx_wideband_survey_stations; host only, needs no device): power [4096] of a stream
+    of `factor` -> (stations as SURVEY_STATION_DTYPE records, ascending in offset_hz, floor_db)."""
+    L = load_library()
+    power = np.ascontiguousarray(power, np.float32)
+    assert power.shape == (SURVEY_BINS,)
+    cfg = FmxSurveyFind(C.sizeof(FmxSurveyFind), int(factor), int(raster_hz), int(origin_hz), int(dc_guard_hz), float(threshold_db))
+    out = np.zeros(256, SURVEY_STATION_DTYPE)              # (16 * 2 304 000 / 50 000 = 737 candidates, each station beats its neighbours within 200 kHz)
+    n, floor_db = C.c_int32(), C.c_float()
+    rc = L.fmx_wideband_survey_stations(C.byref(cfg), power.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.c_void_p), out.size,
+                                        C.byref(n), C.byref(floor_db))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
+    return out[:n.value].copy(), floor_db.value
+
+
 class Wideband:
     """Stage W (include/fmx.h fmx_wideband): `streams` inputs at factor * 2 304 000 S/s -> one 2 304 000 S/s complex stream per station, in the
     layout Fmx.process_device takes."""
@@ -475,6 +518,19 @@ class Wideband:
 
     def set_offset(self, output, hz):
         self._check(self.L.fmx_wideband_set_offset(self.h, int(output), int(hz)))
+
+    def survey(self, blocks_per_record):
+        """Begin a band survey at the next call (blocks of 4096 wide samples per record, 1 .. 4096), or end it (0)."""
+        self._check(self.L.fmx_wideband_survey_enable(self.h, int(blocks_per_record)))
+
+    def survey_read(self, stream, capacity=4):
+        """The records of `stream` completed since its last read, oldest first -> (records as SURVEY_RECORD_DTYPE, power [n, 4096] f32)."""
+        recs = np.zeros(max(capacity, 1), SURVEY_RECORD_DTYPE)
+        power = np.zeros((max(capacity, 1), SURVEY_BINS), np.float32)
+        n = C.c_int32()
+        self._check(self.L.fmx_wideband_survey_read(self.h, int(stream), recs.ctypes.data_as(C.c_void_p), power.ctypes.data_as(C.POINTER(C.c_float)),
+                                                    int(capacity), C.byref(n)))
+        return recs[:n.value].copy(), power[:n.value].copy()
 
     def process_host(self, wide, fmt=IQ_F32, s16_denominator=2048.0):
         """wide: [streams, n_wide, 2] (or [n_wide, 2] for one stream) of float32 / uint8 / int8 / int16 according to fmt

@@ -61,6 +61,33 @@ public:
         return h;
     }
 
+    // the band survey (fmx_wideband_survey_*): from the next call on every stream's averaged power spectrum, records of blocks_per_record
+    // blocks of 4096 wide samples (1 .. 4096; 0 ends it).  The processing thread's, as readSurvey.
+    bool survey(int32_t blocks_per_record) { return check(fmx_wideband_survey_enable(w, blocks_per_record)); }
+    // the records of `stream` completed since its last read, oldest first, at most `capacity`: recs [i] and power [4096 i .. 4096 i + 4095]
+    bool readSurvey(int32_t stream, std::vector<fmx_survey_record> &recs, std::vector<float> &power, int32_t capacity = 4) {
+        recs.assign((size_t)(capacity > 0 ? capacity : 0), fmx_survey_record{});
+        power.assign(recs.size() * 4096, 0.0f);
+        int32_t n = 0;
+        const bool ok = check(fmx_wideband_survey_read(w, stream, recs.data(), power.data(), (int32_t)recs.size(), &n));
+        recs.resize((size_t)n);
+        power.resize((size_t)n * 4096);
+        return ok;
+    }
+    // the stations of one record (needs no device): the raster offsets setOffset accepts, ascending; empty where an argument is rejected
+    static std::vector<fmx_survey_station> stations(const float *power, int32_t factor, int32_t raster_hz = 100000, int32_t origin_hz = 0,
+                                                    float threshold_db = 10.0f, int32_t dc_guard_hz = 0, float *floor_db = nullptr) {
+        fmx_survey_find f{};
+        f.struct_size = (int32_t)sizeof(f); f.factor = factor; f.raster_hz = raster_hz; f.origin_hz = origin_hz; f.dc_guard_hz = dc_guard_hz;
+        f.threshold_db = threshold_db;
+        std::vector<fmx_survey_station> out(16);
+        int32_t n = 0;
+        int rc = fmx_wideband_survey_stations(&f, power, out.data(), (int32_t)out.size(), &n, floor_db);
+        if (rc == FMX_E_TOO_LARGE) { out.resize((size_t)n); rc = fmx_wideband_survey_stations(&f, power, out.data(), (int32_t)out.size(), &n, floor_db); }
+        out.resize(rc == FMX_OK ? (size_t)n : 0);
+        return out;
+    }
+
 private:
     bool check(int rc) { if (rc != FMX_OK) err = fmx_last_error(); return rc == FMX_OK; }
     fmx_wideband w = nullptr;

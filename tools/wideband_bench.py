@@ -5,7 +5,11 @@ per wide sample -- ALGORITHMIC, not counted: every sample once per stream plus t
 table's gathers and the tap fetches that miss the caches are not in it -- and the fraction of the HBM copy bound the stage alone reaches
 (bytes it must move: every wide sample once in, every narrow sample once out, over 8 TB/s).
 
-    python tools/wideband_bench.py [--streams 8] [--factor 8] [--stations 96] [--calls 20] [--warmup 5] [--format f32|u8|s8|s16]
+    python tools/wideband_bench.py [--streams 8] [--factor 8] [--stations 96] [--calls 20] [--warmup 5] [--format f32|u8|s8|s16] [--survey B]
+
+--survey B (blocks of 4096 wide samples per record, 1 .. 4096): the same stage-W calls timed once more with the band survey on
+(fmx_wideband_survey_enable), beside the time with it off from the same run; the line then also holds the survey's added ms per call and the
+scratch bytes it writes and reads again per call (4 B each per wide sample: ALGORITHMIC, as above).
 """
 import argparse
 import importlib
@@ -29,6 +33,7 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--format", default="f32", choices=["f32", "u8", "s8", "s16"])
+    ap.add_argument("--survey", type=int, default=0, metavar="B")
     args = ap.parse_args()
     import torch
     pkg = importlib.import_module("sdr-j-fm_amd")
@@ -73,6 +78,14 @@ def main():
         w.process_device(wide.data_ptr(), n_wide, n_wide, narrow.data_ptr(), n_narrow, fmt=fmt, hip_stream=stream.cuda_stream)
 
     out["ms_per_call_stage_w"] = round(timed(stage_w), 4)
+    if args.survey > 0:
+        w.survey(args.survey)
+        out["survey_blocks_per_record"] = args.survey
+        out["ms_per_call_stage_w_survey_on"] = round(timed(stage_w), 4)
+        out["survey_added_ms_per_call"] = round(out["ms_per_call_stage_w_survey_on"] - out["ms_per_call_stage_w"], 4)
+        out["survey_records_read_stream0"] = int(len(w.survey_read(0)[0]))
+        out["survey_scratch_bytes_written_and_read_per_call"] = 2 * 4 * (n_wide // 4096 * 4096) * S
+        w.survey(0)
     f = pkg.Fmx(C, device=0, max_block=n_narrow)
     for pid, v in ((m.P_BANDWIDTH, 165000), (m.P_LF_CUTOFF, 15000), (m.P_DEEMPHASIS, 50), (m.P_VOLUME_DB, -6.0)):
         f.set_param(pid, v)
