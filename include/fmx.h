@@ -493,6 +493,33 @@ typedef struct fmx_survey_station { int32_t offset_hz; float level_db, snr_db; i
 int  fmx_wideband_survey_stations(const fmx_survey_find *cfg, const float *power, fmx_survey_station *out, int32_t capacity, int32_t *n_stations,
                                   float *floor_db);
 
+/* ---- Stage W at any receiver rate (contract: DESIGN.md 4.10): a *rate object* is a fmx_wideband created with its wide rate Rw in Hz instead of
+ * a factor -- what a fixed-rate receiver (2.5, 8, 10, 12.5, 20 MS/s ...) or a recorded IQ file delivers.  Ro = 2 304 000, g = gcd (Rw, Ro),
+ * L = Ro / g, M = Rw / g.
+ *   accepted   Ro < Rw <= 16 Ro, Rw no multiple of Ro (those stay with `factor`: one configuration has one answer), L <= 576.  E.g. 2 400 000
+ *              (24/25), 2 500 000 (576/625), 3 000 000, 6 000 000, 8 000 000 (36/125), 10 000 000 (144/625), 12 500 000 (576/3125), 20 000 000
+ *              (72/625), 36 000 000 (8/125).  Everything else: FMX_E_INVALID, the text names the rule.
+ *   mix        stage W's: v_m [n] = x [n] O (P_m [n]), P_m [n] = (P_m [n - 1] - f_m) mod Rw, O in f64 rounded to f32, P_m from 0 and never reset,
+ *              |f_m| <= Rw / 2 - 150 000; a change takes effect at the first sample of the next call
+ *   prototype  N_H = 16 M + 1 taps at the rate M Ro: tmp = the reference's Blackman low-pass (fir-filters.cpp:41-62) with
+ *              f = (float) 400000 / (float) (M Ro), H [k] = f32 (tmp [k] L / sum tmp), the sum in f64
+ *   outputs    output j of a stream, from its first sample: q_j = (j + 1) M - 1, n_j = q_j div L, p_j = q_j mod L,
+ *              y_m [j] = sum_{i >= 0, p_j + L i < N_H} H [p_j + L i] v_m [n_j - i], f32 accumulation in tap order; zeros in front of the stream.
+ *              After N samples a stream has produced floor (N L / M) outputs: a call's count differs by one from call to call.
+ *   calls      n_wide = 0 is a no-op; otherwise ceil (M / L) <= n_wide <= max_block (FMX_E_INVALID / FMX_E_TOO_LARGE) and narrow_stride at least
+ *              the call's count.  History and every P_m carry across calls: the outputs do not depend on how a stream is cut, bit for bit.
+ * cfg->factor must be 0, cfg->max_block any value >= ceil (M / L).  fmx_wideband_set_offset, both process calls, the survey calls and
+ * fmx_wideband_destroy take a rate object as they take a factor object (the survey's bins then lie at k' Rw / 4096 Hz). */
+int  fmx_wideband_create_rate(const fmx_wideband_config *cfg, int32_t wide_rate_hz, fmx_wideband *out);
+/* Processing thread: the outputs per station that the next call will produce for n_wide samples (a factor object: n_wide / K). */
+int64_t fmx_wideband_outputs_for(fmx_wideband w, int64_t n_wide);
+/* The prototype H for a rate (host only, needs no device); *n = 16 M + 1, *L_out and *M_out the ratio (each may be NULL); FMX_E_TOO_LARGE when
+ * capacity is smaller (n, L_out, M_out are still set). */
+int  fmx_wideband_rate_taps(int32_t wide_rate_hz, float *dst, int32_t capacity, int32_t *n, int32_t *L_out, int32_t *M_out);
+/* fmx_wideband_survey_stations for a record of a stream at wide_rate_hz (an accepted rate); cfg->factor must be 0. */
+int  fmx_wideband_survey_stations_rate(const fmx_survey_find *cfg, int32_t wide_rate_hz, const float *power, fmx_survey_station *out, int32_t capacity,
+                                       int32_t *n_stations, float *floor_db);
+
 #ifdef __cplusplus
 }
 #endif

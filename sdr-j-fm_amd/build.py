@@ -24,6 +24,7 @@ SOURCES = [
     ("fmx_promote.hip", ["-ffp-contract=off"]),
     ("fmx_scan.hip", []),
     ("fmx_wide.hip", []),
+    ("fmx_wide_rate.hip", []),
     ("fmx_survey.hip", []),
     # the host files (fmx_host.h): they design filters through fmx_design.h, whose taps must not depend on contraction either
     ("fmx_api.hip", ["-ffp-contract=off"]),

@@ -446,6 +446,22 @@ struct WideArgs {
 };
 void launch_wide(const WideArgs &A, int K, int streams, hipStream_t s);
 
+// ---- stage W at any receiver rate (fmx_wide_rate.hip, fmx_wide_rate.h) ----------------------------------------------------
+// Rw / 2 304 000 = M / L in lowest terms: output j takes the taps H [p_j + L i] of a 16 M + 1 tap prototype, its newest sample is n_j.  The
+// runs (WideOut) are stage W's; pbase is any phase in [0, Rw).
+struct WideRateArgs {
+    const void *src; int32_t fmt; float qs;
+    int64_t src_stride, n_wide, n_out, g0, j0; // j0: outputs of the stream in front of this call, floor (g0 L / M)
+    float2 *dst; int64_t dst_stride;
+    const float2 *hist_in; float2 *hist_out;   // [streams][wrate::HIST]: the last NP - 1 converted samples, oldest first
+    int32_t Rw, L, M, NP;
+    const float *phases;                       // [L][NP] H [p + L i], zeros behind the prototype's end
+    const float2 *rot;                         // [outputs][NP] O ((i f) mod Rw)
+    const WideOut *outs;
+    const int32_t *first, *list;
+};
+void launch_wide_rate(const WideRateArgs &A, int streams, hipStream_t s);
+
 // ---- stage W's band survey (fmx_survey.hip, fmx_survey.h) ---------------------------------------------------------
 // One call: the streams' samples behind their carries through the windowed 4096-point transform, block by block into `power`; the blocks
 // summed in order into `acc` and, at record boundaries, into the ring; the samples left over into the carry.

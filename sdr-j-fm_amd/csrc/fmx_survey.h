@@ -141,20 +141,23 @@ inline Plan plan(int32_t fill, int64_t n_wide, int64_t blocks_so_far, int32_t B)
 }
 
 // ---- the station finder (include/fmx.h fmx_wideband_survey_stations): f64 sums, membership of a bin in a window decided in integers -------
+// Rw: the stream's rate, which the caller has checked (cfg->factor must then be 0), or 0: cfg->factor * 2 304 000.
 // Returns FMX_OK, FMX_E_INVALID (*why says which argument) or FMX_E_TOO_LARGE.
-inline int find(const fmx_survey_find *cfg, const float *power, fmx_survey_station *out, int32_t capacity, int32_t *n_stations, float *floor_db,
-                const char **why) {
+inline int find(const fmx_survey_find *cfg, int64_t Rw, const float *power, fmx_survey_station *out, int32_t capacity, int32_t *n_stations,
+                float *floor_db, const char **why) {
     *why = "";
     if (!cfg || !power || !n_stations || (!out && capacity > 0) || capacity < 0) { *why = "null argument"; return FMX_E_INVALID; }
     if (cfg->struct_size != (int32_t)sizeof(fmx_survey_find)) { *why = "fmx_survey_find.struct_size mismatch"; return FMX_E_INVALID; }
-    if (cfg->factor < 2 || cfg->factor > 16) { *why = "factor must be in [2, 16]"; return FMX_E_INVALID; }
+    if (Rw > 0 && cfg->factor != 0) { *why = "factor must be 0 where a wide rate is given"; return FMX_E_INVALID; }
+    if (Rw <= 0 && (cfg->factor < 2 || cfg->factor > 16)) { *why = "factor must be in [2, 16]"; return FMX_E_INVALID; }
+    if (Rw <= 0) Rw = (int64_t)cfg->factor * RATE0;
     if (cfg->raster_hz < 50000 || cfg->raster_hz > 1000000) { *why = "raster_hz must be in [50000, 1000000]"; return FMX_E_INVALID; }
     if (cfg->origin_hz <= -cfg->raster_hz || cfg->origin_hz >= cfg->raster_hz) { *why = "|origin_hz| must be < raster_hz"; return FMX_E_INVALID; }
     if (cfg->dc_guard_hz < 0 || cfg->dc_guard_hz > 99999) { *why = "dc_guard_hz must be in [0, 99999]"; return FMX_E_INVALID; }
     for (int k = 0; k < N; k++)
         if (!(power[k] >= 0.f) || !std::isfinite(power[k])) { *why = "power holds a negative or non-finite entry"; return FMX_E_INVALID; }
     *n_stations = 0;
-    const int64_t Rw = (int64_t)cfg->factor * RATE0, raster = cfg->raster_hz;
+    const int64_t raster = cfg->raster_hz;
     // bin k lies at kp Rw / N Hz; every comparison with a frequency is made on kp Rw against the frequency times N
     auto kp = [](int k) { return (int64_t)(k < N / 2 ? k : k - N); };
     auto usable = [&](int k) { const int64_t f = kp(k) * Rw; return (f < 0 ? -f : f) >= (int64_t)cfg->dc_guard_hz * N; };

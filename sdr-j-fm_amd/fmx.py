@@ -42,6 +42,7 @@ EXPORTS = [
     "fmx_scan_results", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
     "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
     "fmx_wideband_survey_enable", "fmx_wideband_survey_read", "fmx_wideband_survey_stations",
+    "fmx_wideband_create_rate", "fmx_wideband_outputs_for", "fmx_wideband_rate_taps", "fmx_wideband_survey_stations_rate",
 ]
 
 
@@ -240,6 +241,14 @@ def load_library(path=None):
     L.fmx_wideband_survey_read.argtypes = [vp, i32, vp, f32p, i32, C.POINTER(i32)]
     L.fmx_wideband_survey_stations.restype = C.c_int
     L.fmx_wideband_survey_stations.argtypes = [C.POINTER(FmxSurveyFind), f32p, vp, i32, C.POINTER(i32), f32p]
+    L.fmx_wideband_create_rate.restype = C.c_int
+    L.fmx_wideband_create_rate.argtypes = [C.POINTER(FmxWidebandConfig), i32, C.POINTER(vp)]
+    L.fmx_wideband_outputs_for.restype = i64
+    L.fmx_wideband_outputs_for.argtypes = [vp, i64]
+    L.fmx_wideband_rate_taps.restype = C.c_int
+    L.fmx_wideband_rate_taps.argtypes = [i32, f32p, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.fmx_wideband_survey_stations_rate.restype = C.c_int
+    L.fmx_wideband_survey_stations_rate.argtypes = [C.POINTER(FmxSurveyFind), i32, f32p, vp, i32, C.POINTER(i32), f32p]
     if path is None:
         _lib = L
     return L
@@ -465,17 +474,37 @@ def wideband_taps(factor):
     return h[:n.value].copy()
 
 
-def survey_stations(power, factor, raster_hz=100000, origin_hz=0, threshold_db=10.0, dc_guard_hz=0):
+def wideband_rate_taps(rate_hz):
+    """The prototype of stage W for a wide rate in Hz (include/fmx.h fmx_wideband_rate_taps; host only, needs no device)
+    -> (H [16 M + 1] f32, L, M)."""
+    lib = load_library()
+    n, L, M = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = lib.fmx_wideband_rate_taps(int(rate_hz), None, 0, C.byref(n), C.byref(L), C.byref(M))
+    if rc != FMX_E_TOO_LARGE:
+        raise FmxError(rc, lib.fmx_last_error().decode("utf-8", "replace"))
+    h = np.zeros(n.value, np.float32)
+    rc = lib.fmx_wideband_rate_taps(int(rate_hz), h.ctypes.data_as(C.POINTER(C.c_float)), h.size, C.byref(n), C.byref(L), C.byref(M))
+    if rc != FMX_OK:
+        raise FmxError(rc, lib.fmx_last_error().decode("utf-8", "replace"))
+    return h, L.value, M.value
+
+
+def survey_stations(power, factor=0, raster_hz=100000, origin_hz=0, threshold_db=10.0, dc_guard_hz=0, rate_hz=None):
     """The stations of one survey record (include/fmx.h fmx_wideband_survey_stations; host only, needs no device): power [4096] of a stream
-    of `factor` -> (stations as SURVEY_STATION_DTYPE records, ascending in offset_hz, floor_db)."""
+    of `factor`, or of rate_hz S/s (fmx_wideband_survey_stations_rate; factor then stays 0)
+    -> (stations as SURVEY_STATION_DTYPE records, ascending in offset_hz, floor_db)."""
     L = load_library()
     power = np.ascontiguousarray(power, np.float32)
     assert power.shape == (SURVEY_BINS,)
     cfg = FmxSurveyFind(C.sizeof(FmxSurveyFind), int(factor), int(raster_hz), int(origin_hz), int(dc_guard_hz), float(threshold_db))
     out = np.zeros(256, SURVEY_STATION_DTYPE)              # (16 * 2 304 000 / 50 000 = 737 candidates, each station beats its neighbours within 200 kHz)
     n, floor_db = C.c_int32(), C.c_float()
-    rc = L.fmx_wideband_survey_stations(C.byref(cfg), power.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.c_void_p), out.size,
-                                        C.byref(n), C.byref(floor_db))
+    if rate_hz is not None:
+        rc = L.fmx_wideband_survey_stations_rate(C.byref(cfg), int(rate_hz), power.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.c_void_p),
+                                                 out.size, C.byref(n), C.byref(floor_db))
+    else:
+        rc = L.fmx_wideband_survey_stations(C.byref(cfg), power.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.c_void_p), out.size,
+                                            C.byref(n), C.byref(floor_db))
     if rc != FMX_OK:
         raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
     return out[:n.value].copy(), floor_db.value
@@ -486,10 +515,12 @@ class Wideband:
     layout Fmx.process_device takes."""
     NARROW_RATE = 2304000
 
-    def __init__(self, factor, stream_of_output, offset_hz, streams=1, max_block=None, device=0):
+    def __init__(self, factor=0, stream_of_output=(0,), offset_hz=(0,), streams=1, max_block=None, device=0, rate_hz=None):
+        """factor 2 .. 16, or rate_hz: a rate object (fmx_wideband_create_rate) for a receiver whose rate is no multiple of 2 304 000."""
         self.L = load_library()
-        self.factor, self.streams, self.outputs = int(factor), int(streams), len(stream_of_output)
-        self.max_block = int(max_block) if max_block is not None else 16384 * self.factor
+        self.rate_hz = int(rate_hz) if rate_hz is not None else None
+        self.factor, self.streams, self.outputs = (0 if rate_hz is not None else int(factor)), int(streams), len(stream_of_output)
+        self.max_block = int(max_block) if max_block is not None else 16384 * (self.factor or 16)
         assert len(offset_hz) == self.outputs
         cfg = FmxWidebandConfig()
         cfg.struct_size = C.sizeof(FmxWidebandConfig)
@@ -499,7 +530,10 @@ class Wideband:
         cfg.stream_of_output = C.cast(self._map, C.POINTER(C.c_int32))
         cfg.offset_hz = C.cast(self._off, C.POINTER(C.c_int32))
         self.h = C.c_void_p()
-        self._check(self.L.fmx_wideband_create(C.byref(cfg), C.byref(self.h)))
+        if self.rate_hz is not None:
+            self._check(self.L.fmx_wideband_create_rate(C.byref(cfg), self.rate_hz, C.byref(self.h)))
+        else:
+            self._check(self.L.fmx_wideband_create(C.byref(cfg), C.byref(self.h)))
 
     def _check(self, rc):
         if rc != FMX_OK:
@@ -519,6 +553,10 @@ class Wideband:
     def set_offset(self, output, hz):
         self._check(self.L.fmx_wideband_set_offset(self.h, int(output), int(hz)))
 
+    def outputs_for(self, n_wide):
+        """The outputs per station that the next call will produce for n_wide samples (processing thread)."""
+        return int(self.L.fmx_wideband_outputs_for(self.h, int(n_wide)))
+
     def survey(self, blocks_per_record):
         """Begin a band survey at the next call (blocks of 4096 wide samples per record, 1 .. 4096), or end it (0)."""
         self._check(self.L.fmx_wideband_survey_enable(self.h, int(blocks_per_record)))
@@ -534,14 +572,14 @@ class Wideband:
 
     def process_host(self, wide, fmt=IQ_F32, s16_denominator=2048.0):
         """wide: [streams, n_wide, 2] (or [n_wide, 2] for one stream) of float32 / uint8 / int8 / int16 according to fmt
-        -> complex IQ float32 [outputs, n_wide / factor, 2]."""
+        -> complex IQ float32 [outputs, n_wide / factor (a rate object: outputs_for (n_wide)), 2]."""
         dt = {IQ_U8: np.uint8, IQ_S8: np.int8, IQ_S16: np.int16, IQ_F32: np.float32}[fmt]
         wide = np.ascontiguousarray(wide, dt)
         if wide.ndim == 2:
             wide = wide[None]
         assert wide.shape[0] == self.streams and wide.shape[2] == 2
         n = wide.shape[1]
-        cap = max(n // self.factor, 1)
+        cap = max(self.outputs_for(n), 1)
         out = np.zeros((self.outputs, cap, 2), np.float32)
         got = C.c_int64()
         self._check(self.L.fmx_wideband_process_host_raw(self.h, wide.ctypes.data_as(C.c_void_p), fmt, float(s16_denominator), n, n,
@@ -549,7 +587,7 @@ class Wideband:
         return out[:, :got.value]
 
     def process_device(self, d_wide_ptr, wide_stride, n_wide, d_narrow_ptr, narrow_stride, fmt=IQ_F32, s16_denominator=2048.0, hip_stream=None):
-        """Device pointers, asynchronous on hip_stream; returns n_wide / factor.  Fmx.process_device (d_narrow_ptr, narrow_stride, ...) on the
+        """Device pointers, asynchronous on hip_stream; returns the outputs per station (n_wide / factor; a rate object: outputs_for (n_wide)).  Fmx.process_device (d_narrow_ptr, narrow_stride, ...) on the
         same stream takes the result as it lies."""
         got = C.c_int64()
         self._check(self.L.fmx_wideband_process_device_raw(self.h, C.c_void_p(d_wide_ptr), fmt, float(s16_denominator), wide_stride, n_wide,

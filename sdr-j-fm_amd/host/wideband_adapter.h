@@ -26,6 +26,19 @@ public:
         c.stream_of_output = stream_of_output.data(); c.offset_hz = offset_hz.data(); c.max_block = max_block;
         if (fmx_wideband_create(&c, &w) != FMX_OK) { err = fmx_last_error(); w = nullptr; }
     }
+    // A receiver whose rate is no multiple of 2 304 000 (Airspy at 2.5 / 10, SDRplay at 8, a USRP at 12.5 MS/s, a recorded file at 20): a rate
+    // object (fmx_wideband_create_rate).  factor () is 0; a call's count is outputsFor (n_wide), no longer n_wide / factor ().
+    struct Rate { int32_t hz; };
+    Wideband(Rate wide_rate, int32_t streams, const std::vector<int32_t> &stream_of_output, const std::vector<int32_t> &offset_hz,
+             int32_t max_block, int device = 0)
+        : K(0), nOutputs((int32_t)stream_of_output.size()) {
+        if (fmx_abi_version() != FMX_ABI_VERSION) { err = "libfmx has another ABI version than this adapter was built for"; return; }
+        if (offset_hz.size() != stream_of_output.size()) { err = "one offset per output"; return; }
+        fmx_wideband_config c{};
+        c.struct_size = (int32_t)sizeof(c); c.device = device; c.streams = streams; c.factor = 0; c.outputs = nOutputs;
+        c.stream_of_output = stream_of_output.data(); c.offset_hz = offset_hz.data(); c.max_block = max_block;
+        if (fmx_wideband_create_rate(&c, wide_rate.hz, &w) != FMX_OK) { err = fmx_last_error(); w = nullptr; }
+    }
     ~Wideband() { if (w) fmx_wideband_destroy(w); }
     Wideband(const Wideband &) = delete;
     Wideband &operator=(const Wideband &) = delete;
@@ -51,6 +64,17 @@ public:
     bool processHost(const void *wide, fmx_iq_format format, float s16_denominator, int64_t wide_stride, int64_t n_wide, float *narrow,
                      int64_t narrow_stride, int64_t *n_narrow = nullptr) {
         return check(fmx_wideband_process_host_raw(w, wide, (int32_t)format, s16_denominator, wide_stride, n_wide, narrow, narrow_stride, n_narrow));
+    }
+    // the outputs per station that the next call will produce for n_wide samples (the processing thread's)
+    int64_t outputsFor(int64_t n_wide) const { return fmx_wideband_outputs_for(w, n_wide); }
+    // a rate object's prototype: 16 M + 1 real taps (needs no device); empty where the rate is refused
+    static std::vector<float> rateTaps(int32_t wide_rate_hz, int32_t *L = nullptr, int32_t *M = nullptr) {
+        int32_t n = 0;
+        std::vector<float> h;
+        if (fmx_wideband_rate_taps(wide_rate_hz, nullptr, 0, &n, L, M) != FMX_E_TOO_LARGE) return h;
+        h.resize((size_t)n);
+        if (fmx_wideband_rate_taps(wide_rate_hz, h.data(), n, &n, L, M) != FMX_OK) h.clear();
+        return h;
     }
     // the stage's low-pass: 16 factor + 1 real taps (needs no device)
     static std::vector<float> taps(int32_t factor) {
