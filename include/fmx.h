@@ -396,6 +396,45 @@ int64_t fmx_last_rds_samples_of(fmx_handle h, int32_t channel);
  * `capacity`; the library keeps the last 1024 per channel (a reader that fell behind sees the gap in `block`) */
 int  fmx_scan_results(fmx_handle h, int32_t channel, fmx_scan_result *out, int32_t capacity, int32_t *n_results);
 
+/* ---- the modulation meter: what a broadcast monitor reports per station -- peak deviation over 50 ms windows (ITU-R SM.1268), multiplex
+ * power (the mean square of the deviation, which a host averages over 60 s for ITU-R BS.412) and pilot deviation -- as one record per channel and window,
+ * computed on the GPU behind the demodulator, for one channel and for thousands alike.
+ *
+ * Inputs, for fm sample j of a channel (j counts the handle's fm samples since fmx_create, as the taps number them): d [j], the demodulator output, the
+ * value of FMX_TAP_DEMOD (fm-processor.cpp:497), and phi [j], currentPilotPhase, the value of FMX_TAP_PILOT_PHASE (:695).
+ * Window w is the fm samples [9600 w, 9600 (w + 1)), 50 ms; every channel shares the grid.  Inside a window sample i = j - 9600 w belongs to lane
+ * l = i mod 64 as its step q = i div 64 (150 steps).  Each lane accumulates in step order, in f32, without contraction into fma:
+ *     mx = max (mx, d) from -inf, mn = min (mn, d) from +inf, s1 += d, s2 += f32 (d d), si += f32 (d S), sq += f32 (d C)   (sums from 0)
+ * with S, C the device's f32 sine and cosine (sincosf) of the f32 phi.  At the window's end the 64 lanes are combined by the butterfly
+ * a [l] = a [l] op a [l xor m] for m = 32, 16, 8, 4, 2, 1, and
+ *     peak_pos = mx, peak_neg = mn, mean = s1 / 9600.0f, mean_square = s2 / 9600.0f, pilot_i = si / 4800.0f, pilot_q = sq / 4800.0f.
+ * A pilot a sin (phi + e) in d gives (pilot_i, pilot_q) = a (cos e, sin e): its deviation is hypot (pilot_i, pilot_q).
+ * What a channel carries between calls is its 64 x 6 lane accumulators and no sample: on the same d and phi a record is the same bit for bit however
+ * the stream is cut into calls, or a call into pieces, the pilot fields included.  (d and phi themselves depend on the cut in their last bits -- the RF DC
+ * removal and the AFC are evaluated in tiles and segments that begin with the call; not so the PLL decoder with RF DC removal off --, and records of
+ * two cuts differ by as much: DESIGN.md 4.11.)
+ * Window w of a channel leaves a record only if the channel's meter was on in every call that covered one of its samples: a meter switched on in
+ * mid-window starts at the next boundary, one switched off drops the window in progress; a scanning channel's meter runs on, as its chain does.
+ * The device keeps the last 64 records (3.2 s) per channel.  Everything else a handle delivers -- PCM, RDS, meta, taps, peaks, scan records -- is bit for
+ * bit what it is without the meter.  The rows the meter reads are handle-wide: a batch with one metered channel writes them (8 bytes per fm sample) for
+ * every channel and runs as a batch that keeps them does (see fmx_last_second_group). */
+typedef struct fmx_mod_record {
+    int64_t index;        /* the window w; a gap means windows that were not metered or that the reader lost */
+    int64_t end_sample;   /* 9600 (w + 1): the fm sample behind the window's last */
+    float   peak_pos, peak_neg, mean, mean_square, pilot_i, pilot_q;      /* in the demodulator's units (fmx_mod_hz_per_unit), mean_square in their square */
+} fmx_mod_record;
+/* switches the meter of a channel (-1: of every channel) on or off; from any thread, takes effect at the next call */
+int  fmx_mod_meter_enable(fmx_handle h, int32_t channel, int32_t on);
+/* the records the channels first_channel .. first_channel + n_channels - 1 completed since this function last read them, oldest first, at most
+ * capacity_per_channel each (more stay for the next read): channel k's at out [k * capacity_per_channel ..], their number in n_records [k].  One
+ * read-out of the device for the whole range. */
+int  fmx_mod_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_mod_record *out, int32_t capacity_per_channel, int32_t *n_records);
+/* Hz per unit of d (host only, needs no device) for the decoders whose discriminator value is radians per sample -- 2 the PLL decoder's phase increment
+ * (pllC.cpp:80-84), 3 Mixed and 4 ComplexBB (an atan2) --: res = 20 (r - afc) / K_FM, K_FM = 2 B_FM pi / F_G (fm-demodulator.cpp:58-64,198), hence
+ * hz = K_FM fmRate / (40 pi) = B_FM fmRate / (20 F_G), 47 261.5 at 192 000.  FMX_E_UNSUPPORTED for 1 (AM: no frequency), 5 (RealBB: an arcsine table's
+ * half angle of a sine, no linear scale) and 6 (Diff: a difference quotient, no angle). */
+int  fmx_mod_hz_per_unit(int32_t decoder, int32_t fmRate, double *hz);
+
 /* introspection used by the parity tests: the filter taps the kernels run with.
  * which: 0 front-end polyphase taps, 1 PSS low-pass, 2 audio+resampler FIR, 3 resampler alone,
  * 4 the noise squelch's two order-20 filters: [2][10] x (A1, A2, B1, B2), then the two gains (high-pass first),

@@ -23,6 +23,7 @@ SOURCES = [
     ("fmx_ola.hip", ["-ffp-contract=off"]),
     ("fmx_promote.hip", ["-ffp-contract=off"]),
     ("fmx_scan.hip", []),
+    ("fmx_meter.hip", ["-ffp-contract=off"]),      # (the modulation meter's sums are defined without fma: DESIGN 4.11)
     ("fmx_wide.hip", []),
     ("fmx_wide_rate.hip", []),
     ("fmx_survey.hip", []),

@@ -630,6 +630,19 @@ int ensure_scan(fmx_handle h) {
     return FMX_OK;
 }
 
+// the modulation meter's buffers (fmx_meter.hip), allocated by the first call in which a channel's meter is on
+int ensure_meter(fmx_handle h) {
+    if (h->meter_alloc) return FMX_OK;
+    const size_t C = (size_t)h->channels;
+    HIPCHK(hipDeviceSynchronize());
+    FMXCHK(h->mem.alloc(h->d_meter_state, C * meter::QUANT * meter::LANES, true));
+    FMXCHK(h->mem.alloc(h->d_meter_ring, C * meter::RING, true));
+    FMXCHK(h->mem.alloc(h->d_meter_jobs, C));
+    h->call_meter.assign(C, 0); h->meter_on_from.assign(C, -1); h->meter_produced.assign(C, 0); h->rd.mod.assign(C, 0);
+    h->meter_alloc = true;
+    return FMX_OK;
+}
+
 // the tiled work arrays of the demodulator pre-pass (fmx_demod.hip): limited / unlimited samples in, demodulator output out.  (Allocated by the first call
 // that needs them -- before run_call decides how the call is made: a call in pieces needs them too.)
 int ensure_prepass_arrays(fmx_handle h) {
@@ -641,9 +654,10 @@ int ensure_prepass_arrays(fmx_handle h) {
 // the summary of the settings as they stand (fmx_needs.h); under mtx
 CallNeeds summarize(fmx_handle h) {
     CallNeeds nd = needs_begin(h->channels, h->twins, h->ola_mode, h->scope_taps.load());
-    for (const ChanParams &p : h->params) {
+    for (size_t c = 0; c < h->params.size(); c++) {
+        const ChanParams &p = h->params[c];
         const FrontSet &fs = h->h_front_sets[(size_t)p.front_set];
-        needs_add(nd, ChanNeeds{p.decoder, p.squelch_mode, p.rds_mode, p.lo_freq, p.att_l, p.att_r, fs.nd, fs.dc_k});
+        needs_add(nd, ChanNeeds{p.decoder, p.squelch_mode, p.rds_mode, p.lo_freq, p.att_l, p.att_r, fs.nd, fs.dc_k, h->user[c].meter ? 1 : 0});
     }
     return nd;
 }
@@ -674,6 +688,8 @@ int flush_mailbox(fmx_handle h) {
     for (int c = 0; c < h->channels; c++)
         if (h->user[(size_t)c].scanning) { h->call_scan.push_back(c); h->call_scan_thr.push_back(h->user[(size_t)c].scan_thr); }
     if (!h->call_scan.empty()) { const int rc = ensure_scan(h); if (rc) return rc; }
+    if (nd.any_meter) { const int rc = ensure_meter(h); if (rc) return rc; }
+    if (h->meter_alloc) for (int c = 0; c < h->channels; c++) h->call_meter[(size_t)c] = h->user[(size_t)c].meter ? 1 : 0;
     // (a channel's RDS path runs while its decoder is on and stands still otherwise -- block filters, phase delay line, decimator and slicer
     // keep what they hold, as the reference's processor's do: nothing restarts when a decoder is switched; run_piece counts per channel)
     if (nd.any_rds) { const int rc = ensure_rds(h); if (rc) return rc; }
@@ -921,6 +937,35 @@ int stage_scan(fmx_handle h, const CallGeom &G, hipStream_t sa) {
     return FMX_OK;
 }
 
+// the modulation meter: the metered channels' rows of the piece into their lane accumulators, every window that ends in it into the record ring
+// (fmx_meter.hip), on the stream stage B ran on and behind it, where stage_rds reads the same rows.  The bookkeeping is the host's (meter_produce); the
+// kernel gets one job per channel that accumulates.
+int stage_meter(fmx_handle h, const CallGeom &G, hipStream_t s) {
+    const int64_t nj = G.J1 - G.J0;
+    if (nj > h->work_nj) return fail(FMX_E_TOO_LARGE, "the piece has more fm samples than stage B's rows hold");
+    h->meter_jobs.clear();
+    {
+        std::lock_guard<std::mutex> lk(h->mtx);      // (fmx_mod_records reads the counters from any thread)
+        for (int c = 0; c < h->channels; c++) {
+            if (!h->call_meter[(size_t)c]) { h->meter_on_from[(size_t)c] = -1; continue; }      // (off: the window in progress is dropped)
+            if (h->meter_on_from[(size_t)c] < 0) h->meter_on_from[(size_t)c] = G.J0;
+            const meter::Produce mp = meter::meter_produce(h->meter_on_from[(size_t)c], G.J0, nj, h->meter_produced[(size_t)c]);
+            if (mp.first >= G.J1) continue;
+            h->meter_jobs.push_back(MeterJob{c, (int32_t)(mp.first - G.J0), (int32_t)mp.slot(0), 0});
+            h->meter_produced[(size_t)c] = mp.new_produced;
+        }
+    }
+    const size_t n = h->meter_jobs.size();
+    if (n == 0) return FMX_OK;
+    // (pageable source: the copy is staged before the call returns)
+    HIPCHK(hipMemcpyAsync(h->d_meter_jobs, h->meter_jobs.data(), sizeof(MeterJob) * n, hipMemcpyHostToDevice, s));
+    MeterArgs A{};
+    A.jobs = h->d_meter_jobs; A.w_dem = h->B.w_dem; A.w_cur = h->B.w_cur; A.state = h->d_meter_state; A.ring = h->d_meter_ring;
+    A.J0 = G.J0; A.J1 = G.J1; A.lin_rows = h->B.lin_rows;
+    launch_meter(A, (int)n, s); FMX_LAUNCHED();
+    return FMX_OK;
+}
+
 // the scanning channels' frames of the call are zeros (their chain runs on: outside the scanning calls a channel is what it would have been)
 int stage_scan_mute(fmx_handle h, float2 *d_pcm, int64_t pcm_stride, int64_t frames, hipStream_t s) {
     const size_t n = h->call_scan.size();
@@ -1009,6 +1054,7 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     h->last_second_group = second;
     if ((rc = stage_b(h, G, k, piped, second, s, sa))) return rc;
     if (rds_running && (rc = stage_rds(h, G, s))) return rc;
+    if (h->meter_alloc && G.J1 > G.J0 && (rc = stage_meter(h, G, s))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[2], s));
     if ((rc = stage_c(h, G, d_pcm, frames, second, s))) return rc;
     if (!h->call_scan.empty() && frames > 0 && (rc = stage_scan_mute(h, d_pcm, G.pcm_stride, frames, s))) return rc;
@@ -1429,6 +1475,15 @@ int fmx_set_param(fmx_handle h, int32_t channel, int32_t id, double value) {
         refresh_derived(h, c);
     }
     h->params_dirty = true;
+    return FMX_OK;
+}
+
+int fmx_mod_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
+    if (!h) return fail(FMX_E_INVALID, "null handle");
+    if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
+    std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
+    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
+    for (int c = c0; c < c1; c++) h->user[(size_t)c].meter = on != 0;
     return FMX_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "../../include/fmx_debug.h"
 #include "fmx_internal.h"
 #include "fmx_scan.h"
+#include "fmx_meter.h"
 #include "fmx_rdsgroups.h"
 
 #include <algorithm>
@@ -89,6 +90,7 @@ struct ChanUser {
     // scan mode (FMX_P_SCANNING, FMX_P_SCAN_THRESHOLD): startScanning / stopScanning, the constructor's thresHold (fm-processor.cpp:63,108,361-367)
     bool    scanning = false;
     int16_t scan_thr = 20;
+    bool    meter = false;       // the modulation meter (fmx_mod_meter_enable)
 };
 
 struct ProfRec { hipEvent_t e[4]; int64_t in_samples, ch_samples; int n; };
@@ -107,11 +109,12 @@ struct Readers {
     std::vector<int64_t> dec_groups;         // fmx_rds_decode_all: groups of RdsSyncChan::groups
     std::vector<int64_t> groups;             // fmx_rds_groups: the same count
     std::vector<int64_t> scan;               // fmx_scan_results: blocks of fmx_handle_s::scan_blocks
+    std::vector<int64_t> mod;                // fmx_mod_records: records of fmx_handle_s::meter_produced
     std::vector<uint8_t> reset_dec, reset_dec_all;   // resetRds / triggerFrequencyChange asked for the group decoder's reset: fmx_rds_decode's, fmx_rds_decode_all's (under mtx)
     std::vector<RdsGroupDecoderHost> dec, dec_all;   // fmx_rds_decode's decoders (the synchroniser on the host), fmx_rds_decode_all's (on the GPU: rds_sync)
     void init(size_t channels) {
         peaks.assign(channels, 0); bits.assign(channels, 0); dec_bits.assign(channels, 0); symbols.assign(channels, 0);
-        dec_groups.assign(channels, 0); groups.assign(channels, 0); scan.assign(channels, 0);
+        dec_groups.assign(channels, 0); groups.assign(channels, 0); scan.assign(channels, 0); mod.assign(channels, 0);
         reset_dec.assign(channels, 0); reset_dec_all.assign(channels, 0);
     }
 };
@@ -186,6 +189,14 @@ struct fmx_handle_s {
     float2 *d_scan_W = nullptr, *d_scan_carry = nullptr, *d_scan_rec = nullptr; ScanJob *d_scan_jobs = nullptr; int32_t *d_scan_mute = nullptr;
     std::vector<ScanJob> scan_jobs;
     std::vector<int32_t> scan_fill; std::vector<int64_t> scan_blocks, scan_end; std::vector<int16_t> scan_rec_thr;
+    // the modulation meter (fmx_meter.hip, fmx_meter.h): the channels whose meter is on in the piece being made (flush_mailbox); per channel the fm sample
+    // since which its meter has been on in every piece (-1: off) and the records it has completed since fmx_create; the device keeps the lane accumulators
+    // of the window in progress and the record ring; allocated by the first call in which a meter is on
+    std::vector<uint8_t> call_meter;
+    bool meter_alloc = false;
+    float *d_meter_state = nullptr; fmx_mod_record *d_meter_ring = nullptr; MeterJob *d_meter_jobs = nullptr;
+    std::vector<MeterJob> meter_jobs;
+    std::vector<int64_t> meter_on_from, meter_produced;
     std::atomic<int> stageb_form{0};     // FMX_P_STAGEB_FORM
     std::atomic<int> front_parts{0};     // FMX_P_FRONT_PARTS
     std::atomic<int> front_kernel{0};    // FMX_P_FRONT_KERNEL

@@ -421,6 +421,19 @@ void launch_scan(const ScanArgs &A, int n_jobs, hipStream_t s);
 // zeroes frames [0, frames) of the channels chans [0 .. n - 1] at pcm + ch * pcm_stride
 void launch_scan_mute(const int32_t *chans, int n, float2 *pcm, int64_t pcm_stride, int64_t frames, hipStream_t s);
 
+// ---- the modulation meter (fmx_meter.hip, fmx_meter.h) ------------------------------------------------------------------
+// one metered channel of a piece: the first of the piece's rows it accumulates, and the ring slot its first completed window goes to
+struct MeterJob { int32_t ch, r0, slot0, pad; };
+struct MeterArgs {
+    const MeterJob *jobs;         // [n_jobs] (copied per piece on the stream of the launch)
+    const float *w_dem, *w_cur;   // stage B's rows of this piece: fm sample J0 + r of channel ch at ch * lin_rows + r
+    float *state;                 // [channels][meter::QUANT][meter::LANES] the lane accumulators of the window in progress
+    fmx_mod_record *ring;         // [channels][meter::RING]
+    int64_t J0, J1;               // the piece's fm samples
+    int32_t lin_rows, pad;
+};
+void launch_meter(const MeterArgs &A, int n_jobs, hipStream_t s);
+
 // ---- stage W: wide-band ingest (fmx_wide.hip; DESIGN.md "Stage W") ----------------------------------------------------------
 // One stream at K * 2 304 000 S/s feeds many outputs at 2 304 000 S/s: per-sample mix, T = 16 K + 1 real taps, / K.
 constexpr int W_RATE0 = 2304000;       // the narrow rate, and the circle of the output rotator's table

@@ -1,5 +1,5 @@
 // fmx_readout.hip -- the entry points of include/fmx.h that only read a handle: metaData, peak levels, scope taps, tap sets, the RDS bits, symbols, groups
-// and decoders, scan records, the PLL counters, the facts about the last call; and the host-only RDS helpers.  A per-channel read-out waits for the device,
+// and decoders, scan records, the modulation meter's records, the PLL counters, the facts about the last call; and the host-only RDS helpers.  A per-channel read-out waits for the device,
 // asks its ring's producer for the count, and takes [from, from + count) out of one copy of the ring (read_ring); where each reader stands is in the
 // handle's Readers (fmx_host.h).  The two batch RDS read-outs wait for the handle's last call only and copy every channel's ring at once (rds_batch_fetch).
 #include "fmx_host.h"
@@ -28,14 +28,21 @@ int fetch_rds_state(fmx_handle h, int channel, RdsState *st) {
     return FMX_OK;
 }
 
-// The items [t.from, t.from + t.count) of a channel's ring of `ring` entries at d_ring, oldest first: visit (k, item) for k = 0 .. t.count - 1, out of one
-// copy of the ring.  Nothing is copied when there is nothing to take.
-template <class T, class F> int read_ring(const T *d_ring, int ring, RingTake t, F &&visit) {
-    if (t.count <= 0) return FMX_OK;
-    std::vector<T> items((size_t)ring);
-    HIPCHK(hipMemcpy(items.data(), d_ring, sizeof(T) * (size_t)ring, hipMemcpyDeviceToHost));
-    for (int64_t k = 0; k < t.count; k++) visit(k, items[(size_t)ring_slot(t.from + k, ring)]);
+// The rings of `n` consecutive channels, `ring` entries each, at d_rings: of channel k the items [takes [k].from, takes [k].from + takes [k].count), oldest
+// first: visit (k, i, item) for i = 0 .. count - 1, out of ONE copy of the rings.  Nothing is copied when there is nothing to take.
+template <class T, class F> int read_rings(const T *d_rings, int ring, int n, const RingTake *takes, F &&visit) {
+    bool any = false;
+    for (int k = 0; k < n; k++) any |= takes[k].count > 0;
+    if (!any) return FMX_OK;
+    std::vector<T> items((size_t)ring * (size_t)n);
+    HIPCHK(hipMemcpy(items.data(), d_rings, sizeof(T) * items.size(), hipMemcpyDeviceToHost));
+    for (int k = 0; k < n; k++)
+        for (int64_t i = 0; i < takes[k].count; i++) visit(k, i, items[(size_t)k * (size_t)ring + (size_t)ring_slot(takes[k].from + i, ring)]);
     return FMX_OK;
+}
+// ... of one channel: visit (i, item)
+template <class T, class F> int read_ring(const T *d_ring, int ring, RingTake t, F &&visit) {
+    return read_rings(d_ring, ring, 1, &t, [&](int, int64_t i, const T &item) { visit(i, item); });
 }
 
 // fmx_pll_replays / fmx_pll_exact_segments: a counter of ChanState, of one channel or (channel < 0) summed over all
@@ -208,6 +215,42 @@ int fmx_scan_results(fmx_handle h, int32_t channel, fmx_scan_result *out, int32_
     }));
     h->rd.scan[c] = t.next();
     *n_results = (int32_t)t.count;
+    return FMX_OK;
+}
+
+int fmx_mod_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_mod_record *out, int32_t capacity_per_channel, int32_t *n_records) {
+    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || capacity_per_channel < 0 ||
+        (n_channels > 0 && (!n_records || (capacity_per_channel > 0 && !out)))) return fail(FMX_E_INVALID, "bad argument");
+    for (int k = 0; k < n_channels; k++) n_records[k] = 0;
+    if (n_channels == 0 || !h->meter_alloc) return FMX_OK;
+    FMXCHK(device_idle(h));
+    std::lock_guard<std::mutex> lk(h->mtx);
+    std::vector<RingTake> takes((size_t)n_channels);
+    for (int k = 0; k < n_channels; k++) {
+        const size_t c = (size_t)(first_channel + k);
+        takes[(size_t)k] = ring_take(h->meter_produced[c], h->rd.mod[c], meter::RING, capacity_per_channel);      // (a reader that fell behind: the gap shows in `index`)
+    }
+    FMXCHK(read_rings(h->d_meter_ring + (size_t)first_channel * meter::RING, meter::RING, n_channels, takes.data(),
+                      [&](int k, int64_t i, const fmx_mod_record &r) { out[(size_t)k * (size_t)capacity_per_channel + (size_t)i] = r; }));
+    for (int k = 0; k < n_channels; k++) { h->rd.mod[(size_t)(first_channel + k)] = takes[(size_t)k].next(); n_records[k] = (int32_t)takes[(size_t)k].count; }
+    return FMX_OK;
+}
+
+// Hz per unit of the demodulator output, in the reference's own float order: fm_Demodulator's constructor (fm-demodulator.cpp:58-64) makes K_FM of three
+// floats, demodulate () ends in res = 20 (r - afc) / K_FM (:198); r radians per sample are r fmRate / (2 pi) Hz
+int fmx_mod_hz_per_unit(int32_t decoder, int32_t fmRate, double *hz) {
+    if (!hz || fmRate < 1) return fail(FMX_E_INVALID, "bad argument");
+    switch (decoder) {
+    case 2: case 3: case 4: break;      // pllC's phaseIncr (NcoPhase += phaseIncr, pllC.cpp:80-84), the two atan2 discriminators (:169-175)
+    case 1: return fail(FMX_E_UNSUPPORTED, "the AM decoder's output is the carrier's relative amplitude, not a frequency");
+    case 5: return fail(FMX_E_UNSUPPORTED, "the RealBB decoder's value is half the arcsine of sin (phase step) from a table (fm-demodulator.cpp:180-186): linear in frequency only for small deviations");
+    case 6: return fail(FMX_E_UNSUPPORTED, "the Diff decoder's value is a difference quotient over two samples divided by sqrt (2) (fm-demodulator.cpp:190-191), not an angle per sample");
+    default: return fail(FMX_E_INVALID, "decoder must be 1..6");
+    }
+    const float F_G = (float)(0.65 * fmRate / 2), Delta_F = (float)(0.95 * fmRate / 2);
+    const float B_FM = 2 * (Delta_F + F_G);
+    const float K_FM = (float)((double)(2 * B_FM) * design::kPi / (double)F_G);
+    *hz = (double)K_FM / 20.0 * (double)fmRate / (2.0 * design::kPi);
     return FMX_OK;
 }
 

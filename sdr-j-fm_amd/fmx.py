@@ -39,7 +39,7 @@ EXPORTS = [
     "fmx_abi_version", "fmx_last_error", "fmx_create", "fmx_destroy", "fmx_set_param", "fmx_frames_for", "fmx_filter_change_due",
     "fmx_process_host", "fmx_process_device", "fmx_process_host_raw", "fmx_process_device_raw", "fmx_synchronize",
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
-    "fmx_scan_results", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
+    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
     "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
     "fmx_wideband_survey_enable", "fmx_wideband_survey_read", "fmx_wideband_survey_stations",
     "fmx_wideband_create_rate", "fmx_wideband_outputs_for", "fmx_wideband_rate_taps", "fmx_wideband_survey_stations_rate",
@@ -122,6 +122,18 @@ SCAN_DTYPE = np.dtype([("block", np.int64), ("end_sample", np.int64), ("signal_d
 assert SCAN_DTYPE.itemsize == C.sizeof(FmxScanResult)
 
 
+class FmxModRecord(C.Structure):
+    _fields_ = [("index", C.c_int64), ("end_sample", C.c_int64), ("peak_pos", C.c_float), ("peak_neg", C.c_float), ("mean", C.c_float),
+                ("mean_square", C.c_float), ("pilot_i", C.c_float), ("pilot_q", C.c_float)]
+
+
+# fmx_mod_record as a numpy record (Fmx.mod_records)
+MOD_DTYPE = np.dtype([("index", np.int64), ("end_sample", np.int64), ("peak_pos", np.float32), ("peak_neg", np.float32), ("mean", np.float32),
+                      ("mean_square", np.float32), ("pilot_i", np.float32), ("pilot_q", np.float32)])
+assert MOD_DTYPE.itemsize == C.sizeof(FmxModRecord)
+MOD_WINDOW = 9600             # fm samples per record: 50 ms
+
+
 class FmxRdsGroup(C.Structure):
     _fields_ = [("index", C.c_int64), ("end_bit", C.c_int64), ("block", C.c_uint16 * 4)]
 
@@ -195,6 +207,12 @@ def load_library(path=None):
     L.fmx_rds_prepare_text.argtypes = [C.POINTER(C.c_uint8), i32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), i32]
     L.fmx_scan_results.restype = C.c_int
     L.fmx_scan_results.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
+    L.fmx_mod_meter_enable.restype = C.c_int
+    L.fmx_mod_meter_enable.argtypes = [vp, i32, i32]
+    L.fmx_mod_records.restype = C.c_int
+    L.fmx_mod_records.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
+    L.fmx_mod_hz_per_unit.restype = C.c_int
+    L.fmx_mod_hz_per_unit.argtypes = [i32, i32, C.POINTER(C.c_double)]
     L.fmx_rds_bits.restype = C.c_int
     L.fmx_rds_bits.argtypes = [vp, i32, C.POINTER(C.c_uint8), i32, C.POINTER(i32)]
     L.fmx_rds_symbols.restype = C.c_int
@@ -263,6 +281,17 @@ def rds_decode_bits(bits):
     if rc != FMX_OK:
         raise FmxError(rc, L.fmx_last_error().decode())
     return info
+
+
+def mod_hz_per_unit(decoder=3, fmRate=192000):
+    """Hz per unit of the demodulator output, and so of the modulation meter's records, for a decoder (include/fmx.h fmx_mod_hz_per_unit; host only,
+    needs no device).  Raises FmxError (FMX_E_UNSUPPORTED) for the decoders whose output is no frequency."""
+    L = load_library()
+    hz = C.c_double()
+    rc = L.fmx_mod_hz_per_unit(int(decoder), int(fmRate), C.byref(hz))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
+    return hz.value
 
 
 class Fmx:
@@ -372,6 +401,20 @@ class Fmx:
         n = C.c_int32()
         self._check(self.L.fmx_scan_results(self.h, channel, out.ctypes.data, capacity, C.byref(n)))
         return out[:n.value].copy()
+
+    def mod_meter(self, on=True, channel=-1):
+        """Switch the modulation meter of a channel (-1: of every channel) on or off, from the next call on (fmx_mod_meter_enable)."""
+        self._check(self.L.fmx_mod_meter_enable(self.h, int(channel), 1 if on else 0))
+
+    def mod_records(self, first=0, count=None, capacity=64):
+        """The modulation meter's records since the last read, per channel of the range, oldest first (fmx_mod_records): a list of numpy structured
+        arrays (MOD_DTYPE: index, end_sample, peak_pos, peak_neg, mean, mean_square, pilot_i, pilot_q), one per 50 ms window, in the demodulator's
+        units (mod_hz_per_unit).  The library keeps the last 64 per channel."""
+        count = self.channels - first if count is None else count
+        out = np.zeros((max(count, 1), max(capacity, 1)), MOD_DTYPE)
+        n = (C.c_int32 * max(count, 1))()
+        self._check(self.L.fmx_mod_records(self.h, first, count, out.ctypes.data, capacity, n))
+        return [out[k, :n[k]].copy() for k in range(count)]
 
     def rds_bits(self, channel=0, capacity=8192):
         buf = (C.c_uint8 * capacity)()
@@ -670,6 +713,12 @@ class FmProcessor:
     def pollScanResults(self):
         """The scan records since the last poll; the reference emits scanresult () for each with `found` set."""
         return self.fmx.scan_results(self.channel)
+
+    def setModulationMeter(self, on): self.fmx.mod_meter(on, self.channel)
+
+    def pollModulation(self):
+        """The modulation meter's records since the last poll (MOD_DTYPE): peak deviation, multiplex power and pilot per 50 ms window."""
+        return self.fmx.mod_records(self.channel, 1)[0]
 
     def isPilotLocked(self):
         m = self.fmx.meta(self.channel)
