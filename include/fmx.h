@@ -435,6 +435,59 @@ int  fmx_mod_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fm
  * half angle of a sine, no linear scale) and 6 (Diff: a difference quotient, no angle). */
 int  fmx_mod_hz_per_unit(int32_t decoder, int32_t fmRate, double *hz);
 
+/* ---- the programme audio meter: what a broadcast monitor reports of the PROGRAMME -- loudness (ITU-R BS.1770-4 / EBU R 128), level,
+ * silence, a lost ear, an out-of-phase stereo signal -- as one 48-byte record per channel and 100 ms window, computed on the GPU from the PCM the call
+ * delivers, so that the PCM itself can stay on the device.
+ *
+ * Input: the channel's PCM, exactly the values the call delivers (a scanning channel's zeros included).  Frame m counts the handle's PCM frames since
+ * fmx_create (fmx_meta.pcm_frames).  Window w is the frames [4800 w, 4800 (w + 1)), 100 ms, the gating step of BS.1770; every channel shares the grid.
+ * Each (channel, ear) is one sequential machine, run in frame order in IEEE f32 with subnormals and without contraction into fma; its states start at
+ * zero in the piece of a call that switches the meter on, as if the programme had been silent before.  Per frame, x the ear's sample:
+ *     pk = max (pk, |x|)         s2 += f32 (x x)
+ *     for the two K-weighting sections in turn (transposed direct form II), v = x for the first and v = the first's o for the second:
+ *         o = f32 (b0 v) + t1      t1 = f32 (f32 (b1 v) - f32 (a1 o)) + t2      t2 = f32 (b2 v) - f32 (a2 o)
+ *     z += f32 (o o)   (o of the second section)          left ear only: sx += f32 (xL xR)
+ * with BS.1770-4's 48 kHz coefficients rounded to f32:
+ *     section 1: b 1.53512485958697, -2.69169618940638, 1.19839281085285;  a1 -1.69065929318241, a2 0.73248077421585
+ *     section 2: b 1.0, -2.0, 1.0;                                          a1 -1.99004745483398, a2 0.99007225036621
+ * At a window's end: peak = pk, ms = s2 / 4800.0f, kms = z / 4800.0f, cross = sx / 4800.0f; pk, s2, z and sx start again at 0, the filter states run on.
+ * What a channel carries between calls is 16 floats and no sample: on the same PCM the records are the same bit for bit however the stream is cut into
+ * calls, or a call into pieces.  (The PCM itself depends on the cut in its last bits: DESIGN.md 4.12.)
+ * Window w of a channel leaves a record only if the channel's meter was on in every piece that covered one of its frames: the filters run from the first
+ * frame of the piece that switched the meter on, accumulation starts at the first window boundary at or behind it; switching off drops the window in
+ * progress and the states.  The device keeps the last 64 records (6.4 s) per channel.  Everything else a handle delivers -- PCM, RDS, meta, taps, peaks,
+ * scan records, modulation records, fmx_last_second_group -- is bit for bit what it is without the meter; a handle that never switches it on allocates
+ * and launches nothing for it.  The coefficients are those of 48 000 frames/s: a handle with audioRate != 48000 answers FMX_E_UNSUPPORTED. */
+typedef struct fmx_audio_record {
+    int64_t index;        /* the window w; a gap means windows that were not metered or that the reader lost */
+    int64_t end_frame;    /* 4800 (w + 1): the PCM frame behind the window's last */
+    float   peak_l, peak_r;      /* the largest |sample| (sample peak, not true peak) */
+    float   ms_l, ms_r;          /* mean square, unweighted */
+    float   kms_l, kms_r;        /* mean square behind the K-weighting */
+    float   cross;               /* mean of left x right: cross / sqrt (ms_l ms_r) is the window's correlation */
+    int32_t reserved;            /* 0 */
+} fmx_audio_record;
+/* switches the audio meter of a channel (-1: of every channel) on or off; from any thread, takes effect at the next call */
+int  fmx_audio_meter_enable(fmx_handle h, int32_t channel, int32_t on);
+/* the records the channels first_channel .. first_channel + n_channels - 1 completed since this function last read them, oldest first, at most
+ * capacity_per_channel each (more stay for the next read): channel k's at out [k * capacity_per_channel ..], their number in n_records [k].  One
+ * read-out of the device for the whole range. */
+int  fmx_audio_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_audio_record *out, int32_t capacity_per_channel, int32_t *n_records);
+/* BS.1770-4 for two channels of weight 1 over one channel's records in order (host only, needs no device, all arithmetic in double).
+ * A block is 4 records with consecutive `index` (400 ms, 75 % overlap); a gap in `index` breaks the run.  z_j is the mean of kms_l + kms_r over block j,
+ * l_j = -0.691 + 10 log10 z_j.  momentary_lufs is the last 4 records' block, short_term_lufs the same over the last 30 records (3 s), both only if those
+ * records are consecutive; integrated_lufs is -0.691 + 10 log10 of the mean z_j over the blocks with l_j above -70 LUFS and above the relative threshold,
+ * which lies 10 LU below the level of the mean z_j of the blocks above -70 LUFS.  blocks_total counts the blocks, blocks_gated those that passed both
+ * gates.  correlation is sum cross / sqrt (sum ms_l sum ms_r) over all records, 0 where the denominator is 0; peak_dbfs_* is 20 log10 of the largest peak.
+ * A quantity with too few records, or of z = 0 (of a peak of 0), reads -HUGE_VAL. */
+typedef struct fmx_loudness {
+    double  momentary_lufs, short_term_lufs, integrated_lufs;
+    double  correlation;
+    double  peak_dbfs_l, peak_dbfs_r;
+    int64_t blocks_total, blocks_gated;
+} fmx_loudness;
+int  fmx_audio_loudness(const fmx_audio_record *recs, int32_t n, fmx_loudness *out);
+
 /* introspection used by the parity tests: the filter taps the kernels run with.
  * which: 0 front-end polyphase taps, 1 PSS low-pass, 2 audio+resampler FIR, 3 resampler alone,
  * 4 the noise squelch's two order-20 filters: [2][10] x (A1, A2, B1, B2), then the two gains (high-pass first),

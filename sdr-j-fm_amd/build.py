@@ -24,6 +24,7 @@ SOURCES = [
     ("fmx_promote.hip", ["-ffp-contract=off"]),
     ("fmx_scan.hip", []),
     ("fmx_meter.hip", ["-ffp-contract=off"]),      # (the modulation meter's sums are defined without fma: DESIGN 4.11)
+    ("fmx_loud.hip", ["-ffp-contract=off"]),       # (the audio meter's recurrences are defined without fma: DESIGN 4.12)
     ("fmx_wide.hip", []),
     ("fmx_wide_rate.hip", []),
     ("fmx_survey.hip", []),

@@ -643,6 +643,19 @@ int ensure_meter(fmx_handle h) {
     return FMX_OK;
 }
 
+// the programme audio meter's buffers (fmx_loud.hip), allocated by the first call in which a channel's audio meter is on
+int ensure_audio_meter(fmx_handle h) {
+    if (h->loud_alloc) return FMX_OK;
+    const size_t C = (size_t)h->channels;
+    HIPCHK(hipDeviceSynchronize());
+    FMXCHK(h->mem.alloc(h->d_loud_state, C * loud::STATE, true));
+    FMXCHK(h->mem.alloc(h->d_loud_ring, C * loud::RING, true));
+    FMXCHK(h->mem.alloc(h->d_loud_jobs, C));
+    h->call_loud.assign(C, 0); h->loud_on_from.assign(C, -1); h->loud_produced.assign(C, 0); h->rd.audio.assign(C, 0);
+    h->loud_alloc = true;
+    return FMX_OK;
+}
+
 // the tiled work arrays of the demodulator pre-pass (fmx_demod.hip): limited / unlimited samples in, demodulator output out.  (Allocated by the first call
 // that needs them -- before run_call decides how the call is made: a call in pieces needs them too.)
 int ensure_prepass_arrays(fmx_handle h) {
@@ -690,6 +703,9 @@ int flush_mailbox(fmx_handle h) {
     if (!h->call_scan.empty()) { const int rc = ensure_scan(h); if (rc) return rc; }
     if (nd.any_meter) { const int rc = ensure_meter(h); if (rc) return rc; }
     if (h->meter_alloc) for (int c = 0; c < h->channels; c++) h->call_meter[(size_t)c] = h->user[(size_t)c].meter ? 1 : 0;
+    // (the audio meter reads the call's PCM behind everything that writes it and asks nothing of the call's plan: it is no part of CallNeeds)
+    if (!h->loud_alloc && std::any_of(h->user.begin(), h->user.end(), [](const ChanUser &u) { return u.loud; })) { const int rc = ensure_audio_meter(h); if (rc) return rc; }
+    if (h->loud_alloc) for (int c = 0; c < h->channels; c++) h->call_loud[(size_t)c] = h->user[(size_t)c].loud ? 1 : 0;
     // (a channel's RDS path runs while its decoder is on and stands still otherwise -- block filters, phase delay line, decimator and slicer
     // keep what they hold, as the reference's processor's do: nothing restarts when a decoder is switched; run_piece counts per channel)
     if (nd.any_rds) { const int rc = ensure_rds(h); if (rc) return rc; }
@@ -974,6 +990,32 @@ int stage_scan_mute(fmx_handle h, float2 *d_pcm, int64_t pcm_stride, int64_t fra
     return FMX_OK;
 }
 
+// the programme audio meter: the metered channels' frames of the piece, as d_pcm now holds them, through their K-weighting filters and into their window
+// sums, every window that ends in the piece into the record ring (fmx_loud.hip) -- on `s`, behind both channel groups' audio kernels, the gain correction
+// and the scan mute.  The bookkeeping is the host's (audio_produce); the kernel gets one job per metered channel.
+int stage_audio_meter(fmx_handle h, const CallGeom &G, const float2 *d_pcm, int64_t frames, hipStream_t s) {
+    h->loud_jobs.clear();
+    {
+        std::lock_guard<std::mutex> lk(h->mtx);      // (fmx_audio_records reads the counters from any thread)
+        for (int c = 0; c < h->channels; c++) {
+            if (!h->call_loud[(size_t)c]) { h->loud_on_from[(size_t)c] = -1; continue; }      // (off: the window in progress and the states are dropped)
+            if (h->loud_on_from[(size_t)c] < 0) h->loud_on_from[(size_t)c] = G.M0;
+            const loud::Produce ap = loud::audio_produce(h->loud_on_from[(size_t)c], G.M0, frames, h->loud_produced[(size_t)c]);
+            h->loud_jobs.push_back(LoudJob{c, ap.first == G.M0 ? 1 : 0, (int32_t)ap.slot(0), ap.reset ? 1 : 0});
+            h->loud_produced[(size_t)c] = ap.new_produced;
+        }
+    }
+    const size_t n = h->loud_jobs.size();
+    if (n == 0) return FMX_OK;
+    // (pageable source: the copy is staged before the call returns)
+    HIPCHK(hipMemcpyAsync(h->d_loud_jobs, h->loud_jobs.data(), sizeof(LoudJob) * n, hipMemcpyHostToDevice, s));
+    LoudArgs A{};
+    A.jobs = h->d_loud_jobs; A.pcm = d_pcm; A.pcm_stride = G.pcm_stride; A.state = h->d_loud_state; A.ring = h->d_loud_ring;
+    A.M0 = G.M0; A.frames = (int32_t)frames;
+    launch_loud(A, (int)n, s); FMX_LAUNCHED();
+    return FMX_OK;
+}
+
 // stage C: the audio filter and resampler (the block machines: the audio low-pass and the de-emphasis in front of it), a gain change's correction, the
 // second converter
 int stage_c(fmx_handle h, CallGeom &G, float2 *d_pcm, int64_t frames, int second, hipStream_t s) {
@@ -1058,6 +1100,7 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     if (prof) HIPCHK(hipEventRecord(pr.e[2], s));
     if ((rc = stage_c(h, G, d_pcm, frames, second, s))) return rc;
     if (!h->call_scan.empty() && frames > 0 && (rc = stage_scan_mute(h, d_pcm, G.pcm_stride, frames, s))) return rc;
+    if (h->loud_alloc && frames > 0 && (rc = stage_audio_meter(h, G, d_pcm, frames, s))) return rc;
     if (prof) { HIPCHK(hipEventRecord(pr.e[3], s)); h->prof.push_back(pr); }
     FMX_LAUNCHED();
     HIPCHK(g_launch_err);
@@ -1484,6 +1527,17 @@ int fmx_mod_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
     const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
     for (int c = c0; c < c1; c++) h->user[(size_t)c].meter = on != 0;
+    return FMX_OK;
+}
+
+int fmx_audio_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
+    if (!h) return fail(FMX_E_INVALID, "null handle");
+    if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
+    if (h->cv_nt != 0 || h->cfg.audioRate != 48000)
+        return fail(FMX_E_UNSUPPORTED, "the audio meter's K-weighting coefficients are those of 48000 frames/s: not on a handle with another audioRate");
+    std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
+    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
+    for (int c = c0; c < c1; c++) h->user[(size_t)c].loud = on != 0;
     return FMX_OK;
 }
 

@@ -8,6 +8,7 @@
 #include "fmx_internal.h"
 #include "fmx_scan.h"
 #include "fmx_meter.h"
+#include "fmx_loud.h"
 #include "fmx_rdsgroups.h"
 
 #include <algorithm>
@@ -91,6 +92,7 @@ struct ChanUser {
     bool    scanning = false;
     int16_t scan_thr = 20;
     bool    meter = false;       // the modulation meter (fmx_mod_meter_enable)
+    bool    loud = false;        // the programme audio meter (fmx_audio_meter_enable)
 };
 
 struct ProfRec { hipEvent_t e[4]; int64_t in_samples, ch_samples; int n; };
@@ -110,11 +112,12 @@ struct Readers {
     std::vector<int64_t> groups;             // fmx_rds_groups: the same count
     std::vector<int64_t> scan;               // fmx_scan_results: blocks of fmx_handle_s::scan_blocks
     std::vector<int64_t> mod;                // fmx_mod_records: records of fmx_handle_s::meter_produced
+    std::vector<int64_t> audio;              // fmx_audio_records: records of fmx_handle_s::loud_produced
     std::vector<uint8_t> reset_dec, reset_dec_all;   // resetRds / triggerFrequencyChange asked for the group decoder's reset: fmx_rds_decode's, fmx_rds_decode_all's (under mtx)
     std::vector<RdsGroupDecoderHost> dec, dec_all;   // fmx_rds_decode's decoders (the synchroniser on the host), fmx_rds_decode_all's (on the GPU: rds_sync)
     void init(size_t channels) {
         peaks.assign(channels, 0); bits.assign(channels, 0); dec_bits.assign(channels, 0); symbols.assign(channels, 0);
-        dec_groups.assign(channels, 0); groups.assign(channels, 0); scan.assign(channels, 0); mod.assign(channels, 0);
+        dec_groups.assign(channels, 0); groups.assign(channels, 0); scan.assign(channels, 0); mod.assign(channels, 0); audio.assign(channels, 0);
         reset_dec.assign(channels, 0); reset_dec_all.assign(channels, 0);
     }
 };
@@ -197,6 +200,14 @@ struct fmx_handle_s {
     float *d_meter_state = nullptr; fmx_mod_record *d_meter_ring = nullptr; MeterJob *d_meter_jobs = nullptr;
     std::vector<MeterJob> meter_jobs;
     std::vector<int64_t> meter_on_from, meter_produced;
+    // the programme audio meter (fmx_loud.hip, fmx_loud.h): the channels whose meter is on in the piece being made (flush_mailbox); per channel the PCM
+    // frame since which its meter has been on in every piece (-1: off) and the records it has completed since fmx_create; the device keeps each channel's
+    // 16 floats and the record ring; allocated by the first call in which a meter is on (ensure_audio_meter) -- a handle that never does has none of it
+    std::vector<uint8_t> call_loud;
+    bool loud_alloc = false;
+    float *d_loud_state = nullptr; fmx_audio_record *d_loud_ring = nullptr; LoudJob *d_loud_jobs = nullptr;
+    std::vector<LoudJob> loud_jobs;
+    std::vector<int64_t> loud_on_from, loud_produced;
     std::atomic<int> stageb_form{0};     // FMX_P_STAGEB_FORM
     std::atomic<int> front_parts{0};     // FMX_P_FRONT_PARTS
     std::atomic<int> front_kernel{0};    // FMX_P_FRONT_KERNEL

@@ -434,6 +434,21 @@ struct MeterArgs {
 };
 void launch_meter(const MeterArgs &A, int n_jobs, hipStream_t s);
 
+// ---- the programme audio meter (fmx_loud.hip, fmx_loud.h) ----------------------------------------------------------------
+// one metered channel of a piece: whether the window the piece begins in has been metered from its start (it accumulates from the piece's first frame;
+// otherwise from the first window boundary in the piece), the ring slot its first completed window goes to, and whether its 16 floats start at zero
+struct LoudJob { int32_t ch, acc, slot0, reset; };
+struct LoudArgs {
+    const LoudJob *jobs;          // [n_jobs] (copied per piece on the stream of the launch)
+    const float2 *pcm;            // the piece's PCM as the call delivers it: frame M0 + f of channel ch at ch * pcm_stride + f
+    int64_t pcm_stride;
+    float *state;                 // [channels][loud::STATE]
+    fmx_audio_record *ring;       // [channels][loud::RING]
+    int64_t M0;                   // the piece's first PCM frame, counted since fmx_create
+    int32_t frames, pad;          // its frames (> 0)
+};
+void launch_loud(const LoudArgs &A, int n_jobs, hipStream_t s);
+
 // ---- stage W: wide-band ingest (fmx_wide.hip; DESIGN.md "Stage W") ----------------------------------------------------------
 // One stream at K * 2 304 000 S/s feeds many outputs at 2 304 000 S/s: per-sample mix, T = 16 K + 1 real taps, / K.
 constexpr int W_RATE0 = 2304000;       // the narrow rate, and the circle of the output rotator's table

@@ -1,6 +1,6 @@
 // fmx_readout.hip -- the entry points of include/fmx.h that only read a handle: metaData, peak levels, scope taps, tap sets, the RDS bits, symbols, groups
-// and decoders, scan records, the modulation meter's records, the PLL counters, the facts about the last call; and the host-only RDS helpers.  A per-channel read-out waits for the device,
-// asks its ring's producer for the count, and takes [from, from + count) out of one copy of the ring (read_ring); where each reader stands is in the
+// and decoders, scan records, the modulation meter's and the audio meter's records, the PLL counters, the facts about the last call; the host-only RDS
+// helpers and the host-only loudness figures (fmx_audio_loudness).  A per-channel read-out waits for the device, asks its ring's producer for the count, and takes [from, from + count) out of one copy of the ring (read_ring); where each reader stands is in the
 // handle's Readers (fmx_host.h).  The two batch RDS read-outs wait for the handle's last call only and copy every channel's ring at once (rds_batch_fetch).
 #include "fmx_host.h"
 #include "fmx_design.h"
@@ -251,6 +251,68 @@ int fmx_mod_hz_per_unit(int32_t decoder, int32_t fmRate, double *hz) {
     const float B_FM = 2 * (Delta_F + F_G);
     const float K_FM = (float)((double)(2 * B_FM) * design::kPi / (double)F_G);
     *hz = (double)K_FM / 20.0 * (double)fmRate / (2.0 * design::kPi);
+    return FMX_OK;
+}
+
+int fmx_audio_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_audio_record *out, int32_t capacity_per_channel, int32_t *n_records) {
+    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || capacity_per_channel < 0 ||
+        (n_channels > 0 && (!n_records || (capacity_per_channel > 0 && !out)))) return fail(FMX_E_INVALID, "bad argument");
+    for (int k = 0; k < n_channels; k++) n_records[k] = 0;
+    if (n_channels == 0 || !h->loud_alloc) return FMX_OK;
+    FMXCHK(device_idle(h));
+    std::lock_guard<std::mutex> lk(h->mtx);
+    std::vector<RingTake> takes((size_t)n_channels);
+    for (int k = 0; k < n_channels; k++) {
+        const size_t c = (size_t)(first_channel + k);
+        takes[(size_t)k] = ring_take(h->loud_produced[c], h->rd.audio[c], loud::RING, capacity_per_channel);      // (a reader that fell behind: the gap shows in `index`)
+    }
+    FMXCHK(read_rings(h->d_loud_ring + (size_t)first_channel * loud::RING, loud::RING, n_channels, takes.data(),
+                      [&](int k, int64_t i, const fmx_audio_record &r) { out[(size_t)k * (size_t)capacity_per_channel + (size_t)i] = r; }));
+    for (int k = 0; k < n_channels; k++) { h->rd.audio[(size_t)(first_channel + k)] = takes[(size_t)k].next(); n_records[k] = (int32_t)takes[(size_t)k].count; }
+    return FMX_OK;
+}
+
+// BS.1770-4 over one channel's records (include/fmx.h): blocks of 4 consecutive records, the absolute gate at -70 LUFS, the relative gate 10 LU below the
+// level of what passed it
+int fmx_audio_loudness(const fmx_audio_record *recs, int32_t n, fmx_loudness *out) {
+    if (!out || n < 0 || (n > 0 && !recs)) return fail(FMX_E_INVALID, "bad argument");
+    const auto lufs = [](double z) { return z > 0.0 ? -0.691 + 10.0 * std::log10(z) : -HUGE_VAL; };
+    const auto dbfs = [](double p) { return p > 0.0 ? 20.0 * std::log10(p) : -HUGE_VAL; };
+    fmx_loudness L{};
+    L.momentary_lufs = L.short_term_lufs = L.integrated_lufs = -HUGE_VAL;
+    std::vector<double> zb;                 // z_j of every block
+    double sc = 0.0, sl = 0.0, sr = 0.0, pl = 0.0, pr = 0.0;
+    int64_t run = 0;                        // records up to this one with consecutive index
+    for (int32_t i = 0; i < n; i++) {
+        run = (i > 0 && recs[i].index == recs[i - 1].index + 1) ? run + 1 : 1;
+        if (run >= 4) {
+            double z = 0.0;
+            for (int k = 3; k >= 0; k--) z += (double)recs[i - k].kms_l + (double)recs[i - k].kms_r;
+            zb.push_back(z / 4.0);
+        }
+        sc += (double)recs[i].cross; sl += (double)recs[i].ms_l; sr += (double)recs[i].ms_r;
+        pl = std::max(pl, (double)recs[i].peak_l); pr = std::max(pr, (double)recs[i].peak_r);
+    }
+    if (run >= 4) L.momentary_lufs = lufs(zb.back());
+    if (run >= 30) {
+        double z = 0.0;
+        for (int k = 29; k >= 0; k--) z += (double)recs[n - 1 - k].kms_l + (double)recs[n - 1 - k].kms_r;
+        L.short_term_lufs = lufs(z / 30.0);
+    }
+    L.blocks_total = (int64_t)zb.size();
+    double za = 0.0; int64_t na = 0;
+    for (double z : zb) if (lufs(z) > -70.0) { za += z; na++; }
+    if (na > 0) {
+        const double rel = lufs(za / (double)na) - 10.0;
+        double zg = 0.0; int64_t ng = 0;
+        for (double z : zb) if (lufs(z) > -70.0 && lufs(z) > rel) { zg += z; ng++; }
+        L.blocks_gated = ng;
+        if (ng > 0) L.integrated_lufs = lufs(zg / (double)ng);
+    }
+    const double den = std::sqrt(sl * sr);
+    L.correlation = den > 0.0 ? sc / den : 0.0;
+    L.peak_dbfs_l = dbfs(pl); L.peak_dbfs_r = dbfs(pr);
+    *out = L;
     return FMX_OK;
 }
 

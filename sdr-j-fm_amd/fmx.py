@@ -39,7 +39,7 @@ EXPORTS = [
     "fmx_abi_version", "fmx_last_error", "fmx_create", "fmx_destroy", "fmx_set_param", "fmx_frames_for", "fmx_filter_change_due",
     "fmx_process_host", "fmx_process_device", "fmx_process_host_raw", "fmx_process_device_raw", "fmx_synchronize",
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
-    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
+    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
     "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
     "fmx_wideband_survey_enable", "fmx_wideband_survey_read", "fmx_wideband_survey_stations",
     "fmx_wideband_create_rate", "fmx_wideband_outputs_for", "fmx_wideband_rate_taps", "fmx_wideband_survey_stations_rate",
@@ -134,6 +134,23 @@ assert MOD_DTYPE.itemsize == C.sizeof(FmxModRecord)
 MOD_WINDOW = 9600             # fm samples per record: 50 ms
 
 
+class FmxAudioRecord(C.Structure):
+    _fields_ = [("index", C.c_int64), ("end_frame", C.c_int64), ("peak_l", C.c_float), ("peak_r", C.c_float), ("ms_l", C.c_float), ("ms_r", C.c_float),
+                ("kms_l", C.c_float), ("kms_r", C.c_float), ("cross", C.c_float), ("reserved", C.c_int32)]
+
+
+# fmx_audio_record as a numpy record (Fmx.audio_records)
+AUDIO_DTYPE = np.dtype([("index", np.int64), ("end_frame", np.int64), ("peak_l", np.float32), ("peak_r", np.float32), ("ms_l", np.float32),
+                        ("ms_r", np.float32), ("kms_l", np.float32), ("kms_r", np.float32), ("cross", np.float32), ("reserved", np.int32)])
+assert AUDIO_DTYPE.itemsize == C.sizeof(FmxAudioRecord) == 48
+AUDIO_WINDOW = 4800           # PCM frames per record: 100 ms
+
+
+class FmxLoudness(C.Structure):
+    _fields_ = [("momentary_lufs", C.c_double), ("short_term_lufs", C.c_double), ("integrated_lufs", C.c_double), ("correlation", C.c_double),
+                ("peak_dbfs_l", C.c_double), ("peak_dbfs_r", C.c_double), ("blocks_total", C.c_int64), ("blocks_gated", C.c_int64)]
+
+
 class FmxRdsGroup(C.Structure):
     _fields_ = [("index", C.c_int64), ("end_bit", C.c_int64), ("block", C.c_uint16 * 4)]
 
@@ -211,6 +228,12 @@ def load_library(path=None):
     L.fmx_mod_meter_enable.argtypes = [vp, i32, i32]
     L.fmx_mod_records.restype = C.c_int
     L.fmx_mod_records.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
+    L.fmx_audio_meter_enable.restype = C.c_int
+    L.fmx_audio_meter_enable.argtypes = [vp, i32, i32]
+    L.fmx_audio_records.restype = C.c_int
+    L.fmx_audio_records.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
+    L.fmx_audio_loudness.restype = C.c_int
+    L.fmx_audio_loudness.argtypes = [vp, i32, C.POINTER(FmxLoudness)]
     L.fmx_mod_hz_per_unit.restype = C.c_int
     L.fmx_mod_hz_per_unit.argtypes = [i32, i32, C.POINTER(C.c_double)]
     L.fmx_rds_bits.restype = C.c_int
@@ -292,6 +315,19 @@ def mod_hz_per_unit(decoder=3, fmRate=192000):
     if rc != FMX_OK:
         raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
     return hz.value
+
+
+def loudness(records):
+    """The BS.1770-4 / EBU R 128 figures of one channel's audio-meter records in order (AUDIO_DTYPE; include/fmx.h fmx_audio_loudness; host only, needs no
+    device): a dict of momentary_lufs, short_term_lufs, integrated_lufs, correlation, peak_dbfs_l, peak_dbfs_r (float; -inf where there is too little
+    or only silence), blocks_total and blocks_gated."""
+    L = load_library()
+    recs = np.ascontiguousarray(records, AUDIO_DTYPE)
+    out = FmxLoudness()
+    rc = L.fmx_audio_loudness(recs.ctypes.data if recs.size else None, int(recs.size), C.byref(out))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
+    return {name: getattr(out, name) for name, _ in FmxLoudness._fields_}
 
 
 class Fmx:
@@ -414,6 +450,20 @@ class Fmx:
         out = np.zeros((max(count, 1), max(capacity, 1)), MOD_DTYPE)
         n = (C.c_int32 * max(count, 1))()
         self._check(self.L.fmx_mod_records(self.h, first, count, out.ctypes.data, capacity, n))
+        return [out[k, :n[k]].copy() for k in range(count)]
+
+    def audio_meter(self, on=True, channel=-1):
+        """Switch the programme audio meter of a channel (-1: of every channel) on or off, from the next call on (fmx_audio_meter_enable)."""
+        self._check(self.L.fmx_audio_meter_enable(self.h, int(channel), 1 if on else 0))
+
+    def audio_records(self, first=0, count=None, capacity=64):
+        """The audio meter's records since the last read, per channel of the range, oldest first (fmx_audio_records): a list of numpy structured arrays
+        (AUDIO_DTYPE: index, end_frame, peak_l, peak_r, ms_l, ms_r, kms_l, kms_r, cross), one per 100 ms window of the delivered PCM; loudness () turns
+        a channel's records into LUFS.  The library keeps the last 64 per channel."""
+        count = self.channels - first if count is None else count
+        out = np.zeros((max(count, 1), max(capacity, 1)), AUDIO_DTYPE)
+        n = (C.c_int32 * max(count, 1))()
+        self._check(self.L.fmx_audio_records(self.h, first, count, out.ctypes.data, capacity, n))
         return [out[k, :n[k]].copy() for k in range(count)]
 
     def rds_bits(self, channel=0, capacity=8192):
@@ -719,6 +769,12 @@ class FmProcessor:
     def pollModulation(self):
         """The modulation meter's records since the last poll (MOD_DTYPE): peak deviation, multiplex power and pilot per 50 ms window."""
         return self.fmx.mod_records(self.channel, 1)[0]
+
+    def setAudioMeter(self, on): self.fmx.audio_meter(on, self.channel)
+
+    def pollAudio(self):
+        """The audio meter's records since the last poll (AUDIO_DTYPE): peak, mean square, K-weighted mean square and cross term per 100 ms window."""
+        return self.fmx.audio_records(self.channel, 1)[0]
 
     def isPilotLocked(self):
         m = self.fmx.meta(self.channel)

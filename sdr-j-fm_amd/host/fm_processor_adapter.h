@@ -188,6 +188,15 @@ public:
         for (int32_t k = 0; k < n; k++) emit_fn(r[k]);
         return n;
     }
+    // the programme audio meter (include/fmx.h fmx_audio_records; nothing of the reference's): setAudioMeter switches it with the next block, pollAudio
+    // calls `emit_fn(const fmx_audio_record &)` once per 100 ms window completed since the last poll, oldest first (fmx_audio_loudness makes LUFS of them)
+    void setAudioMeter(bool on) { if (h) check(fmx_audio_meter_enable(h, 0, on ? 1 : 0)); }
+    template <class F> int pollAudio(F emit_fn) {
+        fmx_audio_record r[64]; int32_t n = 0;
+        if (!h || fmx_audio_records(h, 0, 1, r, 64, &n) != FMX_OK) return 0;
+        for (int32_t k = 0; k < n; k++) emit_fn(r[k]);
+        return n;
+    }
     // the RDS picture of this processor's channel(s) in one read-out of the device (fmx_rds_decode_all: the block synchroniser has run on the GPU,
     // the group decoder runs here): what the rds classes' signals carried, infos[k] for channel first + k
     bool poll_rds(fmx_rds_info *infos, int32_t first = 0, int32_t count = 1) { return h && check(fmx_rds_decode_all(h, first, count, infos)); }
