@@ -286,7 +286,9 @@ int  fmx_get_peaks(fmx_handle h, int32_t channel, float *lr_db, int32_t capacity
 /* replaces the hf/lf/iq scope ring feeds: copies the most recent n samples of a tap
  * (n * 1 or 2 floats) to host memory; n <= samples produced by the last call (fmx_last_fm_samples / fmx_last_rds_samples: while a channel
  * decodes RDS, a call of more than 31999 fm samples -- 383988 input samples at the rates the reference decimates by 12, 191994 at those it
- * decimates by 6, 31999 where it does not decimate -- is made in pieces of that length, and the taps hold the last piece) */
+ * decimates by 6, 31999 where it does not decimate -- is made in pieces of that length, and the taps at the fm rate hold the last piece.  FMX_TAP_RDS_IQ is read from a ring of 8192
+ * samples per channel and reaches back over the whole call, pieces or not: n <= fmx_last_rds_samples_of and n <= 8192 -- of a call of more than
+ * 786432 input samples only the last 8192 can be had; a larger n is FMX_E_INVALID) */
 int  fmx_get_tap(fmx_handle h, int32_t channel, int32_t tap_id, float *dst, int64_t n);
 /* What the reference's RDS classes tell the GUI through Qt signals (rds-groupdecoder.cpp:44-63, rds-blocksynchronizer.cpp:39-42):
  * setPiCode, setPTYCode, setStationLabel, setRadioText / clearRadioText, setAFDisplay, setMusicSpeechFlag, setGroup,

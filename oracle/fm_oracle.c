@@ -1090,6 +1090,7 @@ typedef struct {
     float fir[21], firbuf[21]; int firip;
     float syncBuffer[21]; int p, symbolCeiling, symbolFloor;
     float omegaRDS, bitIntegrator, bitClkPhase, prev_clkState; int previousBit, Resync;
+    float decidedOn;                                 /* (a record for fmo_rds_slicer: the integrator as the last bit found it) */
     bsync bs;
 } rds3;
 static void rds3_init(rds3 *r, int32_t rate) {
@@ -1142,6 +1143,7 @@ static int rds3_decode(rds3 *r, c32 z, c32 *m, uint8_t *d) {
     if (r->prev_clkState <= 0 && clkState > 0) {         /* rising edge -> look at the integrator */
         const int theBit = r->bitIntegrator >= 0;
         *d = (uint8_t)(theBit ^ r->previousBit);
+        r->decidedOn = r->bitIntegrator;
         r->bitIntegrator = 0;
         r->previousBit = theBit;
         res = 1;
@@ -1151,6 +1153,63 @@ static int rds3_decode(rds3 *r, c32 z, c32 *m, uint8_t *d) {
     if (res) bsync_push(&r->bs, *d);                     /* rdsDecoder::doDecode: if (b) processBit (theBit) */
     return res;
 }
+
+/* ------------------------------------------------------------------ the three slicers as an object of their own: the decoders above, unchanged,
+ * on a 24 kS/s stream given from outside (the chain feeds them its own rdsDecimator output).  Resumable: a run continues where the last one
+ * stopped, so a test can stop at every call boundary.  Per decided bit: the bit, the index of the sample it was decided on (counted from the
+ * object's first sample) and four floats, the decision variable first --
+ *   mode 2: Re o, Im o (the Costas loop's output, `*m`), the fraction mMu keeps behind the truncation, skip
+ *   mode 1: lastData, rdsSlope, lastSyncSlope, rdsMag (= lastSync behind the sample)
+ *   mode 3: bitIntegrator in front of its reset, clkState, bitClkPhase behind the sample, the synchroniser's n_sync_err */
+struct fmo_rds_slicer { int mode; long count; rds2 a; rds1 b; rds3 c; };
+fmo_rds_slicer *fmo_rds_slicer_new(int mode) {
+    if (mode < 1 || mode > 3) return NULL;
+    fmo_rds_slicer *s = (fmo_rds_slicer *)calloc(1, sizeof(*s));
+    s->mode = mode;
+    if (mode == 2) rds2_init(&s->a, 24000); else if (mode == 1) rds1_init(&s->b, 24000); else rds3_init(&s->c, 24000);
+    return s;
+}
+void fmo_rds_slicer_free(fmo_rds_slicer *s) { if (s) { if (s->mode == 3) fmo_sincos_free(s->c.sc); free(s); } }
+long fmo_rds_slicer_run(fmo_rds_slicer *s, const float *iq, long n, uint8_t *bits, int64_t *at, float *vars, long cap) {
+    long nb = 0;
+    for (long i = 0; i < n; i++, s->count++) {
+        const c32 z = C(iq[2 * i], iq[2 * i + 1]);
+        c32 m = C(0, 0); uint8_t d = 0; float v[4];
+        int got;
+        if (s->mode == 2) {
+            got = rds2_decode(&s->a, z, &m, &d);
+            v[0] = m.re; v[1] = m.im; v[2] = s->a.mMu; v[3] = (float)s->a.skip;
+        } else if (s->mode == 1) {
+            const float lastData = s->b.lastData, lastSyncSlope = s->b.lastSyncSlope;
+            got = rds1_decode(&s->b, z, &m, &d);
+            v[0] = lastData; v[1] = s->b.lastSyncSlope; v[2] = lastSyncSlope; v[3] = s->b.lastSync;
+        } else {
+            got = rds3_decode(&s->c, z, &m, &d);
+            v[0] = s->c.decidedOn; v[1] = s->c.prev_clkState; v[2] = s->c.bitClkPhase; v[3] = (float)s->c.bs.n_sync_err;
+        }
+        if (!got) continue;
+        if (nb < cap) {
+            if (bits) bits[nb] = d;
+            if (at) at[nb] = s->count;
+            if (vars) memcpy(vars + 4 * nb, v, sizeof(v));
+        }
+        nb++;
+    }
+    return nb;
+}
+/* the scalar state behind the last sample: mode 2 {AGC gain, Costas freq, Costas phase, mMu, skip, sampleCount}; mode 1 {Costas freq, Costas
+ * phase, lastSync}; mode 3 {Costas freq, Costas phase, bitClkPhase, n_sync_err, synced}; returns the number of fields */
+int fmo_rds_slicer_state(const fmo_rds_slicer *s, float *out) {
+    if (s->mode == 2) {
+        out[0] = s->a.agc.gain; out[1] = s->a.costas.freq; out[2] = s->a.costas.phase; out[3] = s->a.mMu;
+        out[4] = (float)s->a.skip; out[5] = (float)s->a.sampleCount;
+        return 6;
+    }
+    if (s->mode == 1) { out[0] = s->b.costas.freq; out[1] = s->b.costas.phase; out[2] = s->b.lastSync; return 3; }
+    out[0] = s->c.costas.freq; out[1] = s->c.costas.phase; out[2] = s->c.bitClkPhase; out[3] = (float)s->c.bs.n_sync_err; out[4] = (float)s->c.bs.synced;
+    return 5;
+}
+long fmo_rds_slicer_samples(const fmo_rds_slicer *s) { return s->count; }
 
 typedef struct { float *buf; long cap, n; } tapbuf;
 

@@ -143,6 +143,14 @@ float fmo_iir_pass(fmo_iir *f, float v);
 void  fmo_bsync_run(const uint8_t *bits, long n, int32_t *sync_errors, int32_t *synced);
 /* rdsDecoder_1's constants as the kernels hold them: rdsFilter taps [21], Match kernel [43], sharpFilter [8][A1 A2 B1 B2], gain */
 void  fmo_rds1_coeffs(float *out);
+/* rdsDecoder_1 / _2 / _3 (mode) on a 24 kS/s stream of its own, resumable from run to run; per decided bit the bit, the index of the sample it
+ * was decided on and four floats (decision variable first; see fm_oracle.c); _run returns the bits this run decided, of which it wrote up to cap */
+typedef struct fmo_rds_slicer fmo_rds_slicer;
+fmo_rds_slicer *fmo_rds_slicer_new(int mode);
+void  fmo_rds_slicer_free(fmo_rds_slicer *);
+long  fmo_rds_slicer_run(fmo_rds_slicer *, const float *iq, long n, uint8_t *bits, int64_t *at, float *vars, long cap);
+int   fmo_rds_slicer_state(const fmo_rds_slicer *, float *out /* [6] */);
+long  fmo_rds_slicer_samples(const fmo_rds_slicer *);
 /* test helpers with the signatures of ref_iir_* (kind 0 low-pass, 1 high-pass, 2 band-pass) */
 /* squelch (squelchClass.cpp:11-113): state + the calls fmProcessor makes (fm-processor.cpp:87, 410-413, 499-509) */
 typedef struct { float noiseThr, levelThr, avgHigh, avgLow; int32_t hold, rate, count, suppress; fmo_iir high, low; } fmo_squelch;

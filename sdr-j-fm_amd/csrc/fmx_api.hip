@@ -1147,12 +1147,18 @@ int run_call(fmx_handle h, const void *d_iq, int32_t fmt, float s16_den, int64_t
     const CallArgs a{fmt, s16_den, stream_stride, pcm_stride};
     const int64_t bps = bytes_per_sample(fmt);
     int64_t pos = 0, total = 0;
+    const bool rds_pieces = plan.lens.size() > 1 && cs.any_rds;   // (only a call that decodes RDS pays for the copy)
+    std::vector<int64_t> nc_before;                               // every channel's own count of fm samples in front of such a call
+    if (rds_pieces) nc_before = h->rds_alloc ? h->rds_nc : std::vector<int64_t>((size_t)h->channels, 0);
     for (size_t k = 0; k < plan.lens.size(); k++) {
         int64_t got = 0;
         rc = run_piece(h, a, reinterpret_cast<const char *>(d_iq) + pos * bps, plan.lens[k], d_pcm + total, ps, (int)k, overlapped, &got);
         if (rc) { if (overlapped) (void)hipDeviceSynchronize(); return rc; }
         pos += plan.lens[k]; total += got;
     }
+    // fmx_last_rds_samples_of counts the CALL's outputs: stage_rds has left the last piece's (a call in pieces gave 1209 of its 5208)
+    for (size_t c = 0; rds_pieces && h->rds_alloc && c < nc_before.size(); c++)
+        if (h->rds_nc[c] != nc_before[c]) { h->last_m0[c] = nc_before[c] / 8; h->last_m1[c] = h->rds_nc[c] / 8; }
     if (overlapped) {
         HIPCHK(hipEventRecord(h->pipe_evE, h->pipe_sB)); HIPCHK(hipStreamWaitEvent(s, h->pipe_evE, 0));
         h->last_pieces = (int)plan.lens.size();

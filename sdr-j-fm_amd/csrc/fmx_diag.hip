@@ -99,6 +99,27 @@ int fmx_debug_phase_cycles(fmx_handle h, int32_t enable, unsigned long long *out
     return FMX_OK;
 }
 
+// diagnostics (include/fmx_debug.h): the scalar state of a channel's RDS slicers behind the handle's last call, a plain copy (no launch)
+int fmx_debug_rds_state(fmx_handle h, int32_t channel, float *out, int32_t capacity, int32_t *n) {
+    if (!h || !out || !n || channel < 0 || channel >= h->channels || capacity < FMX_DEBUG_RDS_STATE_FIELDS) return fail(FMX_E_INVALID, "bad argument");
+    *n = 0;
+    if (!h->rds_alloc) return FMX_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipDeviceSynchronize());
+    RdsState s2; Rds1State s1; Rds3State s3;
+    HIPCHK(hipMemcpy(&s2, h->R.state + channel, sizeof(s2), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&s1, h->R.state1 + channel, sizeof(s1), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&s3, h->R.state3 + channel, sizeof(s3), hipMemcpyDeviceToHost));
+    const float v[FMX_DEBUG_RDS_STATE_FIELDS] = {
+        (float)h->params[channel].rds_mode, (float)s2.nbits,
+        s2.gain, s2.c_freq, s2.c_phase, s2.mu, (float)s2.skip, (float)s2.sample_count,
+        s1.c_freq, s1.c_phase, s1.last_sync,
+        s3.c_freq, s3.c_phase, s3.bit_clk_phase, (float)s3.bs_sync_err, (float)s3.bs_synced };
+    std::memcpy(out, v, sizeof(v));
+    *n = FMX_DEBUG_RDS_STATE_FIELDS;
+    return FMX_OK;
+}
+
 int fmx_profile_enable(fmx_handle h, int32_t on) {
     if (!h) return fail(FMX_E_INVALID, "null handle");
     h->prof_on = on != 0;

@@ -320,15 +320,19 @@ __global__ void rds_matched(DeviceBuffers B, RdsBuffers Rb, int nj) {
 // three AGC outputs, and nothing of it feeds back into the AGC.  One lane per channel walking the samples with the symbol branch
 // inside -- round 1 / 2 -- made a wave pay for the branch at nearly every sample (64 lanes at unrelated symbol phases: some lane
 // is in it 96 % of the time; 0.87 ms per call at 2048 channels on 32 waves).  Two kernels instead:
-//   rds_agc      the AGC (agc.h:14-18) of every sample, in place in mfc: a workgroup per channel, the gain by a scan (see there);
+//   rds_agc      the AGC (agc.h:14-18) of every sample, in place in mfc: a workgroup per channel, the gain walked by one lane from LDS (see there);
 //   rds_symbols  lane per channel over the SYMBOLS: the sample a symbol falls on follows from the skip count in closed form
 //                (`++sampleCount >= skipNrSamples`), so a lane jumps from symbol to symbol and every lane is in the branch together.
 constexpr int AGC_T = 256, AGC_K = 10;                         // threads per channel, samples per thread (2400 outputs per 0.1 s call)
 __global__ __launch_bounds__(AGC_T) void rds_agc(DeviceBuffers B, RdsBuffers Rb, int C, int nj) {
     // AGC (2e-3, 0.38, start 9), agc.h:14-18: out = in * gain; gain += rate * (ref - |out|).  |out| = |in * gain| is taken as gain * |in|
-    // with |in| from rds_matched (the same value to an ulp), which makes the gain an AFFINE recurrence, gain' = gain (1 - rate |in|) +
-    // rate ref: one workgroup per channel, every thread composes the maps of its AGC_K adjacent samples in f64, a scan over the
-    // workgroup gives the gain in front of each thread, and the thread then runs its own samples in the reference's f32 expression.
+    // with |in| from rds_matched (the same value to an ulp), so the gain needs nothing but the magnitudes: one workgroup per channel
+    // loads a round's magnitudes into LDS -- coalesced --, ONE lane walks them through the reference's f32 expression and leaves the gain
+    // in front of each thread's AGC_K samples, and every thread then runs its own samples, in the same expression.
+    // The recurrence is f32 and must stay f32: while the baseband is zero (the block filters' latency, 8000 samples) every step adds
+    // rate * ref = 7.6e-4 to a gain between 9 and 15 and rounds by the SAME fraction of an ulp -- the reference's gain runs away from the
+    // exact sum by 6.5e-4 (4.3e-5 of the gain), which moved every symbol of the pull-in by up to 1.5e-4 of the peak while an f64 scan of
+    // affine maps stood here (tests/test_gpu_rds_slicers.py).
     // (Lane per channel over the samples -- the first form of this kernel -- had 64 lanes walking 64 rows in 64 different pages:
     // 0.16-0.2 ms per call at 2048 channels, all of it address translation and load latency.)
     const int ch = blockIdx.x;
@@ -337,43 +341,50 @@ __global__ __launch_bounds__(AGC_T) void rds_agc(DeviceBuffers B, RdsBuffers Rb,
     if (nc0 < 0) return;
     const int64_t m0 = nc0 / 8; const int nout = (int)((nc0 + nj) / 8 - m0);          // the channel's own 24 kS/s outputs of this call
     (void)m0;
-    __shared__ double sA[4], sB[4];
+    __shared__ float sAbs[AGC_T * AGC_K];                          // |in| of the round's samples
+    __shared__ float sG[AGC_T];                                    // the gain in front of each thread's samples
     __shared__ float2 sLast[3];
     __shared__ float sGain;                                        // the gain behind a round of AGC_T * AGC_K samples
     RdsState *sp = Rb.state + ch;
     const float g0 = sp->gain;
     float2 *row = Rb.mfc + (size_t)ch * Rb.mfc_stride;
     const float *mrow = Rb.mfm + (size_t)ch * Rb.mfc_stride + 2;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const float2 p0 = sp->sb0, p1 = sp->sb1, p2 = sp->sb2;
     __syncthreads();                                               // (everybody has read the state the last thread rewrites below)
     if (tid == 0) { row[0] = p1; row[1] = p2; }                   // what the first symbols of this call may look back at
     for (int base = 0; base < nout; base += AGC_T * AGC_K) {       // (one round for calls of up to 2560 outputs)
         const int q0 = base + tid * AGC_K;
         float a[AGC_K]; float2 x[AGC_K];
-        double A = 1.0, Bv = 0.0;
 #pragma unroll
         for (int i = 0; i < AGC_K; i++) {
             const bool ok = q0 + i < nout;
             a[i] = ok ? mrow[q0 + i] : 0.f; x[i] = ok ? row[2 + q0 + i] : make_float2(0.f, 0.f);
-            if (ok) { const double m = 1.0 - (double)2e-3f * (double)a[i]; A *= m; Bv = Bv * m + (double)2e-3f * (double)0.38f; }
+            sAbs[tid * AGC_K + i] = a[i];
         }
-        // inclusive scan of the maps g -> A g + B over the wave, then over the four waves
-        double cA = A, cB = Bv;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const double pA = __shfl_up(cA, o, 64), pB = __shfl_up(cB, o, 64);
-            if (lane >= o) { cB = cA * pB + cB; cA = cA * pA; }
-        }
-        if (lane == 63) { sA[wv] = cA; sB[wv] = cB; }
         __syncthreads();
-        double gin = (double)((base == 0) ? g0 : sGain);
-        for (int v = 0; v < wv; v++) gin = sA[v] * gin + sB[v];      // gain behind the waves in front
-        {
-            const double eA = __shfl_up(cA, 1, 64), eB = __shfl_up(cB, 1, 64);
-            if (lane > 0) gin = eA * gin + eB;                          // ... and behind the lanes in front
+        if (tid == 0) {                                            // the gain in front of every thread's samples: the reference's recurrence, sample by sample
+            float g = (base == 0) ? g0 : sGain;
+            const int cnt = nout - base < AGC_T * AGC_K ? nout - base : AGC_T * AGC_K;
+            // (the magnitudes of the next ten samples are fetched while the gain walks these ten: no LDS latency in the chain)
+            float av[AGC_K], nx[AGC_K];
+#pragma unroll
+            for (int i = 0; i < AGC_K; i++) av[i] = sAbs[i];
+            for (int t = 0; t * AGC_K < cnt; t++) {
+                sG[t] = g;
+                const int tn = t + 1 < AGC_T ? t + 1 : t;
+#pragma unroll
+                for (int i = 0; i < AGC_K; i++) nx[i] = sAbs[tn * AGC_K + i];
+                const int left = cnt - t * AGC_K;
+#pragma unroll
+                for (int i = 0; i < AGC_K; i++)
+                    if (i < left) g += 2e-3f * (0.38f - g * av[i]);
+#pragma unroll
+                for (int i = 0; i < AGC_K; i++) av[i] = nx[i];
+            }
         }
-        float gain = (float)gin;
+        __syncthreads();
+        float gain = q0 < nout ? sG[tid] : 0.f;
 #pragma unroll
         for (int i = 0; i < AGC_K; i++) {
             if (q0 + i < nout) {

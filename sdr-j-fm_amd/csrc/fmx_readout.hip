@@ -144,6 +144,7 @@ int fmx_get_tap(fmx_handle h, int32_t channel, int32_t tap, float *dst, int64_t 
         if (!h->rds_alloc) return fail(FMX_E_INVALID, "RDS is off");
         const int64_t lm0 = h->last_m0[(size_t)channel], lm1 = h->last_m1[(size_t)channel];      // (the channel's own count: fmx_last_rds_samples_of)
         if (n > lm1 - lm0) return fail(FMX_E_INVALID, "n exceeds the RDS samples the channel produced in the last call");
+        if (n > RDS24_RING) return fail(FMX_E_INVALID, "n exceeds the 8192 RDS samples the library keeps");      // (a call of more than 786432 input samples)
         char *o = (char *)dst;
         for (int64_t m = lm1 - n; m < lm1;) {
             const int64_t pos = m & (RDS24_RING - 1);

@@ -155,6 +155,10 @@ class FmxRdsGroup(C.Structure):
     _fields_ = [("index", C.c_int64), ("end_bit", C.c_int64), ("block", C.c_uint16 * 4)]
 
 
+# the fields of fmx_debug_rds_state, in its order (include/fmx_debug.h)
+RDS_STATE_FIELDS = ("mode", "nbits", "rds2_gain", "rds2_freq", "rds2_phase", "rds2_mu", "rds2_skip", "rds2_sample_count",
+                    "rds1_freq", "rds1_phase", "rds1_last_sync", "rds3_freq", "rds3_phase", "rds3_bit_clk_phase", "rds3_sync_err", "rds3_synced")
+
 # fmx_rds_group as a numpy record (Fmx.rds_groups)
 RDS_GROUP_DTYPE = np.dtype({"names": ["index", "end_bit", "block"], "formats": [np.int64, np.int64, (np.uint16, 4)], "offsets": [0, 8, 16],
                             "itemsize": C.sizeof(FmxRdsGroup)})
@@ -258,6 +262,8 @@ def load_library(path=None):
     L.fmx_last_rds_samples.argtypes = [vp]
     L.fmx_last_rds_samples_of.restype = C.c_int64
     L.fmx_last_rds_samples_of.argtypes = [vp, C.c_int32]
+    L.fmx_debug_rds_state.restype = C.c_int                 # include/fmx_debug.h: a diagnostic, not one of EXPORTS
+    L.fmx_debug_rds_state.argtypes = [vp, i32, f32p, i32, C.POINTER(i32)]
     L.fmx_get_taps.restype = C.c_int
     L.fmx_get_taps.argtypes = [vp, i32, i32, f32p, i32, C.POINTER(i32)]
     L.fmx_profile_enable.restype = C.c_int
@@ -478,6 +484,14 @@ class Fmx:
         n = C.c_int32()
         self._check(self.L.fmx_rds_symbols(self.h, channel, out.ctypes.data_as(C.POINTER(C.c_float)), capacity, C.byref(n)))
         return out[:n.value].copy()
+
+    def debug_rds_state(self, channel=0):
+        """The scalar state of the channel's RDS slicers behind the last call (fmx_debug_rds_state, include/fmx_debug.h: a diagnostic) as a dict
+        of RDS_STATE_FIELDS; empty on a handle whose RDS was never switched on."""
+        out = np.zeros(len(RDS_STATE_FIELDS), np.float32)
+        n = C.c_int32()
+        self._check(self.L.fmx_debug_rds_state(self.h, channel, out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(n)))
+        return dict(zip(RDS_STATE_FIELDS[:n.value], out.tolist()))
 
     def last_fm_samples(self):
         return int(self.L.fmx_last_fm_samples(self.h))

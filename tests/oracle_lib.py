@@ -157,6 +157,11 @@ def oracle():
         "fmo_chain_peaks": (lng, [vp, c_float_p, lng]),
         "fmo_rds1_coeffs": (None, [c_float_p]),
         "fmo_bsync_run": (None, [c_u8_p, lng, c_i32_p, c_i32_p]),
+        "fmo_rds_slicer_new": (vp, [C.c_int]),
+        "fmo_rds_slicer_free": (None, [vp]),
+        "fmo_rds_slicer_run": (lng, [vp, c_float_p, lng, c_u8_p, C.POINTER(C.c_int64), c_float_p, lng]),
+        "fmo_rds_slicer_state": (C.c_int, [vp, c_float_p]),
+        "fmo_rds_slicer_samples": (lng, [vp]),
         "fmo_iir_new": (vp, [C.c_int, C.c_int, i32, i32, i32, C.c_int]),
         "fmo_iir_free": (None, [vp]),
         "fmo_iir_coeffs": (C.c_int, [vp, c_float_p]),
@@ -341,6 +346,48 @@ def synth_iq(n, return_rds_bits=False, rds_payload=None, **kw):
         bits = bits[:nb]
     L.fmo_siggen_free(g)
     return (out, bits) if return_rds_bits else out
+
+
+RDS_SLICER_STATE = {2: ("gain", "freq", "phase", "mu", "skip", "sample_count"), 1: ("freq", "phase", "last_sync"),
+                    3: ("freq", "phase", "bit_clk_phase", "sync_err", "synced")}
+
+
+class OracleRdsSlicer:
+    """fmo_rds_slicer: rdsDecoder_1 / _2 / _3 of the oracle on a 24 kS/s stream of its own, resumable from run to run."""
+
+    def __init__(self, mode):
+        self.L = oracle()
+        self.mode = mode
+        self.h = self.L.fmo_rds_slicer_new(mode)
+        assert self.h
+
+    def run(self, iq):
+        """The next samples [n, 2] -> (bits, the index of the sample each was decided on, vars [nbits, 4]: see fm_oracle.c)."""
+        iq = np.ascontiguousarray(iq, np.float32).reshape(-1, 2)
+        cap = iq.shape[0] // 8 + 8                      # (a bit takes ~20 samples; RDS_2 with a skip of 3 at its start: far below one in 8)
+        bits, at, var = np.zeros(cap, np.uint8), np.zeros(cap, np.int64), np.zeros((cap, 4), np.float32)
+        n = self.L.fmo_rds_slicer_run(self.h, fptr(iq), iq.shape[0], u8ptr(bits), at.ctypes.data_as(C.POINTER(C.c_int64)), fptr(var), cap)
+        assert n <= cap
+        return bits[:n], at[:n], var[:n]
+
+    def state(self):
+        out = np.zeros(8, np.float32)
+        n = self.L.fmo_rds_slicer_state(self.h, fptr(out))
+        return dict(zip(RDS_SLICER_STATE[self.mode], out[:n].tolist()))
+
+    def samples(self):
+        return int(self.L.fmo_rds_slicer_samples(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.fmo_rds_slicer_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class OracleChain:

@@ -26,8 +26,8 @@ def test_library_exports_every_declared_symbol(fmx_amd):
     for n in header_functions():
         assert hasattr(L, n), n
     assert L.fmx_abi_version() == 3
-    dbg = header_functions("fmx_debug.h")          # the two diagnostic exports have a header of their own (not part of the boundary)
-    assert dbg == ["fmx_debug_phase_cycles", "fmx_debug_stream_bandwidth"]
+    dbg = header_functions("fmx_debug.h")          # the diagnostic exports have a header of their own (not part of the boundary)
+    assert dbg == ["fmx_debug_phase_cycles", "fmx_debug_rds_state", "fmx_debug_stream_bandwidth"]
     for n in dbg:
         assert hasattr(L, n), n
     # ... and nothing else is exported under the library's prefix
