@@ -617,9 +617,17 @@ __global__ __launch_bounds__(FB_T, PART == 0 ? SB_WG_PER_SIMD : 4) void stageb_k
                 // samples unchanged (unless it flips a rounding: 6e-4 per ulp and run): every thread runs its samples from its incoming
                 // value, the end values' misses against the next threads' incoming values are prefix-summed into corrections, and the
                 // passes repeat until every run ends on the next run's start -- the chain from the exact cy.afc is then the sequential one.
+                // A pass makes at least one more thread final (thread 0 starts from cy.afc; the first thread behind the final ones sees a
+                // prefix of zeros and takes its predecessor's end value as it is), so FB_T + 1 passes always suffice; a steady average (a
+                // mistuned carrier) needs two or three.  A cap of eight was not enough for an ordinary programme, whose average swings through
+                // zero with the audio (+-0.009 at 1 kHz; presumably a shift does not ride through a run whose value climbs into the next
+                // binade, and every such place behind a corrected thread costs a pass): the walk then fell back to the scan's values without a
+                // word, and since an f32 recurrence does not forget a shift of one ulp (1e-4 ulp per sample rounds away), a quarter of a
+                // receiver's DEMOD samples differed from the reference's in their last bit (tests/test_gpu_stage_b_per_sample.py, which
+                // holds every sample of such handles to bit identity).
                 if (P.pll_seq == 1 || afc_big) {
                     const float afc0 = cy.afc;
-                    for (int pass = 0; pass < 8; pass++) {
+                    for (int pass = 0; pass < FB_T + 1; pass++) {
                         float o = afc;
 #pragma unroll
                         for (int i = 0; i < FB_K; i++) if (i < nv) o = c1 * o + fmDcAlpha * res[i];
@@ -1098,7 +1106,7 @@ __global__ __launch_bounds__(FB_T, PART == 0 ? SB_WG_PER_SIMD : 4) void stageb_k
                 // 1 / 3000 per sample).  The lock decisions then sit on the reference's metric, not within 1e-7 of it.
                 if (P.pll_seq == 1) {
                     const float lock0 = cy.lock;
-                    for (int pass = 0; pass < 8; pass++) {
+                    for (int pass = 0; pass < FB_T + 1; pass++) {             // (as many as always suffice: see the AFC)
                         float o = lock;
 #pragma unroll
                         for (int i = 0; i < FB_K; i++) if (i < nv) o = (float)((double)xq[i] + (double)o * keep);
@@ -1450,7 +1458,7 @@ __global__ __launch_bounds__(FB_T, PART == 0 ? SB_WG_PER_SIMD : 4) void stageb_k
         // ================= 38 kHz mix, PSS input, stereo matrix (fm-processor.cpp:707-730, 517-549) =================
         float2 x[FB_K];
         {
-            constexpr double INV2PI = 1.0 / FMX_2PI;
+            const double SC64 = T.sincos_C;
             const int ssel = P.sound_sel; const float pano = (P.fm_mode == 1) ? P.panorama : 1.0f;
             const int icl = (int)((pss_count0 + calls_before) & smask);   // ring position of the segment's first call
             const float P32 = 6.2831855f, C32 = T.wrap32_c;
@@ -1464,10 +1472,16 @@ __global__ __launch_bounds__(FB_T, PART == 0 ? SB_WG_PER_SIMD : 4) void stageb_k
                 float cc = (cur[i] < P32) ? cur[i] : (cur[i] - P32) + C32;                   // PI_Constrain of [0, 2 pi + 0.7), see the pilot PLL
                 if (wide) cc = pi_constrain(cur[i]);
                 const float p = (float)(2 * ((double)cc + FMX_PI_4) - (double)used[i]);      // (+ PILOTTESTDELAY = 0, fm-processor.cpp:42: x + 0 = x for x > 0)
-                const double u = __builtin_amdgcn_fract((double)p * INV2PI);
-                // SinCos::getComplex sincos.cpp:93-97 (the fraction of a turn is at most 1 - 2^-53, v_fract_f64's own bound: its product with 192000 rounds
-                // below 192000, the index needs no clamp)
-                const int idx = (int)(u * (double)SINCOS_N);
+                // fmod (p, 2 pi) ROUNDED TO F32 (:714), as the reference hands it to SinCos: from 2 pi on the exact remainder has more bits than an f32, the
+                // rounding moves it by up to 2.4e-7 rad, and an index formed from the unrounded fraction of the turn is one entry off in 0.28 % of those
+                // samples (6.5e-5 |demod| in L - R: tests/test_gpu_stage_b_per_sample.py).  cc is in [0, 2 pi) and |pilotDelayPSS| <= pi / 4, so p lies in
+                // (pi / 4, 4 pi + 3 pi / 4]: the remainder is one or two subtractions of f64 (2 pi), each exact
+                double r = (double)p;
+                r = (r >= 2 * FMX_2PI) ? r - 2 * FMX_2PI : r;
+                r = (r >= FMX_2PI) ? r - FMX_2PI : r;
+                // SinCos::getCos / getSin / getComplex sincos.cpp:63-97: entry (int)(phase * C) % Rate.  (Their second fmod only meets a remainder that rounded
+                // up to 6.2831855f: index 192000 either way, which sincos_idx_hw_bits folds onto entry 0 -- (1, -0.0) for the table's (1, +0.0))
+                const int idx = (int)((double)(float)r * SC64);
                 float2 e;
                 sincos_idx_hw_bits(idx, &e.y, &e.x);
                 float dif = 0.f;
