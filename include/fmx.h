@@ -490,6 +490,61 @@ typedef struct fmx_loudness {
 } fmx_loudness;
 int  fmx_audio_loudness(const fmx_audio_record *recs, int32_t n, fmx_loudness *out);
 
+/* ---- the reception meter: what a monitoring receiver reports of the RECEPTION beside modulation -- RF level, a carrier-to-noise figure,
+ * the envelope's modulation depth (the multipath indicator) and the frequency offset; tuner ICs call them "level / WAM / offset" -- as one 40-byte record
+ * per channel and 50 ms window, computed on the GPU from the channel's fm-rate samples in front of the limiter, where the envelope still carries the noise
+ * and the multipath.
+ *
+ * Input, for fm sample j of a channel (j counts the handle's fm samples since fmx_create, as the taps number them): v [j], the value of FMX_TAP_FM_IQ,
+ * read as every reader of stage A's ring reads it -- ring position (j - delay_fm) & ring_mask, zero while j - delay_fm < 0, delay_fm the latency of the
+ * channel's input filter in force in the piece that reads -- and u [j] = v [j - 1] under the same rule: the previous sample comes from the ring and is
+ * never carried.
+ * The grid is the modulation meter's, so that records of the two meters pair by `index`: window w is the fm samples [9600 w, 9600 (w + 1)), 50 ms; inside
+ * a window sample i = j - 9600 w belongs to lane l = i mod 64 as its step q = i div 64 (150 steps).  Each lane accumulates in step order, in f32, without
+ * contraction into fma; with f32 (.) one rounding:
+ *     p  = f32 (f32 (v.re v.re) + f32 (v.im v.im))
+ *     mx = max (mx, p) from -inf, mn = min (mn, p) from +inf, s1 += p, s2 += f32 (p p)                                    (sums from 0)
+ *     cr += f32 (f32 (v.re u.re) + f32 (v.im u.im)),  ci += f32 (f32 (v.im u.re) - f32 (v.re u.im))
+ * (cr, ci) is the sum of v conj (u), the autocorrelation at lag 1.  At the window's end the 64 lanes are combined by the butterfly
+ * a [l] = a [l] op a [l xor m] for m = 32, 16, 8, 4, 2, 1, and
+ *     p_max = mx, p_min = mn, p_mean = s1 / 9600.0f, p2_mean = s2 / 9600.0f, r1_re = cr / 9600.0f, r1_im = ci / 9600.0f.
+ * What a channel carries between calls is its 64 x 6 lane accumulators and no sample: on the same ring contents a record is the same bit for bit however
+ * the stream is cut into calls, or a call into pieces.  (The ring's contents themselves depend on the cut in their last bits where the RF DC removal is on:
+ * it is evaluated in tiles that begin with the call)
+ * Window w of a channel leaves a record only if the channel's meter was on in every piece that covered one of its samples: a meter switched on in
+ * mid-window starts at the next boundary, one switched off drops the window in progress; a scanning channel's meter runs on, as its chain does.
+ * The device keeps the last 64 records (3.2 s) per channel.  Everything else a handle delivers -- PCM, RDS, meta, taps, peaks, scan records, both other
+ * meters' records, fmx_last_second_group, fmx_last_call_pieces, fmx_last_front_kernel -- is bit for bit, or equal to, what it is without the meter: the
+ * ring is kept by every handle in every mode, so a reception meter asks nothing of a call's plan and can be on for every channel of a batch, which stays
+ * the plain batch it was.  A handle that never switches it on allocates and launches nothing for it. */
+typedef struct fmx_rx_record {
+    int64_t index;        /* the window w; a gap means windows that were not metered or that the reader lost */
+    int64_t end_sample;   /* 9600 (w + 1): the fm sample behind the window's last */
+    float   p_max, p_min, p_mean, p2_mean;      /* of the power |v|^2 (full scale 1); p2_mean in its square */
+    float   r1_re, r1_im;                       /* the mean of v conj (v one sample earlier) */
+} fmx_rx_record;   /* 40 bytes */
+/* switches the reception meter of a channel (-1: of every channel) on or off; from any thread, takes effect at the next call */
+int  fmx_rx_meter_enable(fmx_handle h, int32_t channel, int32_t on);
+/* the records the channels first_channel .. first_channel + n_channels - 1 completed since this function last read them, oldest first, at most
+ * capacity_per_channel each (more stay for the next read): channel k's at out [k * capacity_per_channel ..], their number in n_records [k].  One
+ * read-out of the device for the whole range. */
+int  fmx_rx_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rx_record *out, int32_t capacity_per_channel, int32_t *n_records);
+/* The reception figures of one channel's records (host only, needs no device, all arithmetic in double).  With M2 the mean of p_mean and M4 the mean of
+ * p2_mean over the n records:
+ *   level_dbfs = 10 log10 M2 (-HUGE_VAL for M2 = 0);
+ *   cnr_db     the M2M4 estimate for a carrier of constant envelope in complex Gaussian noise: S = sqrt (2 M2^2 - M4), N = M2 - S,
+ *              cnr_db = 10 log10 (S / N); -HUGE_VAL where 2 M2^2 - M4 <= 0 (no carrier: the channel is noise), +HUGE_VAL where N <= 0;
+ *   am_depth   the largest over the records of (sqrt p_max - sqrt p_min) / (sqrt p_max + sqrt p_min), the envelope's modulation depth; 0 for a record
+ *              with p_max = 0;
+ *   offset_hz  atan2 (sum r1_im, sum r1_re) fmRate / (2 pi): the power-weighted centre of the instantaneous frequency, whatever the decoder;
+ *   windows    n.
+ * n = 0 (or a null pointer, or fmRate < 1) gives FMX_E_INVALID. */
+typedef struct fmx_rx_quality {
+    double  level_dbfs, cnr_db, am_depth, offset_hz;
+    int64_t windows;
+} fmx_rx_quality;
+int  fmx_rx_quality_of(const fmx_rx_record *recs, int32_t n, int32_t fmRate, fmx_rx_quality *out);
+
 /* introspection used by the parity tests: the filter taps the kernels run with.
  * which: 0 front-end polyphase taps, 1 PSS low-pass, 2 audio+resampler FIR, 3 resampler alone,
  * 4 the noise squelch's two order-20 filters: [2][10] x (A1, A2, B1, B2), then the two gains (high-pass first),

@@ -25,6 +25,7 @@ SOURCES = [
     ("fmx_scan.hip", []),
     ("fmx_meter.hip", ["-ffp-contract=off"]),      # (the modulation meter's sums are defined without fma: DESIGN 4.11)
     ("fmx_loud.hip", ["-ffp-contract=off"]),       # (the audio meter's recurrences are defined without fma: DESIGN 4.12)
+    ("fmx_rx.hip", ["-ffp-contract=off"]),         # (the reception meter's sums are defined without fma: DESIGN 4.13)
     ("fmx_wide.hip", []),
     ("fmx_wide_rate.hip", []),
     ("fmx_survey.hip", []),

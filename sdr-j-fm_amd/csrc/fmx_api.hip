@@ -656,6 +656,19 @@ int ensure_audio_meter(fmx_handle h) {
     return FMX_OK;
 }
 
+// the reception meter's buffers (fmx_rx.hip), allocated by the first call in which a channel's reception meter is on
+int ensure_rx_meter(fmx_handle h) {
+    if (h->rx_alloc) return FMX_OK;
+    const size_t C = (size_t)h->channels;
+    HIPCHK(hipDeviceSynchronize());
+    FMXCHK(h->mem.alloc(h->d_rx_state, C * rx::QUANT * meter::LANES, true));
+    FMXCHK(h->mem.alloc(h->d_rx_ring, C * rx::RING, true));
+    FMXCHK(h->mem.alloc(h->d_rx_jobs, C));
+    h->call_rx.assign(C, 0); h->rx_on_from.assign(C, -1); h->rx_produced.assign(C, 0); h->rd.rx.assign(C, 0);
+    h->rx_alloc = true;
+    return FMX_OK;
+}
+
 // the tiled work arrays of the demodulator pre-pass (fmx_demod.hip): limited / unlimited samples in, demodulator output out.  (Allocated by the first call
 // that needs them -- before run_call decides how the call is made: a call in pieces needs them too.)
 int ensure_prepass_arrays(fmx_handle h) {
@@ -706,6 +719,9 @@ int flush_mailbox(fmx_handle h) {
     // (the audio meter reads the call's PCM behind everything that writes it and asks nothing of the call's plan: it is no part of CallNeeds)
     if (!h->loud_alloc && std::any_of(h->user.begin(), h->user.end(), [](const ChanUser &u) { return u.loud; })) { const int rc = ensure_audio_meter(h); if (rc) return rc; }
     if (h->loud_alloc) for (int c = 0; c < h->channels; c++) h->call_loud[(size_t)c] = h->user[(size_t)c].loud ? 1 : 0;
+    // (the reception meter reads stage A's ring, which every handle keeps in every mode: no part of CallNeeds either)
+    if (!h->rx_alloc && std::any_of(h->user.begin(), h->user.end(), [](const ChanUser &u) { return u.rx; })) { const int rc = ensure_rx_meter(h); if (rc) return rc; }
+    if (h->rx_alloc) for (int c = 0; c < h->channels; c++) h->call_rx[(size_t)c] = h->user[(size_t)c].rx ? 1 : 0;
     // (a channel's RDS path runs while its decoder is on and stands still otherwise -- block filters, phase delay line, decimator and slicer
     // keep what they hold, as the reference's processor's do: nothing restarts when a decoder is switched; run_piece counts per channel)
     if (nd.any_rds) { const int rc = ensure_rds(h); if (rc) return rc; }
@@ -982,6 +998,38 @@ int stage_meter(fmx_handle h, const CallGeom &G, hipStream_t s) {
     return FMX_OK;
 }
 
+// the reception meter: the metered channels' fm samples of the piece, out of stage A's ring, into their lane accumulators, every window that ends in it into
+// the record ring (fmx_rx.hip) -- on the stream stage A ran on, behind this piece's stage A and ahead of the next one's, as stage_scan.  The sample in front
+// of the piece's first comes from the ring: rx::ring_holds says that stage A has not yet written over it (with fmx_create's sizing of the ring it always
+// does, as for stage B, which looks back two samples).  The bookkeeping is the host's (meter_produce); the kernel gets one job per channel that accumulates.
+int stage_rx(fmx_handle h, const CallGeom &G, hipStream_t sa) {
+    const int64_t nj = G.J1 - G.J0;
+    h->rx_jobs.clear();
+    {
+        std::lock_guard<std::mutex> lk(h->mtx);      // (fmx_rx_records reads the counters from any thread)
+        for (int c = 0; c < h->channels; c++)
+            if (h->call_rx[(size_t)c] && !rx::ring_holds(h->ring, h->h_front_sets[(size_t)h->params[(size_t)c].front_set].delay_fm, nj, h->twins))
+                return fail(FMX_E_TOO_LARGE, "the piece has more fm samples than stage A's ring keeps behind the reception meter's look-back");
+        for (int c = 0; c < h->channels; c++) {
+            if (!h->call_rx[(size_t)c]) { h->rx_on_from[(size_t)c] = -1; continue; }      // (off: the window in progress is dropped)
+            if (h->rx_on_from[(size_t)c] < 0) h->rx_on_from[(size_t)c] = G.J0;
+            const meter::Produce mp = meter::meter_produce(h->rx_on_from[(size_t)c], G.J0, nj, h->rx_produced[(size_t)c]);
+            if (mp.first >= G.J1) continue;
+            h->rx_jobs.push_back(RxJob{c, (int32_t)(mp.first - G.J0), (int32_t)mp.slot(0), 0});
+            h->rx_produced[(size_t)c] = mp.new_produced;
+        }
+    }
+    const size_t n = h->rx_jobs.size();
+    if (n == 0) return FMX_OK;
+    // (pageable source: the copy is staged before the call returns)
+    HIPCHK(hipMemcpyAsync(h->d_rx_jobs, h->rx_jobs.data(), sizeof(RxJob) * n, hipMemcpyHostToDevice, sa));
+    RxArgs A{};
+    A.jobs = h->d_rx_jobs; A.zring = h->B.zring; A.params = h->d_params; A.front_sets = h->d_front_sets; A.state = h->d_rx_state; A.ring = h->d_rx_ring;
+    A.J0 = G.J0; A.J1 = G.J1; A.ring_mask = G.ring_mask;
+    launch_rx(A, (int)n, sa); FMX_LAUNCHED();
+    return FMX_OK;
+}
+
 // the scanning channels' frames of the call are zeros (their chain runs on: outside the scanning calls a channel is what it would have been)
 int stage_scan_mute(fmx_handle h, float2 *d_pcm, int64_t pcm_stride, int64_t frames, hipStream_t s) {
     const size_t n = h->call_scan.size();
@@ -1085,6 +1133,7 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     if (capture && (rc = capture_samples(h, d_iq, a, G, sa))) return rc;
     if ((rc = stage_a(h, G, d_iq, s, sa))) return rc;
     if (!h->call_scan.empty() && G.J1 > G.J0 && (rc = stage_scan(h, G, sa))) return rc;
+    if (h->rx_alloc && G.J1 > G.J0 && (rc = stage_rx(h, G, sa))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[1], sa));
     G.stageb_form = h->stageb_form.load(); G.no_deemph = h->ola_mode ? 1 : 0;
     // a plain batch (no pre-pass, no RDS, no scope-tap rows: stage B as the whole kernel) runs stages B and C as two channel groups on two streams where it has
@@ -1544,6 +1593,15 @@ int fmx_audio_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
     const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
     for (int c = c0; c < c1; c++) h->user[(size_t)c].loud = on != 0;
+    return FMX_OK;
+}
+
+int fmx_rx_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
+    if (!h) return fail(FMX_E_INVALID, "null handle");
+    if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
+    std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
+    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
+    for (int c = c0; c < c1; c++) h->user[(size_t)c].rx = on != 0;
     return FMX_OK;
 }
 

@@ -449,6 +449,20 @@ struct LoudArgs {
 };
 void launch_loud(const LoudArgs &A, int n_jobs, hipStream_t s);
 
+// ---- the reception meter (fmx_rx.hip, fmx_rx.h) -------------------------------------------------------------------------
+// one metered channel of a piece: the first of the piece's fm samples it accumulates (relative to J0), and the ring slot its first completed window goes to
+struct RxJob { int32_t ch, r0, slot0, pad; };
+struct RxArgs {
+    const RxJob *jobs;            // [n_jobs] (copied per piece on the stream of the launch)
+    const float2 *zring;          // stage A's fm-rate ring, [channels][ring_mask + 1]
+    const ChanParams *params; const FrontSet *front_sets;   // (the channel's delay_fm)
+    float *state;                 // [channels][rx::QUANT][meter::LANES] the lane accumulators of the window in progress
+    fmx_rx_record *ring;          // [channels][rx::RING]
+    int64_t J0, J1;               // the piece's fm samples
+    int32_t ring_mask, pad;
+};
+void launch_rx(const RxArgs &A, int n_jobs, hipStream_t s);
+
 // ---- stage W: wide-band ingest (fmx_wide.hip; DESIGN.md "Stage W") ----------------------------------------------------------
 // One stream at K * 2 304 000 S/s feeds many outputs at 2 304 000 S/s: per-sample mix, T = 16 K + 1 real taps, / K.
 constexpr int W_RATE0 = 2304000;       // the narrow rate, and the circle of the output rotator's table

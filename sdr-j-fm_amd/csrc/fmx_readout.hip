@@ -1,6 +1,6 @@
 // fmx_readout.hip -- the entry points of include/fmx.h that only read a handle: metaData, peak levels, scope taps, tap sets, the RDS bits, symbols, groups
-// and decoders, scan records, the modulation meter's and the audio meter's records, the PLL counters, the facts about the last call; the host-only RDS
-// helpers and the host-only loudness figures (fmx_audio_loudness).  A per-channel read-out waits for the device, asks its ring's producer for the count, and takes [from, from + count) out of one copy of the ring (read_ring); where each reader stands is in the
+// and decoders, scan records, the modulation meter's, the audio meter's and the reception meter's records, the PLL counters, the facts about the last call;
+// the host-only RDS helpers, the host-only loudness figures (fmx_audio_loudness) and the host-only reception figures (fmx_rx_quality_of).  A per-channel read-out waits for the device, asks its ring's producer for the count, and takes [from, from + count) out of one copy of the ring (read_ring); where each reader stands is in the
 // handle's Readers (fmx_host.h).  The two batch RDS read-outs wait for the handle's last call only and copy every channel's ring at once (rds_batch_fetch).
 #include "fmx_host.h"
 #include "fmx_design.h"
@@ -314,6 +314,52 @@ int fmx_audio_loudness(const fmx_audio_record *recs, int32_t n, fmx_loudness *ou
     L.correlation = den > 0.0 ? sc / den : 0.0;
     L.peak_dbfs_l = dbfs(pl); L.peak_dbfs_r = dbfs(pr);
     *out = L;
+    return FMX_OK;
+}
+
+int fmx_rx_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rx_record *out, int32_t capacity_per_channel, int32_t *n_records) {
+    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || capacity_per_channel < 0 ||
+        (n_channels > 0 && (!n_records || (capacity_per_channel > 0 && !out)))) return fail(FMX_E_INVALID, "bad argument");
+    for (int k = 0; k < n_channels; k++) n_records[k] = 0;
+    if (n_channels == 0 || !h->rx_alloc) return FMX_OK;
+    FMXCHK(device_idle(h));
+    std::lock_guard<std::mutex> lk(h->mtx);
+    std::vector<RingTake> takes((size_t)n_channels);
+    for (int k = 0; k < n_channels; k++) {
+        const size_t c = (size_t)(first_channel + k);
+        takes[(size_t)k] = ring_take(h->rx_produced[c], h->rd.rx[c], rx::RING, capacity_per_channel);      // (a reader that fell behind: the gap shows in `index`)
+    }
+    FMXCHK(read_rings(h->d_rx_ring + (size_t)first_channel * rx::RING, rx::RING, n_channels, takes.data(),
+                      [&](int k, int64_t i, const fmx_rx_record &r) { out[(size_t)k * (size_t)capacity_per_channel + (size_t)i] = r; }));
+    for (int k = 0; k < n_channels; k++) { h->rd.rx[(size_t)(first_channel + k)] = takes[(size_t)k].next(); n_records[k] = (int32_t)takes[(size_t)k].count; }
+    return FMX_OK;
+}
+
+// the reception figures of one channel's records (include/fmx.h): level, the M2M4 carrier-to-noise estimate, the envelope's depth, the lag-1 offset
+int fmx_rx_quality_of(const fmx_rx_record *recs, int32_t n, int32_t fmRate, fmx_rx_quality *out) {
+    if (!out || !recs || n <= 0 || fmRate < 1) return fail(FMX_E_INVALID, "bad argument");
+    double s2 = 0.0, s4 = 0.0, sre = 0.0, sim = 0.0, depth = 0.0;
+    for (int32_t i = 0; i < n; i++) {
+        s2 += (double)recs[i].p_mean; s4 += (double)recs[i].p2_mean;
+        sre += (double)recs[i].r1_re; sim += (double)recs[i].r1_im;
+        if (recs[i].p_max > 0.0f) {
+            const double a = std::sqrt((double)recs[i].p_max), b = std::sqrt(std::max(0.0, (double)recs[i].p_min));
+            depth = std::max(depth, (a - b) / (a + b));
+        }
+    }
+    const double M2 = s2 / (double)n, M4 = s4 / (double)n;
+    fmx_rx_quality Q{};
+    Q.level_dbfs = M2 > 0.0 ? 10.0 * std::log10(M2) : -HUGE_VAL;
+    const double disc = 2.0 * M2 * M2 - M4;
+    if (disc <= 0.0) Q.cnr_db = -HUGE_VAL;
+    else {
+        const double S = std::sqrt(disc), N = M2 - S;
+        Q.cnr_db = N <= 0.0 ? HUGE_VAL : 10.0 * std::log10(S / N);
+    }
+    Q.am_depth = depth;
+    Q.offset_hz = std::atan2(sim, sre) * (double)fmRate / (2.0 * design::kPi);
+    Q.windows = n;
+    *out = Q;
     return FMX_OK;
 }
 

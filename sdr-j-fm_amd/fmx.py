@@ -39,7 +39,7 @@ EXPORTS = [
     "fmx_abi_version", "fmx_last_error", "fmx_create", "fmx_destroy", "fmx_set_param", "fmx_frames_for", "fmx_filter_change_due",
     "fmx_process_host", "fmx_process_device", "fmx_process_host_raw", "fmx_process_device_raw", "fmx_synchronize",
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
-    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
+    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rx_meter_enable", "fmx_rx_records", "fmx_rx_quality_of", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
     "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
     "fmx_wideband_survey_enable", "fmx_wideband_survey_read", "fmx_wideband_survey_stations",
     "fmx_wideband_create_rate", "fmx_wideband_outputs_for", "fmx_wideband_rate_taps", "fmx_wideband_survey_stations_rate",
@@ -151,6 +151,23 @@ class FmxLoudness(C.Structure):
                 ("peak_dbfs_l", C.c_double), ("peak_dbfs_r", C.c_double), ("blocks_total", C.c_int64), ("blocks_gated", C.c_int64)]
 
 
+class FmxRxRecord(C.Structure):
+    _fields_ = [("index", C.c_int64), ("end_sample", C.c_int64), ("p_max", C.c_float), ("p_min", C.c_float), ("p_mean", C.c_float),
+                ("p2_mean", C.c_float), ("r1_re", C.c_float), ("r1_im", C.c_float)]
+
+
+# fmx_rx_record as a numpy record (Fmx.rx_records)
+RX_DTYPE = np.dtype([("index", np.int64), ("end_sample", np.int64), ("p_max", np.float32), ("p_min", np.float32), ("p_mean", np.float32),
+                     ("p2_mean", np.float32), ("r1_re", np.float32), ("r1_im", np.float32)])
+assert RX_DTYPE.itemsize == C.sizeof(FmxRxRecord) == 40
+RxRecord = FmxRxRecord
+RX_WINDOW = 9600              # fm samples per record: 50 ms, the modulation meter's grid
+
+
+class FmxRxQuality(C.Structure):
+    _fields_ = [("level_dbfs", C.c_double), ("cnr_db", C.c_double), ("am_depth", C.c_double), ("offset_hz", C.c_double), ("windows", C.c_int64)]
+
+
 class FmxRdsGroup(C.Structure):
     _fields_ = [("index", C.c_int64), ("end_bit", C.c_int64), ("block", C.c_uint16 * 4)]
 
@@ -238,6 +255,12 @@ def load_library(path=None):
     L.fmx_audio_records.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
     L.fmx_audio_loudness.restype = C.c_int
     L.fmx_audio_loudness.argtypes = [vp, i32, C.POINTER(FmxLoudness)]
+    L.fmx_rx_meter_enable.restype = C.c_int
+    L.fmx_rx_meter_enable.argtypes = [vp, i32, i32]
+    L.fmx_rx_records.restype = C.c_int
+    L.fmx_rx_records.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
+    L.fmx_rx_quality_of.restype = C.c_int
+    L.fmx_rx_quality_of.argtypes = [vp, i32, i32, C.POINTER(FmxRxQuality)]
     L.fmx_mod_hz_per_unit.restype = C.c_int
     L.fmx_mod_hz_per_unit.argtypes = [i32, i32, C.POINTER(C.c_double)]
     L.fmx_rds_bits.restype = C.c_int
@@ -334,6 +357,18 @@ def loudness(records):
     if rc != FMX_OK:
         raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
     return {name: getattr(out, name) for name, _ in FmxLoudness._fields_}
+
+
+def rx_quality(records, fmRate=192000):
+    """The reception figures of one channel's reception-meter records (RX_DTYPE; include/fmx.h fmx_rx_quality_of; host only, needs no device): a dict of
+    level_dbfs, cnr_db (-inf: no carrier, +inf: no noise), am_depth, offset_hz and windows.  Raises FmxError (FMX_E_INVALID) for no records."""
+    L = load_library()
+    recs = np.ascontiguousarray(records, RX_DTYPE)
+    out = FmxRxQuality()
+    rc = L.fmx_rx_quality_of(recs.ctypes.data if recs.size else None, int(recs.size), int(fmRate), C.byref(out))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
+    return {name: getattr(out, name) for name, _ in FmxRxQuality._fields_}
 
 
 class Fmx:
@@ -470,6 +505,22 @@ class Fmx:
         out = np.zeros((max(count, 1), max(capacity, 1)), AUDIO_DTYPE)
         n = (C.c_int32 * max(count, 1))()
         self._check(self.L.fmx_audio_records(self.h, first, count, out.ctypes.data, capacity, n))
+        return [out[k, :n[k]].copy() for k in range(count)]
+
+    def rx_meter(self, on=True, channel=-1):
+        """Switch the reception meter of a channel (-1: of every channel) on or off, from the next call on (fmx_rx_meter_enable)."""
+        self._check(self.L.fmx_rx_meter_enable(self.h, int(channel), 1 if on else 0))
+
+    rx_meter_enable = rx_meter
+
+    def rx_records(self, first=0, count=None, capacity=64):
+        """The reception meter's records since the last read, per channel of the range, oldest first (fmx_rx_records): a list of numpy structured arrays
+        (RX_DTYPE: index, end_sample, p_max, p_min, p_mean, p2_mean, r1_re, r1_im), one per 50 ms window of the channel's fm-rate samples; rx_quality ()
+        turns a channel's records into level, C/N, envelope depth and offset.  The library keeps the last 64 per channel."""
+        count = self.channels - first if count is None else count
+        out = np.zeros((max(count, 1), max(capacity, 1)), RX_DTYPE)
+        n = (C.c_int32 * max(count, 1))()
+        self._check(self.L.fmx_rx_records(self.h, first, count, out.ctypes.data, capacity, n))
         return [out[k, :n[k]].copy() for k in range(count)]
 
     def rds_bits(self, channel=0, capacity=8192):
@@ -789,6 +840,12 @@ class FmProcessor:
     def pollAudio(self):
         """The audio meter's records since the last poll (AUDIO_DTYPE): peak, mean square, K-weighted mean square and cross term per 100 ms window."""
         return self.fmx.audio_records(self.channel, 1)[0]
+
+    def setReceptionMeter(self, on): self.fmx.rx_meter(on, self.channel)
+
+    def pollReception(self):
+        """The reception meter's records since the last poll (RX_DTYPE): power maximum, minimum, mean, mean square and lag-1 correlation per 50 ms window."""
+        return self.fmx.rx_records(self.channel, 1)[0]
 
     def isPilotLocked(self):
         m = self.fmx.meta(self.channel)

@@ -197,6 +197,17 @@ public:
         for (int32_t k = 0; k < n; k++) emit_fn(r[k]);
         return n;
     }
+    // the reception meter (include/fmx.h fmx_rx_records; nothing of the reference's): setReceptionMeter switches it with the next block, pollReception
+    // calls `emit_fn(const fmx_rx_record &)` once per 50 ms window completed since the last poll, oldest first (fmx_rx_quality_of makes level, C/N, envelope
+    // depth and offset of them: receptionQuality over the records one poll handed out)
+    void setReceptionMeter(bool on) { if (h) check(fmx_rx_meter_enable(h, 0, on ? 1 : 0)); }
+    template <class F> int pollReception(F emit_fn) {
+        fmx_rx_record r[64]; int32_t n = 0;
+        if (!h || fmx_rx_records(h, 0, 1, r, 64, &n) != FMX_OK) return 0;
+        for (int32_t k = 0; k < n; k++) emit_fn(r[k]);
+        return n;
+    }
+    static bool receptionQuality(const fmx_rx_record *recs, int32_t n, fmx_rx_quality *q, int32_t fmRate = 192000) { return fmx_rx_quality_of(recs, n, fmRate, q) == FMX_OK; }
     // the RDS picture of this processor's channel(s) in one read-out of the device (fmx_rds_decode_all: the block synchroniser has run on the GPU,
     // the group decoder runs here): what the rds classes' signals carried, infos[k] for channel first + k
     bool poll_rds(fmx_rds_info *infos, int32_t first = 0, int32_t count = 1) { return h && check(fmx_rds_decode_all(h, first, count, infos)); }
