@@ -545,6 +545,76 @@ typedef struct fmx_rx_quality {
 } fmx_rx_quality;
 int  fmx_rx_quality_of(const fmx_rx_record *recs, int32_t n, int32_t fmRate, fmx_rx_quality *out);
 
+/* ---- the RDS meter: the RDS sub-carrier itself, in front of every slicer -- its injection level (the RDS deviation, which regulators
+ * limit), its phase against the third harmonic of the pilot (IEC 62106: 0 or 90 degrees within 10) and how clean it is -- as one 40-byte record per
+ * channel and window of 2560 RDS samples (106.7 ms, about 127 bits), computed on the GPU from the 24 kS/s complex baseband behind the RDS path's decimator.
+ *
+ * Input, for RDS sample m of a channel: z [m] = (I, Q), the value of FMX_TAP_RDS_IQ, at position m & 8191 of the channel's ring of 24 kS/s samples.  m
+ * counts the channel's own 24 kS/s outputs since fmx_create -- the count fmx_last_rds_samples_of adds up -- and stands still while the channel's decoder is
+ * off: channels switched on at different times have different grids, and that is intended.
+ * Window w is the channel's RDS samples [2560 w, 2560 (w + 1)); inside a window sample i = m - 2560 w belongs to lane i mod 64 as its step i div 64 (40
+ * steps).  Each lane accumulates in step order, in f32, without contraction into fma; with f32 (.) one rounding:
+ *     ii = f32 (I I), qq = f32 (Q Q), p = f32 (ii + qq)
+ *     mx = max (mx, p) from -inf, sii += ii, sqq += qq, siq += f32 (I Q), si += I, sq += Q                               (sums from 0)
+ * At the window's end the 64 lanes are combined by the butterfly a [l] = a [l] op a [l xor k] for k = 32, 16, 8, 4, 2, 1, and
+ *     p_max = mx, ii_mean = sii / 2560.0f, qq_mean = sqq / 2560.0f, iq_mean = siq / 2560.0f, i_mean = si / 2560.0f, q_mean = sq / 2560.0f.
+ * What a channel carries between pieces is its 64 x 6 lane accumulators and no sample: on the same ring contents a record is the same bit for bit however
+ * the stream is cut into calls, or a call into pieces (the pieces of at most 31 999 fm samples that calls with RDS on are made in included).
+ * Window w of a channel leaves a record only if the channel's meter was on in every piece in which the channel produced one of the window's samples: a
+ * meter switched on in mid-window starts at the next boundary, one switched off drops the window in progress.  A piece in which the channel's decoder is
+ * off changes nothing: a window may span a pause of the decoder, as the path's own filters do.  Enabling the meter does not switch RDS on: a metered
+ * channel whose decoder never runs gets no records.  The slicer (RDS_1 / 2 / 3), FMX_A_RESET_RDS and FMX_A_TRIGGER_FREQUENCY_CHANGE do not touch the
+ * meter: the front end runs on, and so does the meter.  The device keeps the last 64 records (6.8 s) per channel.  Everything else a handle delivers --
+ * PCM, RDS bits, groups, fmx_rds_decode_all, meta, taps, peaks, scan records, the three other meters' records, fmx_last_second_group,
+ * fmx_last_call_pieces, fmx_last_front_kernel -- is bit for bit, or equal to, what it is without the meter.  A handle that never switches it on allocates
+ * and launches nothing for it. */
+typedef struct fmx_rds_meter_record {
+    int64_t index;        /* the window w; a gap means windows that were not metered or that the reader lost */
+    int64_t end_sample;   /* 2560 (w + 1), in the channel's own RDS-sample count */
+    float   p_max;                                   /* the largest I I + Q Q */
+    float   ii_mean, qq_mean, iq_mean, i_mean, q_mean;   /* the sums / 2560.0f */
+} fmx_rds_meter_record;   /* 40 bytes */
+/* switches the RDS meter of a channel (-1: of every channel) on or off; from any thread, takes effect at the next call; switches no decoder */
+int  fmx_rds_meter_enable(fmx_handle h, int32_t channel, int32_t on);
+/* the records the channels first_channel .. first_channel + n_channels - 1 completed since this function last read them, oldest first, at most
+ * capacity_per_channel each (more stay for the next read): channel k's at out [k * capacity_per_channel ..], their number in n_records [k].  One
+ * read-out of the device for the whole range. */
+int  fmx_rds_meter_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rds_meter_record *out, int32_t capacity_per_channel, int32_t *n_records);
+/* The calibration of a channel's RDS meter, from the handle's own designed taps (computed on the host, in double; like fmx_get_taps it brings the
+ * handle's tap sets up to the current settings first, and needs no call to have been made):
+ *   gain        |z| per unit of sub-carrier amplitude in the demodulator output d: the real 57 kHz band-pass's response at 57 kHz (0.5000: only the
+ *               real part of the complex band-pass's result is kept), times 3 (the analytic-signal filter's factor), times the magnitude of the
+ *               decimator's complex DC gain (1.9459): 2.9188 at 192 kS/s;
+ *   phase0_deg  the chain's constant rotation, the argument of the decimator's complex DC gain (59.08 degrees): band-pass and analytic-signal filter are
+ *               linear in phase with a delay of 384 samples, whole periods of 19 and 57 kHz, and the mixer turns by minus three times the pilot's own
+ *               delayed phase.  With it phase_deg below refers to the pilot as transmitted;
+ *   path_57k    the static response, relative to DC, of what lies between the antenna and d for a small sub-carrier at 57 kHz: the channel's RF path
+ *               (the input filter in force with the two decimators, the mean of the sidebands at +-57 kHz) times the discriminator's own response
+ *               (sin x / x for the one-sample phase difference, x = pi 57000 / fmRate: 0.861).  FMX_E_UNSUPPORTED for the decoders
+ *               fmx_mod_hz_per_unit refuses. */
+typedef struct fmx_rds_meter_calib {
+    double gain, phase0_deg, path_57k;
+} fmx_rds_meter_calib;
+int  fmx_rds_meter_cal(fmx_handle h, int32_t channel, fmx_rds_meter_calib *out);
+/* The figures of one channel's records (host only, needs no device, all arithmetic in double).  With A, B, C, mi, mq the means over the n records of
+ * ii_mean, qq_mean, iq_mean, i_mean, q_mean:  a = A - mi^2, b = B - mq^2, c = C - mi mq (the covariance of I and Q), r = hypot ((a - b) / 2, c),
+ * l+ = (a + b) / 2 + r, l- = (a + b) / 2 - r (its eigenvalues), K = hz_per_unit / (gain path_57k), hz_per_unit from fmx_mod_hz_per_unit:
+ *   injection_rms_hz   sqrt (max (l+ - l-, 0)) K: the power on the sub-carrier's axis above the power across it, which is booked as noise;
+ *   injection_peak_hz  sqrt (max p_max) K;
+ *   carrier_hz         hypot (mi, mq) K: an unmodulated 57 kHz component (ARI, or leakage);
+ *   phase_deg          atan2 (2 c, a - b) / 2 in degrees, minus phase0_deg, folded into (-45, 135]: both nominal values, 0 and 90, are interior;
+ *   axis_db            10 log10 (l+ / l-); +HUGE_VAL where l- <= 0; -HUGE_VAL, with phase_deg 0, where l+ <= 0;
+ *   windows            n.
+ * n = 0 or a null pointer gives FMX_E_INVALID.
+ * What the injection figures mean: the sub-carrier as THIS chain's demodulator sees it, corrected for the static path.  The reference's two short decimators (25 taps and 3 taps: 0.869 and 0.899 at 57 kHz)
+ * make the receiver selective at 57 kHz, and a programme at full deviation moves the sidebands across that slope: under programme the figure
+ * reads low by what DESIGN.md 4.14 lists.  axis_db has a ceiling of its own, the unfiltered pilot PLL's jitter, tripled. */
+typedef struct fmx_rds_figures {
+    double  injection_rms_hz, injection_peak_hz, carrier_hz, phase_deg, axis_db;
+    int64_t windows;
+} fmx_rds_figures;
+int  fmx_rds_meter_figures(const fmx_rds_meter_record *recs, int32_t n, const fmx_rds_meter_calib *cal, double hz_per_unit, fmx_rds_figures *out);
+
 /* introspection used by the parity tests: the filter taps the kernels run with.
  * which: 0 front-end polyphase taps, 1 PSS low-pass, 2 audio+resampler FIR, 3 resampler alone,
  * 4 the noise squelch's two order-20 filters: [2][10] x (A1, A2, B1, B2), then the two gains (high-pass first),

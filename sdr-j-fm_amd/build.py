@@ -26,6 +26,7 @@ SOURCES = [
     ("fmx_meter.hip", ["-ffp-contract=off"]),      # (the modulation meter's sums are defined without fma: DESIGN 4.11)
     ("fmx_loud.hip", ["-ffp-contract=off"]),       # (the audio meter's recurrences are defined without fma: DESIGN 4.12)
     ("fmx_rx.hip", ["-ffp-contract=off"]),         # (the reception meter's sums are defined without fma: DESIGN 4.13)
+    ("fmx_rdsm.hip", ["-ffp-contract=off"]),       # (the RDS meter's sums are defined without fma: DESIGN 4.14)
     ("fmx_wide.hip", []),
     ("fmx_wide_rate.hip", []),
     ("fmx_survey.hip", []),

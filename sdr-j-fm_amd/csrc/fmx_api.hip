@@ -669,6 +669,19 @@ int ensure_rx_meter(fmx_handle h) {
     return FMX_OK;
 }
 
+// the RDS meter's buffers (fmx_rdsm.hip), allocated by the first call in which a channel's RDS meter is on and a decoder runs
+int ensure_rds_meter(fmx_handle h) {
+    if (h->rdsm_alloc) return FMX_OK;
+    const size_t C = (size_t)h->channels;
+    HIPCHK(hipDeviceSynchronize());
+    FMXCHK(h->mem.alloc(h->d_rdsm_state, C * rdsm::QUANT * rdsm::LANES, true));
+    FMXCHK(h->mem.alloc(h->d_rdsm_ring, C * rdsm::RING, true));
+    FMXCHK(h->mem.alloc(h->d_rdsm_jobs, C));
+    h->call_rdsm.assign(C, 0); h->rdsm_on_from.assign(C, -1); h->rdsm_produced.assign(C, 0); h->rd.rdsm.assign(C, 0);
+    h->rdsm_alloc = true;
+    return FMX_OK;
+}
+
 // the tiled work arrays of the demodulator pre-pass (fmx_demod.hip): limited / unlimited samples in, demodulator output out.  (Allocated by the first call
 // that needs them -- before run_call decides how the call is made: a call in pieces needs them too.)
 int ensure_prepass_arrays(fmx_handle h) {
@@ -725,6 +738,9 @@ int flush_mailbox(fmx_handle h) {
     // (a channel's RDS path runs while its decoder is on and stands still otherwise -- block filters, phase delay line, decimator and slicer
     // keep what they hold, as the reference's processor's do: nothing restarts when a decoder is switched; run_piece counts per channel)
     if (nd.any_rds) { const int rc = ensure_rds(h); if (rc) return rc; }
+    // (the RDS meter reads the path's own 24 kS/s ring and switches no decoder on: no part of CallNeeds, and nothing before a decoder runs)
+    if (!h->rdsm_alloc && nd.any_rds && std::any_of(h->user.begin(), h->user.end(), [](const ChanUser &u) { return u.rdsm; })) { const int rc = ensure_rds_meter(h); if (rc) return rc; }
+    if (h->rdsm_alloc) for (int c = 0; c < h->channels; c++) h->call_rdsm[(size_t)c] = h->user[(size_t)c].rdsm ? 1 : 0;
     if (nd.keep_taps && !h->w_diff_mem) {
         HIPCHK(hipDeviceSynchronize());
         FMXCHK(h->mem.alloc(h->w_diff_mem, (size_t)h->work_nj * h->pitch, true));
@@ -918,6 +934,40 @@ int stage_b(fmx_handle h, const CallGeom &G, int k, bool piped, int second, hipS
     return FMX_OK;
 }
 
+// the RDS meter: the metered channels' 24 kS/s samples of the piece, out of the path's rds24 ring, into their lane accumulators, every window that ends in
+// it into the record ring (fmx_rdsm.hip) -- on the RDS path's stream behind the piece's launch_rds, whose rds_mix_decim wrote the samples, and so ahead of the
+// next piece's writes.  Channel c's path had processed rds_nc0 [c] samples in front of the piece (< 0: its decoder is off, the channel gets no job and
+// nothing of its changes).  The bookkeeping is the host's (rdsm::piece); the kernel gets one job per channel that accumulates.
+int stage_rds_meter(fmx_handle h, const CallGeom &G, hipStream_t s) {
+    const int64_t nj = G.J1 - G.J0;
+    h->rdsm_jobs.clear();
+    {
+        std::lock_guard<std::mutex> lk(h->mtx);      // (fmx_rds_meter_records reads the counters from any thread)
+        for (int c = 0; c < h->channels; c++) {
+            const int64_t a = h->rds_nc0[(size_t)c];
+            if (a >= 0 && h->call_rdsm[(size_t)c] && !rdsm::ring_holds(a / 8, (a + nj) / 8))
+                return fail(FMX_E_TOO_LARGE, "the piece has more RDS samples than the path's 24 kS/s ring holds");
+        }
+        for (int c = 0; c < h->channels; c++) {
+            const int64_t a = h->rds_nc0[(size_t)c];
+            const rdsm::Piece p = rdsm::piece(h->call_rdsm[(size_t)c] != 0, a >= 0, h->rdsm_on_from[(size_t)c], a < 0 ? 0 : a / 8, a < 0 ? 0 : (a + nj) / 8,
+                                              h->rdsm_produced[(size_t)c]);
+            h->rdsm_on_from[(size_t)c] = p.on_from;
+            if (!p.job) continue;
+            h->rdsm_jobs.push_back(RdsmJob{p.first, (a + nj) / 8, c, (int32_t)p.slot(0)});
+            h->rdsm_produced[(size_t)c] = p.new_produced;
+        }
+    }
+    const size_t n = h->rdsm_jobs.size();
+    if (n == 0) return FMX_OK;
+    // (pageable source: the copy is staged before the call returns)
+    HIPCHK(hipMemcpyAsync(h->d_rdsm_jobs, h->rdsm_jobs.data(), sizeof(RdsmJob) * n, hipMemcpyHostToDevice, s));
+    RdsmArgs A{};
+    A.jobs = h->d_rdsm_jobs; A.rds24 = h->R.rds24; A.state = h->d_rdsm_state; A.ring = h->d_rdsm_ring; A.channels = h->channels;
+    launch_rdsm(A, (int)n, s); FMX_LAUNCHED();
+    return FMX_OK;
+}
+
 // the RDS path of the channels that decode it, each at its own block phase
 int stage_rds(fmx_handle h, const CallGeom &G, hipStream_t s) {
     const int64_t nj = G.J1 - G.J0;
@@ -936,7 +986,7 @@ int stage_rds(fmx_handle h, const CallGeom &G, hipStream_t s) {
         h->last_m0[(size_t)c] = a / 8; h->last_m1[(size_t)c] = (a + nj) / 8;
         h->rds_nc[(size_t)c] = a + nj;
     }
-    return FMX_OK;
+    return h->rdsm_alloc ? stage_rds_meter(h, G, s) : FMX_OK;
 }
 
 // scan mode: the scanning channels' fm samples of the call behind their carries, every complete block of 1024 into the record ring (fmx_scan.hip), on the
@@ -1602,6 +1652,15 @@ int fmx_rx_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
     const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
     for (int c = c0; c < c1; c++) h->user[(size_t)c].rx = on != 0;
+    return FMX_OK;
+}
+
+int fmx_rds_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
+    if (!h) return fail(FMX_E_INVALID, "null handle");
+    if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
+    std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes, and no decoder is switched)
+    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
+    for (int c = c0; c < c1; c++) h->user[(size_t)c].rdsm = on != 0;
     return FMX_OK;
 }
 

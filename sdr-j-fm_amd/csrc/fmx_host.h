@@ -10,6 +10,7 @@
 #include "fmx_meter.h"
 #include "fmx_loud.h"
 #include "fmx_rx.h"
+#include "fmx_rdsm.h"
 #include "fmx_rdsgroups.h"
 
 #include <algorithm>
@@ -95,6 +96,7 @@ struct ChanUser {
     bool    meter = false;       // the modulation meter (fmx_mod_meter_enable)
     bool    loud = false;        // the programme audio meter (fmx_audio_meter_enable)
     bool    rx = false;          // the reception meter (fmx_rx_meter_enable)
+    bool    rdsm = false;        // the RDS meter (fmx_rds_meter_enable)
 };
 
 struct ProfRec { hipEvent_t e[4]; int64_t in_samples, ch_samples; int n; };
@@ -116,11 +118,12 @@ struct Readers {
     std::vector<int64_t> mod;                // fmx_mod_records: records of fmx_handle_s::meter_produced
     std::vector<int64_t> audio;              // fmx_audio_records: records of fmx_handle_s::loud_produced
     std::vector<int64_t> rx;                 // fmx_rx_records: records of fmx_handle_s::rx_produced
+    std::vector<int64_t> rdsm;               // fmx_rds_meter_records: records of fmx_handle_s::rdsm_produced
     std::vector<uint8_t> reset_dec, reset_dec_all;   // resetRds / triggerFrequencyChange asked for the group decoder's reset: fmx_rds_decode's, fmx_rds_decode_all's (under mtx)
     std::vector<RdsGroupDecoderHost> dec, dec_all;   // fmx_rds_decode's decoders (the synchroniser on the host), fmx_rds_decode_all's (on the GPU: rds_sync)
     void init(size_t channels) {
         peaks.assign(channels, 0); bits.assign(channels, 0); dec_bits.assign(channels, 0); symbols.assign(channels, 0);
-        dec_groups.assign(channels, 0); groups.assign(channels, 0); scan.assign(channels, 0); mod.assign(channels, 0); audio.assign(channels, 0); rx.assign(channels, 0);
+        dec_groups.assign(channels, 0); groups.assign(channels, 0); scan.assign(channels, 0); mod.assign(channels, 0); audio.assign(channels, 0); rx.assign(channels, 0); rdsm.assign(channels, 0);
         reset_dec.assign(channels, 0); reset_dec_all.assign(channels, 0);
     }
 };
@@ -219,6 +222,15 @@ struct fmx_handle_s {
     float *d_rx_state = nullptr; fmx_rx_record *d_rx_ring = nullptr; RxJob *d_rx_jobs = nullptr;
     std::vector<RxJob> rx_jobs;
     std::vector<int64_t> rx_on_from, rx_produced;
+    // the RDS meter (fmx_rdsm.hip, fmx_rdsm.h): the channels whose meter is on in the piece being made (flush_mailbox); per channel the RDS sample of its own
+    // count since which its meter has been on in every piece that produced one (-1: it has not) and the records it has completed since fmx_create; the
+    // device keeps the lane accumulators of the window in progress and the record ring; allocated by the first call in which a meter is on and a decoder
+    // runs (ensure_rds_meter) -- a handle that never does has none of it
+    std::vector<uint8_t> call_rdsm;
+    bool rdsm_alloc = false;
+    float *d_rdsm_state = nullptr; fmx_rds_meter_record *d_rdsm_ring = nullptr; RdsmJob *d_rdsm_jobs = nullptr;
+    std::vector<RdsmJob> rdsm_jobs;
+    std::vector<int64_t> rdsm_on_from, rdsm_produced;
     std::atomic<int> stageb_form{0};     // FMX_P_STAGEB_FORM
     std::atomic<int> front_parts{0};     // FMX_P_FRONT_PARTS
     std::atomic<int> front_kernel{0};    // FMX_P_FRONT_KERNEL

@@ -463,6 +463,18 @@ struct RxArgs {
 };
 void launch_rx(const RxArgs &A, int n_jobs, hipStream_t s);
 
+// ---- the RDS meter (fmx_rdsm.hip, fmx_rdsm.h) ---------------------------------------------------------------------------
+// one metered channel of a piece: the RDS samples [first, m1) of its own count it accumulates, and the ring slot its first completed window goes to
+struct RdsmJob { int64_t first, m1; int32_t ch, slot0; };
+struct RdsmArgs {
+    const RdsmJob *jobs;          // [n_jobs] (copied per piece on the stream of the launch)
+    const float2 *rds24;          // the RDS path's 24 kS/s ring, [channels][RDS24_RING]
+    float *state;                 // [channels][rdsm::QUANT][rdsm::LANES] the lane accumulators of the window in progress
+    fmx_rds_meter_record *ring;   // [channels][rdsm::RING]
+    int32_t channels, pad;
+};
+void launch_rdsm(const RdsmArgs &A, int n_jobs, hipStream_t s);
+
 // ---- stage W: wide-band ingest (fmx_wide.hip; DESIGN.md "Stage W") ----------------------------------------------------------
 // One stream at K * 2 304 000 S/s feeds many outputs at 2 304 000 S/s: per-sample mix, T = 16 K + 1 real taps, / K.
 constexpr int W_RATE0 = 2304000;       // the narrow rate, and the circle of the output rotator's table

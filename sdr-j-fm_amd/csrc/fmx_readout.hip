@@ -1,11 +1,13 @@
 // fmx_readout.hip -- the entry points of include/fmx.h that only read a handle: metaData, peak levels, scope taps, tap sets, the RDS bits, symbols, groups
-// and decoders, scan records, the modulation meter's, the audio meter's and the reception meter's records, the PLL counters, the facts about the last call;
-// the host-only RDS helpers, the host-only loudness figures (fmx_audio_loudness) and the host-only reception figures (fmx_rx_quality_of).  A per-channel read-out waits for the device, asks its ring's producer for the count, and takes [from, from + count) out of one copy of the ring (read_ring); where each reader stands is in the
+// and decoders, scan records, the modulation meter's, the audio meter's, the reception meter's and the RDS meter's records, the PLL counters, the facts about
+// the last call; the host-only RDS helpers, the host-only loudness figures (fmx_audio_loudness), reception figures (fmx_rx_quality_of) and RDS meter's
+// calibration and figures (fmx_rds_meter_cal, fmx_rds_meter_figures).  A per-channel read-out waits for the device, asks its ring's producer for the count, and takes [from, from + count) out of one copy of the ring (read_ring); where each reader stands is in the
 // handle's Readers (fmx_host.h).  The two batch RDS read-outs wait for the handle's last call only and copy every channel's ring at once (rds_batch_fetch).
 #include "fmx_host.h"
 #include "fmx_design.h"
 
 #include <cmath>
+#include <complex>
 #include <cstring>
 
 namespace {
@@ -360,6 +362,111 @@ int fmx_rx_quality_of(const fmx_rx_record *recs, int32_t n, int32_t fmRate, fmx_
     Q.offset_hz = std::atan2(sim, sre) * (double)fmRate / (2.0 * design::kPi);
     Q.windows = n;
     *out = Q;
+    return FMX_OK;
+}
+
+int fmx_rds_meter_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rds_meter_record *out, int32_t capacity_per_channel, int32_t *n_records) {
+    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || capacity_per_channel < 0 ||
+        (n_channels > 0 && (!n_records || (capacity_per_channel > 0 && !out)))) return fail(FMX_E_INVALID, "bad argument");
+    for (int k = 0; k < n_channels; k++) n_records[k] = 0;
+    if (n_channels == 0 || !h->rdsm_alloc) return FMX_OK;
+    FMXCHK(device_idle(h));
+    std::lock_guard<std::mutex> lk(h->mtx);
+    std::vector<RingTake> takes((size_t)n_channels);
+    for (int k = 0; k < n_channels; k++) {
+        const size_t c = (size_t)(first_channel + k);
+        takes[(size_t)k] = ring_take(h->rdsm_produced[c], h->rd.rdsm[c], rdsm::RING, capacity_per_channel);      // (a reader that fell behind: the gap shows in `index`)
+    }
+    FMXCHK(read_rings(h->d_rdsm_ring + (size_t)first_channel * rdsm::RING, rdsm::RING, n_channels, takes.data(),
+                      [&](int k, int64_t i, const fmx_rds_meter_record &r) { out[(size_t)k * (size_t)capacity_per_channel + (size_t)i] = r; }));
+    for (int k = 0; k < n_channels; k++) { h->rd.rdsm[(size_t)(first_channel + k)] = takes[(size_t)k].next(); n_records[k] = (int32_t)takes[(size_t)k].count; }
+    return FMX_OK;
+}
+
+// the calibration of a channel's RDS meter (include/fmx.h), from the taps the handle runs with: the 57 kHz band-pass (ensure_rds: only the real part of
+// the complex kernel's result is kept), the analytic-signal filter's factor 3 (rds_spectrum), rdsDecimator's complex kernel; in front of the demodulator
+// the channel's front-end taps (with the input filter as a block machine on a handle that runs it so) and the one-sample phase difference
+int fmx_rds_meter_cal(fmx_handle h, int32_t channel, fmx_rds_meter_calib *out) {
+    if (!h || !out || channel < 0 || channel >= h->channels) return fail(FMX_E_INVALID, "bad argument");
+    // the response of real taps g [0 .. n) at `turns` cycles per sample, about the delay `centre`, in double
+    auto fir_response = [](const float *g, int n, int stride, double turns, double centre) -> std::complex<double> {
+        double re = 0.0, im = 0.0;
+        for (int i = 0; i < n; i++) {
+            const double a = -2.0 * design::kPi * turns * ((double)i - centre);
+            re += (double)g[(size_t)i * (size_t)stride] * std::cos(a); im += (double)g[(size_t)i * (size_t)stride] * std::sin(a);
+        }
+        return {re, im};
+    };
+    const int32_t fmRate = h->cfg.fmRate, inRate = h->cfg.inputRate;
+    std::vector<float> G;
+    int32_t decoder = 0, ola_bw = 0;
+    {
+        std::lock_guard<std::mutex> lk(h->mtx);
+        if (h->sets_dirty) { HIPCHK(hipSetDevice(h->cfg.device)); int rc = ensure_sets(h); if (rc) return rc; h->params_dirty = true; }
+        decoder = h->params[(size_t)channel].decoder;
+        if (h->ola_mode) ola_bw = h->user[(size_t)channel].bandwidth > 0 ? h->user[(size_t)channel].bandwidth : 0;
+        const FrontSet &fs = h->h_front_sets[(size_t)h->params[(size_t)channel].front_set];
+        const float *t = &h->h_front_taps[(size_t)h->params[(size_t)channel].front_set * A_TAPS_STRIDE];
+        G.assign(A_TAPS_STRIDE, 0.f);       // (FIR order: G [k], k = 12 d + off - r, as fmx_get_taps hands them out)
+        for (int d = 0; d < fs.nd; d++) for (int r = 0; r < DECIM; r++) {
+            const int k = 12 * d + fs.off - r;
+            if (k >= 0 && k < A_TAPS_STRIDE) G[(size_t)k] = t[(d + 1) * DECIM + r];
+        }
+    }
+    double hz = 0.0;
+    { const int rc = fmx_mod_hz_per_unit(decoder, fmRate, &hz); if (rc) return rc; }      // (FMX_E_UNSUPPORTED: the decoder's output is no frequency)
+    fmx_rds_meter_calib K{};
+    const double sub = 3.0 * 19000.0;
+    const std::vector<float> bp = design::bandpass(768, 3 * 19000 - 4800 / 2, 3 * 19000 + 4800 / 2, fmRate);
+    const std::complex<double> Hbp = fir_response(bp.data(), 768, 2, sub / (double)fmRate, 384.0);      // (the real parts: Re (a * s) = a * Re (s))
+    const std::vector<float> dk = design::decim_complex(11, 24000 / 2, fmRate);
+    std::complex<double> D0(0.0, 0.0);
+    for (int i = 0; i < 11; i++) D0 += std::complex<double>((double)dk[(size_t)2 * i], (double)dk[(size_t)2 * i + 1]);
+    K.gain = 3.0 * std::abs(Hbp) * std::abs(D0);
+    K.phase0_deg = (std::arg(D0) + std::arg(Hbp)) * 180.0 / design::kPi;
+    // the RF path: the sidebands of a small sub-carrier lie 57 kHz on either side of the carrier; the response relative to the carrier's, their mean
+    const double tr = sub / (double)inRate;
+    const double g0 = std::abs(fir_response(G.data(), (int)G.size(), 1, 0.0, 0.0));
+    double rf = g0 > 0.0 ? 0.5 * (std::abs(fir_response(G.data(), (int)G.size(), 1, tr, 0.0)) + std::abs(fir_response(G.data(), (int)G.size(), 1, -tr, 0.0))) / g0 : 0.0;
+    if (ola_bw > 0) {
+        const std::vector<float> L = design::lowpass(251, ola_bw / 2, inRate);      // (ola_take_settings)
+        const double l0 = std::abs(fir_response(L.data(), 251, 1, 0.0, 0.0));
+        rf *= 0.5 * (std::abs(fir_response(L.data(), 251, 1, tr, 0.0)) + std::abs(fir_response(L.data(), 251, 1, -tr, 0.0))) / l0;
+    }
+    const double x = design::kPi * sub / (double)fmRate;
+    K.path_57k = rf * std::sin(x) / x;
+    *out = K;
+    return FMX_OK;
+}
+
+// the figures of one channel's RDS-meter records (include/fmx.h): the covariance of I and Q, its eigenvalues and its axis
+int fmx_rds_meter_figures(const fmx_rds_meter_record *recs, int32_t n, const fmx_rds_meter_calib *cal, double hz_per_unit, fmx_rds_figures *out) {
+    if (!out || !recs || !cal || n <= 0) return fail(FMX_E_INVALID, "bad argument");
+    double A = 0.0, B = 0.0, Cq = 0.0, mi = 0.0, mq = 0.0, pmax = 0.0;
+    for (int32_t i = 0; i < n; i++) {
+        A += (double)recs[i].ii_mean; B += (double)recs[i].qq_mean; Cq += (double)recs[i].iq_mean;
+        mi += (double)recs[i].i_mean; mq += (double)recs[i].q_mean;
+        pmax = std::max(pmax, (double)recs[i].p_max);
+    }
+    A /= (double)n; B /= (double)n; Cq /= (double)n; mi /= (double)n; mq /= (double)n;
+    const double a = A - mi * mi, b = B - mq * mq, c = Cq - mi * mq;
+    const double r = std::hypot((a - b) / 2.0, c);
+    const double lp = (a + b) / 2.0 + r, lm = (a + b) / 2.0 - r;
+    const double K = hz_per_unit / (cal->gain * cal->path_57k);
+    fmx_rds_figures F{};
+    F.injection_rms_hz = std::sqrt(std::max(lp - lm, 0.0)) * K;
+    F.injection_peak_hz = std::sqrt(pmax) * K;
+    F.carrier_hz = std::hypot(mi, mq) * K;
+    if (lp <= 0.0) { F.phase_deg = 0.0; F.axis_db = -HUGE_VAL; }
+    else {
+        double ph = 0.5 * std::atan2(2.0 * c, a - b) * 180.0 / design::kPi - cal->phase0_deg;
+        ph = std::fmod(ph, 180.0);                 // (an axis: modulo 180)
+        if (ph <= -45.0) ph += 180.0; else if (ph > 135.0) ph -= 180.0;
+        F.phase_deg = ph;
+        F.axis_db = lm <= 0.0 ? HUGE_VAL : 10.0 * std::log10(lp / lm);
+    }
+    F.windows = n;
+    *out = F;
     return FMX_OK;
 }
 

@@ -39,7 +39,7 @@ EXPORTS = [
     "fmx_abi_version", "fmx_last_error", "fmx_create", "fmx_destroy", "fmx_set_param", "fmx_frames_for", "fmx_filter_change_due",
     "fmx_process_host", "fmx_process_device", "fmx_process_host_raw", "fmx_process_device_raw", "fmx_synchronize",
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
-    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rx_meter_enable", "fmx_rx_records", "fmx_rx_quality_of", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
+    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rx_meter_enable", "fmx_rx_records", "fmx_rx_quality_of", "fmx_rds_meter_enable", "fmx_rds_meter_records", "fmx_rds_meter_cal", "fmx_rds_meter_figures", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
     "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
     "fmx_wideband_survey_enable", "fmx_wideband_survey_read", "fmx_wideband_survey_stations",
     "fmx_wideband_create_rate", "fmx_wideband_outputs_for", "fmx_wideband_rate_taps", "fmx_wideband_survey_stations_rate",
@@ -168,6 +168,27 @@ class FmxRxQuality(C.Structure):
     _fields_ = [("level_dbfs", C.c_double), ("cnr_db", C.c_double), ("am_depth", C.c_double), ("offset_hz", C.c_double), ("windows", C.c_int64)]
 
 
+class FmxRdsMeterRecord(C.Structure):
+    _fields_ = [("index", C.c_int64), ("end_sample", C.c_int64), ("p_max", C.c_float), ("ii_mean", C.c_float), ("qq_mean", C.c_float),
+                ("iq_mean", C.c_float), ("i_mean", C.c_float), ("q_mean", C.c_float)]
+
+
+# fmx_rds_meter_record as a numpy record (Fmx.rds_meter_records)
+RDSM_DTYPE = np.dtype([("index", np.int64), ("end_sample", np.int64), ("p_max", np.float32), ("ii_mean", np.float32), ("qq_mean", np.float32),
+                       ("iq_mean", np.float32), ("i_mean", np.float32), ("q_mean", np.float32)])
+assert RDSM_DTYPE.itemsize == C.sizeof(FmxRdsMeterRecord) == 40
+RDSM_WINDOW = 2560            # RDS samples (24 kS/s, the channel's own count) per record: 106.7 ms
+
+
+class FmxRdsMeterCal(C.Structure):
+    _fields_ = [("gain", C.c_double), ("phase0_deg", C.c_double), ("path_57k", C.c_double)]
+
+
+class FmxRdsFigures(C.Structure):
+    _fields_ = [("injection_rms_hz", C.c_double), ("injection_peak_hz", C.c_double), ("carrier_hz", C.c_double), ("phase_deg", C.c_double),
+                ("axis_db", C.c_double), ("windows", C.c_int64)]
+
+
 class FmxRdsGroup(C.Structure):
     _fields_ = [("index", C.c_int64), ("end_bit", C.c_int64), ("block", C.c_uint16 * 4)]
 
@@ -261,6 +282,14 @@ def load_library(path=None):
     L.fmx_rx_records.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
     L.fmx_rx_quality_of.restype = C.c_int
     L.fmx_rx_quality_of.argtypes = [vp, i32, i32, C.POINTER(FmxRxQuality)]
+    L.fmx_rds_meter_enable.restype = C.c_int
+    L.fmx_rds_meter_enable.argtypes = [vp, i32, i32]
+    L.fmx_rds_meter_records.restype = C.c_int
+    L.fmx_rds_meter_records.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
+    L.fmx_rds_meter_cal.restype = C.c_int
+    L.fmx_rds_meter_cal.argtypes = [vp, i32, C.POINTER(FmxRdsMeterCal)]
+    L.fmx_rds_meter_figures.restype = C.c_int
+    L.fmx_rds_meter_figures.argtypes = [vp, i32, C.POINTER(FmxRdsMeterCal), C.c_double, C.POINTER(FmxRdsFigures)]
     L.fmx_mod_hz_per_unit.restype = C.c_int
     L.fmx_mod_hz_per_unit.argtypes = [i32, i32, C.POINTER(C.c_double)]
     L.fmx_rds_bits.restype = C.c_int
@@ -369,6 +398,20 @@ def rx_quality(records, fmRate=192000):
     if rc != FMX_OK:
         raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
     return {name: getattr(out, name) for name, _ in FmxRxQuality._fields_}
+
+
+def rds_meter_figures(records, cal, hz_per_unit):
+    """The figures of one channel's RDS-meter records (RDSM_DTYPE; include/fmx.h fmx_rds_meter_figures; host only, needs no device): a dict of
+    injection_rms_hz, injection_peak_hz, carrier_hz, phase_deg, axis_db and windows.  `cal` is what Fmx.rds_meter_cal returned (a dict of gain,
+    phase0_deg, path_57k), hz_per_unit what mod_hz_per_unit returned.  Raises FmxError (FMX_E_INVALID) for no records."""
+    L = load_library()
+    recs = np.ascontiguousarray(records, RDSM_DTYPE)
+    k = FmxRdsMeterCal(float(cal["gain"]), float(cal["phase0_deg"]), float(cal["path_57k"]))
+    out = FmxRdsFigures()
+    rc = L.fmx_rds_meter_figures(recs.ctypes.data if recs.size else None, int(recs.size), C.byref(k), float(hz_per_unit), C.byref(out))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
+    return {name: getattr(out, name) for name, _ in FmxRdsFigures._fields_}
 
 
 class Fmx:
@@ -522,6 +565,26 @@ class Fmx:
         n = (C.c_int32 * max(count, 1))()
         self._check(self.L.fmx_rx_records(self.h, first, count, out.ctypes.data, capacity, n))
         return [out[k, :n[k]].copy() for k in range(count)]
+
+    def rds_meter_enable(self, on=True, channel=-1):
+        """Switch the RDS meter of a channel (-1: of every channel) on or off, from the next call on (fmx_rds_meter_enable).  Switches no decoder."""
+        self._check(self.L.fmx_rds_meter_enable(self.h, int(channel), 1 if on else 0))
+
+    def rds_meter_records(self, first=0, count=None, capacity=64):
+        """The RDS meter's records since the last read, per channel of the range, oldest first (fmx_rds_meter_records): a list of numpy structured arrays
+        (RDSM_DTYPE: index, end_sample, p_max, ii_mean, qq_mean, iq_mean, i_mean, q_mean), one per window of 2560 of the channel's own 24 kS/s samples;
+        rds_meter_figures () turns a channel's records into injection, phase and axis ratio.  The library keeps the last 64 per channel."""
+        count = self.channels - first if count is None else count
+        out = np.zeros((max(count, 1), max(capacity, 1)), RDSM_DTYPE)
+        n = (C.c_int32 * max(count, 1))()
+        self._check(self.L.fmx_rds_meter_records(self.h, first, count, out.ctypes.data, capacity, n))
+        return [out[k, :n[k]].copy() for k in range(count)]
+
+    def rds_meter_cal(self, channel=0):
+        """The calibration of a channel's RDS meter from the handle's own taps (fmx_rds_meter_cal): a dict of gain, phase0_deg and path_57k."""
+        out = FmxRdsMeterCal()
+        self._check(self.L.fmx_rds_meter_cal(self.h, int(channel), C.byref(out)))
+        return {name: getattr(out, name) for name, _ in FmxRdsMeterCal._fields_}
 
     def rds_bits(self, channel=0, capacity=8192):
         buf = (C.c_uint8 * capacity)()
@@ -846,6 +909,12 @@ class FmProcessor:
     def pollReception(self):
         """The reception meter's records since the last poll (RX_DTYPE): power maximum, minimum, mean, mean square and lag-1 correlation per 50 ms window."""
         return self.fmx.rx_records(self.channel, 1)[0]
+
+    def setRdsMeter(self, on): self.fmx.rds_meter_enable(on, self.channel)
+
+    def pollRdsMeter(self):
+        """The RDS meter's records since the last poll (RDSM_DTYPE): power maximum and the second and first moments of I and Q per 2560 RDS samples."""
+        return self.fmx.rds_meter_records(self.channel, 1)[0]
 
     def isPilotLocked(self):
         m = self.fmx.meta(self.channel)

@@ -208,6 +208,20 @@ public:
         return n;
     }
     static bool receptionQuality(const fmx_rx_record *recs, int32_t n, fmx_rx_quality *q, int32_t fmRate = 192000) { return fmx_rx_quality_of(recs, n, fmRate, q) == FMX_OK; }
+    // the RDS meter (include/fmx.h fmx_rds_meter_records; nothing of the reference's): setRdsMeter switches it with the next block (it switches no RDS
+    // decoder on), pollRdsMeter calls `emit_fn(const fmx_rds_meter_record &)` once per window of 2560 RDS samples completed since the last poll, oldest
+    // first; rdsMeterCal is the channel's calibration from the handle's taps, rdsMeterFigures makes injection, phase and axis ratio of the records
+    void setRdsMeter(bool on) { if (h) check(fmx_rds_meter_enable(h, 0, on ? 1 : 0)); }
+    template <class F> int pollRdsMeter(F emit_fn) {
+        fmx_rds_meter_record r[64]; int32_t n = 0;
+        if (!h || fmx_rds_meter_records(h, 0, 1, r, 64, &n) != FMX_OK) return 0;
+        for (int32_t k = 0; k < n; k++) emit_fn(r[k]);
+        return n;
+    }
+    bool rdsMeterCal(fmx_rds_meter_calib *cal) { return h && check(fmx_rds_meter_cal(h, 0, cal)); }
+    static bool rdsMeterFigures(const fmx_rds_meter_record *recs, int32_t n, const fmx_rds_meter_calib *cal, double hz_per_unit, fmx_rds_figures *f) {
+        return fmx_rds_meter_figures(recs, n, cal, hz_per_unit, f) == FMX_OK;
+    }
     // the RDS picture of this processor's channel(s) in one read-out of the device (fmx_rds_decode_all: the block synchroniser has run on the GPU,
     // the group decoder runs here): what the rds classes' signals carried, infos[k] for channel first + k
     bool poll_rds(fmx_rds_info *infos, int32_t first = 0, int32_t count = 1) { return h && check(fmx_rds_decode_all(h, first, count, infos)); }
