@@ -615,6 +615,76 @@ typedef struct fmx_rds_figures {
 } fmx_rds_figures;
 int  fmx_rds_meter_figures(const fmx_rds_meter_record *recs, int32_t n, const fmx_rds_meter_calib *cal, double hz_per_unit, fmx_rds_figures *out);
 
+/* ---- The spectrum meter (nothing of the reference's: it hands these samples to its HF scope, fm-processor.cpp:417-421; contract: DESIGN.md 4.15).
+ * Per metered STREAM the power spectrum of the samples the handle is fed at inputRate -- exactly the values stage A converts (all four fmx_iq_formats,
+ * s16_denominator and stream_stride honoured), in front of RF DC removal, balance and oscillator -- as a mean and a max-hold per record.
+ * Grid: g counts a stream's input samples since fmx_create (all streams share it).  With S = `every` (1 .. 4096) and B = `blocks_per_record`
+ * (1 .. 4096), both handle-wide, block b is the samples [4096 S b, 4096 S b + 4096) -- the other 4096 (S - 1) samples of a period are not read: S = 1
+ * is the band survey's gap-free grid, S = 16 costs a sixteenth -- and record r the blocks [r B, r B + B).
+ * Arithmetic: the band survey's window w (periodic Hann, f64 rounded to f32), twiddles and 4096-point transform (fmx_survey.h make_window,
+ * make_twiddles, pass1 .. pass3, unchanged): p_b [k] = |sum_i w [i] x [4096 S b + i] exp (-2 pi i ik / 4096)|^2, and per bin k in f32
+ *     mean_r [k] = c  (p_rB [k] + p_rB+1 [k] + ... in block order, from 0),  c  = f32 (1 / (B sum w^2))        (the survey's accumulate)
+ *     peak_r [k] = c1 max_b p_b [k],                                          c1 = f32 (1 / sum w^2)
+ * White noise of power s^2 reads s^2 in mean; a steady carrier reads the same in both.  Bin k lies at k inputRate / 4096 Hz (k >= 2048: minus inputRate).
+ * Carried between calls per metered stream: the 0 .. 4095 samples of a block in progress, the sum and the maximum per bin, nothing else: records are bit
+ * for bit the same however a stream is cut into calls and a call into pieces (RDS pieces, overlapping pre-pass pieces, calls of one sample).
+ * Switch: per stream, from any thread, takes effect at the next call.  A stream's first block is the first that begins at or behind the first sample of
+ * the piece that switched it on; record r is delivered only if every one of its blocks was taken while the stream was on; switching off drops the
+ * record in progress.  The device keeps the last 4 records per metered stream: a reader that falls behind sees a gap in `index`.
+ * Everything else a handle delivers -- PCM, RDS, meta, taps, peaks, scan records, the four other meters' records, fmx_last_second_group,
+ * fmx_last_call_pieces, fmx_last_front_kernel -- is bit for bit, or equal to, what it is without the meter.  A handle that never switches it on allocates
+ * and launches nothing for it; memory (192 KB per stream) is allocated for the streams that are switched on. */
+typedef struct fmx_spectrum_record {
+    int64_t index;        /* the record r; a gap means records that were not metered or that the reader lost */
+    int64_t end_sample;   /* one past the last sample read: 4096 S ((r + 1) B - 1) + 4096, in the handle's input-sample count */
+    int32_t blocks;       /* B */
+    int32_t every;        /* S */
+} fmx_spectrum_record;   /* 24 bytes */
+/* blocks per record and `every`, handle-wide (default 16, 1); only while no stream's meter is on, else FMX_E_INVALID.  Record indices and every
+ * stream's read cursor start over on the new grid, and records not yet read are lost. */
+int  fmx_spectrum_setup(fmx_handle h, int32_t blocks_per_record, int32_t every);
+/* switches the spectrum meter of a stream (-1: of every stream) on or off; from any thread, takes effect at the next call */
+int  fmx_spectrum_enable(fmx_handle h, int32_t stream, int32_t on);
+/* the records of one stream completed since this function last read that stream, oldest first, at most `capacity` (more stay for the next read):
+ * recs [i], mean [4096 i ..], peak [4096 i ..] (peak may be NULL).  Waits for the handle's last call only, not for the device. */
+int  fmx_spectrum_read(fmx_handle h, int32_t stream, fmx_spectrum_record *recs, float *mean, float *peak, int32_t capacity, int32_t *n_records);
+/* The figures of one record (host only, needs no device, every sum in double; a bin's membership in a window is decided in integers: bin kp,
+ * -2048 .. 2047, lies inside |f - f0| <= d when |kp rate_hz - 4096 f0| <= 4096 d).  Bins with |f| < dc_guard_hz are left out of every sum: the meter
+ * reads in front of the RF DC removal.  A quantity that cannot be formed reads -HUGE_VAL.  All frequencies in the result are relative to centre_hz.
+ *   channel_db      10 log10 of the sum of mean over |f - centre| <= 100 kHz;
+ *   obw_lower_hz, obw_upper_hz, obw_hz
+ *                   within the span |f - centre| <= 150 kHz: the frequencies below and above which (1 - obw_fraction) / 2 of the span's power lies, a bin's
+ *                   power spread evenly over its width rate_hz / 4096 (ITU-R SM.443's beta / 2 method), and their distance;
+ *   xdb_hz          the distance between the outermost bins of the span whose mean lies less than x_db below the span's largest bin;
+ *   centroid_hz     the power-weighted mean of f - centre over the span;
+ *   adj_db [4]      for the offsets -2, -1, +1, +2 raster_hz: the power in +-100 kHz about centre + offset, minus channel_db; -HUGE_VAL where that
+ *                   window leaves |f| <= rate_hz / 2 - 50 kHz;
+ *   mask_margin_db, mask_worst_hz
+ *                   the smallest, over the bins with |f - centre| inside [mask [0].offset_hz, mask [n_mask - 1].offset_hz], of
+ *                   limit (|f - centre|) - (10 log10 (sum of peak over the bins within rbw_hz / 2 of f) - channel_db), the limit interpolated linearly in dB
+ *                   between the caller's break points, and where it is found.  Negative: violated.  Formed only when peak and mask are given.
+ * FMX_E_INVALID (fmx_last_error names the argument) for: struct_size; rate_hz outside [1000, 100 000 000]; |centre_hz| > rate_hz / 2; raster_hz outside
+ * [50 000, 1 000 000]; dc_guard_hz outside [0, 99 999]; obw_fraction outside (0, 1); x_db not positive and finite; rbw_hz outside [1, 200 000]; a mask of
+ * one point, of offsets that are negative, not finite or not ascending, or of limits that are not finite; an entry of mean or peak that is negative or
+ * not finite. */
+typedef struct fmx_spectrum_mask_point { double offset_hz, limit_db; } fmx_spectrum_mask_point;
+typedef struct fmx_spectrum_find {
+    int32_t struct_size;       /* sizeof(fmx_spectrum_find) */
+    int32_t rate_hz;           /* the stream's rate: the handle's inputRate */
+    int32_t centre_hz;         /* where the channel sits in the stream: its set_localOscillator value */
+    int32_t raster_hz;
+    int32_t dc_guard_hz;
+    int32_t rbw_hz;            /* e.g. 10 000 */
+    double  obw_fraction;      /* e.g. 0.99 */
+    double  x_db;              /* e.g. 26 */
+    const fmx_spectrum_mask_point *mask;   /* [n_mask] ascending |offset_hz|, or NULL */
+    int32_t n_mask, reserved;
+} fmx_spectrum_find;
+typedef struct fmx_spectrum_figs {
+    double channel_db, obw_hz, obw_lower_hz, obw_upper_hz, xdb_hz, centroid_hz, adj_db[4], mask_margin_db, mask_worst_hz;
+} fmx_spectrum_figs;
+int  fmx_spectrum_figures(const fmx_spectrum_find *cfg, const float *mean, const float *peak, fmx_spectrum_figs *out);
+
 /* introspection used by the parity tests: the filter taps the kernels run with.
  * which: 0 front-end polyphase taps, 1 PSS low-pass, 2 audio+resampler FIR, 3 resampler alone,
  * 4 the noise squelch's two order-20 filters: [2][10] x (A1, A2, B1, B2), then the two gains (high-pass first),

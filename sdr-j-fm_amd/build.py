@@ -30,6 +30,7 @@ SOURCES = [
     ("fmx_wide.hip", []),
     ("fmx_wide_rate.hip", []),
     ("fmx_survey.hip", []),
+    ("fmx_spec.hip", []),                          # (the spectrum meter shares the survey's transform: compiled as the survey is)
     # the host files (fmx_host.h): they design filters through fmx_design.h, whose taps must not depend on contraction either
     ("fmx_api.hip", ["-ffp-contract=off"]),
     ("fmx_readout.hip", ["-ffp-contract=off"]),

@@ -682,6 +682,50 @@ int ensure_rds_meter(fmx_handle h) {
     return FMX_OK;
 }
 
+// The spectrum meter's memory (fmx_spec.hip), under mtx: a slot for every stream whose meter is on and has none yet.  Memory is per slot -- 32 KB of carry,
+// 32 KB of sum and maximum, 128 KB of ring -- and grows to the slots in use: the arrays are allocated anew and the old slots copied.  The scratch of block
+// powers holds what a call of max_block samples completes for every slot, or spec::SCRATCH_BYTES where that is less (stage_spectrum cuts the piece then).
+int ensure_spectrum(fmx_handle h) {
+    const size_t NS = (size_t)h->streams;
+    if (h->spec_slot.empty()) {
+        h->spec_slot.assign(NS, -1); h->spec_on_from.assign(NS, -1); h->spec_tag.assign(NS * spec::RING, -1); h->rd.spec.assign(NS, 0); h->call_spec.assign(NS, 0);
+    }
+    int32_t need = h->spec_slots;
+    for (size_t s = 0; s < NS; s++) if (h->user_spec[s] && h->spec_slot[s] < 0) need++;
+    if (need > h->spec_cap) {
+        HIPCHK(hipDeviceSynchronize());
+        if (!h->d_spec_win) {
+            std::vector<float> win(spec::N); std::vector<float2> W(spec::N);
+            survey::make_window(win.data()); survey::make_twiddles(W.data());
+            FMXCHK(h->mem.upload(h->d_spec_win, win)); FMXCHK(h->mem.upload(h->d_spec_W, W));
+            HIPCHK(hipEventCreateWithFlags(&h->ev_spec, hipEventDisableTiming));
+        }
+        float2 *carry = nullptr; float *acc = nullptr, *ring = nullptr;
+        FMXCHK(h->mem.alloc(carry, (size_t)need * spec::N, true));
+        FMXCHK(h->mem.alloc(acc, (size_t)need * 2 * spec::N, true));
+        FMXCHK(h->mem.alloc(ring, (size_t)need * spec::RING * 2 * spec::N, true));
+        if (h->spec_slots > 0) {
+            const size_t k = (size_t)h->spec_slots;
+            HIPCHK(hipMemcpy(carry, h->d_spec_carry, sizeof(float2) * k * spec::N, hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(acc, h->d_spec_acc, sizeof(float) * k * 2 * spec::N, hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(ring, h->d_spec_ring, sizeof(float) * k * spec::RING * 2 * spec::N, hipMemcpyDeviceToDevice));
+            HIPCHK(hipDeviceSynchronize());
+        }
+        h->mem.release(h->d_spec_carry); h->mem.release(h->d_spec_acc); h->mem.release(h->d_spec_ring); h->mem.release(h->d_spec_jobs);
+        h->d_spec_carry = carry; h->d_spec_acc = acc; h->d_spec_ring = ring;
+        FMXCHK(h->mem.alloc(h->d_spec_jobs, (size_t)need));
+        const int64_t want = spec::scratch_blocks_for(need, (h->cfg.max_block + spec::N - 1) / spec::N + 1);
+        if (want > h->spec_scratch) {
+            h->mem.release(h->d_spec_power);
+            FMXCHK(h->mem.alloc(h->d_spec_power, (size_t)want * spec::N));
+            h->spec_scratch = want;
+        }
+        h->spec_cap = need;
+    }
+    for (size_t s = 0; s < NS; s++) if (h->user_spec[s] && h->spec_slot[s] < 0) h->spec_slot[s] = h->spec_slots++;
+    return FMX_OK;
+}
+
 // the tiled work arrays of the demodulator pre-pass (fmx_demod.hip): limited / unlimited samples in, demodulator output out.  (Allocated by the first call
 // that needs them -- before run_call decides how the call is made: a call in pieces needs them too.)
 int ensure_prepass_arrays(fmx_handle h) {
@@ -741,6 +785,17 @@ int flush_mailbox(fmx_handle h) {
     // (the RDS meter reads the path's own 24 kS/s ring and switches no decoder on: no part of CallNeeds, and nothing before a decoder runs)
     if (!h->rdsm_alloc && nd.any_rds && std::any_of(h->user.begin(), h->user.end(), [](const ChanUser &u) { return u.rdsm; })) { const int rc = ensure_rds_meter(h); if (rc) return rc; }
     if (h->rdsm_alloc) for (int c = 0; c < h->channels; c++) h->call_rdsm[(size_t)c] = h->user[(size_t)c].rdsm ? 1 : 0;
+    // (the spectrum meter reads the call's input and its own memory: no part of CallNeeds.  fmx_spectrum_setup's grid is taken over here, while no
+    // stream's meter is on: indices, cursors and what the ring held start over)
+    if (h->spec_setup_dirty) {
+        h->spec_B = h->spec_B_user; h->spec_S = h->spec_S_user; h->spec_setup_dirty = false;
+        std::fill(h->spec_on_from.begin(), h->spec_on_from.end(), -1); std::fill(h->spec_tag.begin(), h->spec_tag.end(), -1);
+        std::fill(h->rd.spec.begin(), h->rd.spec.end(), 0);
+    }
+    if (!h->user_spec.empty()) {
+        if (std::any_of(h->user_spec.begin(), h->user_spec.end(), [](uint8_t on) { return on != 0; })) { const int rc = ensure_spectrum(h); if (rc) return rc; }
+        if (!h->call_spec.empty()) h->call_spec = h->user_spec;
+    }
     if (nd.keep_taps && !h->w_diff_mem) {
         HIPCHK(hipDeviceSynchronize());
         FMXCHK(h->mem.alloc(h->w_diff_mem, (size_t)h->work_nj * h->pitch, true));
@@ -1080,6 +1135,50 @@ int stage_rx(fmx_handle h, const CallGeom &G, hipStream_t sa) {
     return FMX_OK;
 }
 
+// The spectrum meter: the metered streams' input samples of the piece through fmx_spec.hip, on the stream stage A ran on.  What the piece means on the
+// grid is spec::piece's integers; the metered streams go in groups, a group's blocks in chunks (spec::group_streams, spec::chunk_blocks), so that the
+// scratch holds every launch's block powers; the sums stay in block order, so nothing depends on the cutting.  The piece's last launch of a group writes
+// the carry.  Where stage A's stream is not the piece's own (overlapping pieces) the piece's stream waits for the meter: the caller's input buffer is
+// free when the call's last stream is.  The ring tags -- which record a slot holds -- change under mtx with the event fmx_spectrum_read waits for.
+int stage_spectrum(fmx_handle h, const CallGeom &G, const void *d_iq, hipStream_t s, hipStream_t sa) {
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const int32_t S = h->spec_S, B = h->spec_B;
+    const spec::Piece p = spec::piece(G.g0, G.n, S, B);
+    h->spec_jobs.clear();
+    for (int st = 0; st < h->streams; st++) {
+        if (!h->call_spec[(size_t)st]) { h->spec_on_from[(size_t)st] = -1; continue; }      // (off: the record in progress is dropped)
+        if (h->spec_on_from[(size_t)st] < 0) h->spec_on_from[(size_t)st] = G.g0;
+        h->spec_jobs.push_back(SpecJob{st, h->spec_slot[(size_t)st], spec::first_block(h->spec_on_from[(size_t)st], S)});
+    }
+    const int64_t nj = (int64_t)h->spec_jobs.size();
+    if (nj == 0) return FMX_OK;
+    if (h->spec_c_B != B) {                   // (c follows B: fmx_spectrum_setup)
+        std::vector<float> win(spec::N);
+        survey::make_window(win.data());
+        h->spec_c = survey::record_scale(win.data(), B); h->spec_c1 = survey::record_scale(win.data(), 1); h->spec_c_B = B;
+    }
+    // (pageable source: the copy is staged before the call returns)
+    HIPCHK(hipMemcpyAsync(h->d_spec_jobs, h->spec_jobs.data(), sizeof(SpecJob) * (size_t)nj, hipMemcpyHostToDevice, sa));
+    SpecArgs A{};
+    A.jobs = h->d_spec_jobs; A.src = d_iq; A.fmt = G.iq_format; A.qs = G.iq_scale; A.src_stride = G.stream_stride; A.g0 = G.g0; A.n = G.n; A.S = S; A.B = B;
+    A.fill = p.fill; A.fill_after = p.fill_after; A.append = p.append; A.carry_src = p.carry_src; A.c = h->spec_c; A.c1 = h->spec_c1;
+    A.window = h->d_spec_win; A.W = h->d_spec_W; A.carry = h->d_spec_carry; A.acc = h->d_spec_acc; A.ring = h->d_spec_ring; A.power = h->d_spec_power;
+    spec::launches(nj, h->spec_scratch, p.blocks, p.fill_after > 0, [&](int64_t j0, int64_t gn, int64_t done, int64_t nb, bool write_carry) {
+        A.job0 = (int32_t)j0; A.n_jobs = (int32_t)gn;
+        A.b = p.b0 + done; A.nb = (int32_t)nb; A.phase = (int32_t)(A.b % B);
+        A.write_carry = write_carry ? 1 : 0;
+        launch_spec(A, sa);
+    });
+    FMX_LAUNCHED();
+    HIPCHK(hipEventRecord(h->ev_spec, sa)); h->ev_spec_set = true;
+    if (sa != s) HIPCHK(hipStreamWaitEvent(s, h->ev_spec, 0));
+    const int64_t r_end = p.record0 + p.records;
+    for (const SpecJob &job : h->spec_jobs)
+        for (int64_t r = std::max(p.record0, r_end - spec::RING); r < r_end; r++)
+            if (spec::delivered(r, B, job.first)) h->spec_tag[(size_t)job.stream * spec::RING + (size_t)(r & (spec::RING - 1))] = r;
+    return FMX_OK;
+}
+
 // the scanning channels' frames of the call are zeros (their chain runs on: outside the scanning calls a channel is what it would have been)
 int stage_scan_mute(fmx_handle h, float2 *d_pcm, int64_t pcm_stride, int64_t frames, hipStream_t s) {
     const size_t n = h->call_scan.size();
@@ -1184,6 +1283,7 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     if ((rc = stage_a(h, G, d_iq, s, sa))) return rc;
     if (!h->call_scan.empty() && G.J1 > G.J0 && (rc = stage_scan(h, G, sa))) return rc;
     if (h->rx_alloc && G.J1 > G.J0 && (rc = stage_rx(h, G, sa))) return rc;
+    if (h->spec_cap > 0 && (rc = stage_spectrum(h, G, d_iq, s, sa))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[1], sa));
     G.stageb_form = h->stageb_form.load(); G.no_deemph = h->ola_mode ? 1 : 0;
     // a plain batch (no pre-pass, no RDS, no scope-tap rows: stage B as the whole kernel) runs stages B and C as two channel groups on two streams where it has
@@ -1546,7 +1646,7 @@ int fmx_destroy(fmx_handle h) {
     for (auto &pr : h->prof) for (int i = 0; i < 4; i++) (void)hipEventDestroy(pr.e[i]);
     for (hipEvent_t e : h->step_ev) if (e) (void)hipEventDestroy(e);
     if (h->rd_stream) { (void)hipStreamSynchronize(h->rd_stream); (void)hipStreamDestroy(h->rd_stream); }
-    for (hipEvent_t e : {h->ev_call, h->ev_in, h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {h->ev_call, h->ev_spec, h->ev_in, h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
     for (hipStream_t st : {h->stream, h->pipe_sA, h->pipe_sP, h->pipe_sB}) if (st) (void)hipStreamDestroy(st);
     h->mem.release_all(); h->rds_mem.release_all();
     delete h;
@@ -1661,6 +1761,27 @@ int fmx_rds_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes, and no decoder is switched)
     const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
     for (int c = c0; c < c1; c++) h->user[(size_t)c].rdsm = on != 0;
+    return FMX_OK;
+}
+
+int fmx_spectrum_setup(fmx_handle h, int32_t blocks_per_record, int32_t every) {
+    if (!h) return fail(FMX_E_INVALID, "null handle");
+    if (blocks_per_record < 1 || blocks_per_record > spec::MAX_B) return fail(FMX_E_INVALID, "blocks_per_record must be in [1, 4096]");
+    if (every < 1 || every > spec::MAX_S) return fail(FMX_E_INVALID, "every must be in [1, 4096]");
+    std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes the grid over at the next call)
+    if (std::any_of(h->user_spec.begin(), h->user_spec.end(), [](uint8_t on) { return on != 0; }))
+        return fail(FMX_E_INVALID, "fmx_spectrum_setup: a stream's spectrum meter is on");
+    h->spec_B_user = blocks_per_record; h->spec_S_user = every; h->spec_setup_dirty = true;
+    return FMX_OK;
+}
+
+int fmx_spectrum_enable(fmx_handle h, int32_t stream, int32_t on) {
+    if (!h) return fail(FMX_E_INVALID, "null handle");
+    if (stream < -1 || stream >= h->streams) return fail(FMX_E_INVALID, "stream out of range");
+    std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
+    if (h->user_spec.empty()) h->user_spec.assign((size_t)h->streams, 0);
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? h->streams : stream + 1;
+    for (int s = s0; s < s1; s++) h->user_spec[(size_t)s] = on != 0;
     return FMX_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "fmx_rx.h"
 #include "fmx_rdsm.h"
 #include "fmx_rdsgroups.h"
+#include "fmx_spec.h"
 
 #include <algorithm>
 #include <atomic>
@@ -119,6 +120,7 @@ struct Readers {
     std::vector<int64_t> audio;              // fmx_audio_records: records of fmx_handle_s::loud_produced
     std::vector<int64_t> rx;                 // fmx_rx_records: records of fmx_handle_s::rx_produced
     std::vector<int64_t> rdsm;               // fmx_rds_meter_records: records of fmx_handle_s::rdsm_produced
+    std::vector<int64_t> spec;               // fmx_spectrum_read, per STREAM: the next record index it hands out (sized by the meter's first use)
     std::vector<uint8_t> reset_dec, reset_dec_all;   // resetRds / triggerFrequencyChange asked for the group decoder's reset: fmx_rds_decode's, fmx_rds_decode_all's (under mtx)
     std::vector<RdsGroupDecoderHost> dec, dec_all;   // fmx_rds_decode's decoders (the synchroniser on the host), fmx_rds_decode_all's (on the GPU: rds_sync)
     void init(size_t channels) {
@@ -231,6 +233,19 @@ struct fmx_handle_s {
     float *d_rdsm_state = nullptr; fmx_rds_meter_record *d_rdsm_ring = nullptr; RdsmJob *d_rdsm_jobs = nullptr;
     std::vector<RdsmJob> rdsm_jobs;
     std::vector<int64_t> rdsm_on_from, rdsm_produced;
+    // the spectrum meter (fmx_spec.hip, fmx_spec.h), per STREAM: the user's switch (under mtx), the streams whose meter is on in the piece being made
+    // (flush_mailbox), the input sample of the piece that switched it on (-1: off), its slot in the meter's device memory (-1: none yet; a stream keeps
+    // its slot) and per ring slot the record it holds (-1: none).  B and S in force, and what fmx_spectrum_setup asked for (taken over by flush_mailbox).
+    // The device keeps per slot the carry, sum and maximum, and the ring; memory grows with the streams switched on (ensure_spectrum) -- a handle that
+    // never switches the meter on has none of it
+    std::vector<uint8_t> user_spec, call_spec;
+    std::vector<int64_t> spec_on_from; std::vector<int32_t> spec_slot; std::vector<int64_t> spec_tag;
+    int32_t spec_B = 16, spec_S = 1, spec_B_user = 16, spec_S_user = 1; bool spec_setup_dirty = false;
+    int32_t spec_slots = 0, spec_cap = 0; int64_t spec_scratch = 0;      // slots in use, slots allocated, blocks of scratch allocated
+    float spec_c = 0.f, spec_c1 = 0.f; int32_t spec_c_B = 0;            // 1 / (B sum w^2) for B = spec_c_B, 1 / sum w^2
+    float2 *d_spec_carry = nullptr, *d_spec_W = nullptr; float *d_spec_acc = nullptr, *d_spec_ring = nullptr, *d_spec_power = nullptr, *d_spec_win = nullptr;
+    SpecJob *d_spec_jobs = nullptr; std::vector<SpecJob> spec_jobs;
+    hipEvent_t ev_spec = nullptr; bool ev_spec_set = false;             // behind the last piece's spectrum kernels: what fmx_spectrum_read waits for
     std::atomic<int> stageb_form{0};     // FMX_P_STAGEB_FORM
     std::atomic<int> front_parts{0};     // FMX_P_FRONT_PARTS
     std::atomic<int> front_kernel{0};    // FMX_P_FRONT_KERNEL

@@ -536,6 +536,30 @@ struct SurveyArgs {
 };
 void launch_survey(const SurveyArgs &A, int streams, hipStream_t s);
 
+// ---- the spectrum meter (fmx_spec.hip, fmx_spec.h) -------------------------------------------------------------------
+// one metered stream of a piece: the handle's stream, its slot in the meter's memory, and the first block it takes (spec::first_block)
+struct SpecJob { int32_t stream, slot; int64_t first; };
+// One launch pair: the jobs [job0, job0 + n_jobs) and the blocks [b, b + nb) of the piece [g0, g0 + n) -- a chunk of a group (spec::chunk_blocks,
+// spec::group_streams) -- through the transform into `power`, then folded in block order into `acc` and, at record ends, into the ring.  The piece's last
+// fold (write_carry) also writes the samples carried behind the piece.
+struct SpecArgs {
+    const SpecJob *jobs;                       // [all jobs of the piece] (copied per piece on the stream of the launch)
+    const void *src; int32_t fmt; float qs;    // the piece's input as stage A reads it
+    int64_t src_stride, g0, n;
+    int32_t S, B;
+    int32_t fill, fill_after, append, write_carry;   // spec::Piece
+    int64_t carry_src;
+    int64_t b; int32_t nb, phase;              // the chunk: its first block, its blocks, b mod B
+    int32_t job0, n_jobs;
+    float c, c1;                               // 1 / (B sum w^2), 1 / sum w^2
+    const float *window; const float2 *W;      // [4096] each
+    float2 *carry;                             // [slots][4096] converted samples of the block in progress
+    float *acc;                                // [slots][2][4096] sum, maximum
+    float *ring;                               // [slots][spec::RING][2][4096] mean, peak
+    float *power;                              // [n_jobs][nb][4096] the chunk's block powers (at most spec::SCRATCH_BYTES)
+};
+void launch_spec(const SpecArgs &A, hipStream_t s);
+
 void launch_front(const DeviceTables &T, const DeviceBuffers &B, const CallGeom &G, const void *iq,
                   int channels, hipStream_t s);
 // fmx_front4.hip: whole tiles of the call front4_kernel can take (0: none), and its launch over that many

@@ -470,6 +470,45 @@ int fmx_rds_meter_figures(const fmx_rds_meter_record *recs, int32_t n, const fmx
     return FMX_OK;
 }
 
+// the spectrum meter's records of one stream: which record a ring slot holds is the host's (fmx_handle_s::spec_tag); behind the handle's last call only
+int fmx_spectrum_read(fmx_handle h, int32_t stream, fmx_spectrum_record *recs, float *mean, float *peak, int32_t capacity, int32_t *n_records) {
+    if (!h || !n_records) return fail(FMX_E_INVALID, "null argument");
+    *n_records = 0;
+    if (stream < 0 || stream >= h->streams) return fail(FMX_E_INVALID, "stream out of range");
+    if (capacity < 0 || (capacity > 0 && (!recs || !mean))) return fail(FMX_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (h->spec_tag.empty() || capacity == 0) return FMX_OK;
+    int64_t have[spec::RING]; int n = 0;
+    for (int k = 0; k < spec::RING; k++) {
+        const int64_t r = h->spec_tag[(size_t)stream * spec::RING + (size_t)k];
+        if (r >= h->rd.spec[(size_t)stream]) have[n++] = r;      // (older ones were read, or overwritten: the gap shows in `index`)
+    }
+    std::sort(have, have + n);
+    n = std::min<int>(n, capacity);
+    if (n == 0) return FMX_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (!h->rd_stream) HIPCHK(hipStreamCreateWithFlags(&h->rd_stream, hipStreamNonBlocking));
+    if (h->ev_spec_set) HIPCHK(hipStreamWaitEvent(h->rd_stream, h->ev_spec, 0));
+    const float *ring = h->d_spec_ring + (size_t)h->spec_slot[(size_t)stream] * spec::RING * 2 * spec::N;
+    for (int i = 0; i < n; i++) {
+        const int64_t r = have[i];
+        recs[i] = fmx_spectrum_record{r, spec::record_end(r, h->spec_B, h->spec_S), h->spec_B, h->spec_S};
+        const float *slot = ring + (size_t)(r & (spec::RING - 1)) * 2 * spec::N;
+        HIPCHK(hipMemcpyAsync(mean + (size_t)i * spec::N, slot, sizeof(float) * spec::N, hipMemcpyDeviceToHost, h->rd_stream));
+        if (peak) HIPCHK(hipMemcpyAsync(peak + (size_t)i * spec::N, slot + spec::N, sizeof(float) * spec::N, hipMemcpyDeviceToHost, h->rd_stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->rd_stream));
+    h->rd.spec[(size_t)stream] = have[n - 1] + 1;
+    *n_records = n;
+    return FMX_OK;
+}
+
+int fmx_spectrum_figures(const fmx_spectrum_find *cfg, const float *mean, const float *peak, fmx_spectrum_figs *out) {
+    const char *why = "";
+    const int rc = spec::figures(cfg, mean, peak, out, &why);
+    return rc == FMX_OK ? FMX_OK : fail(rc, why);
+}
+
 int64_t fmx_pll_replays(fmx_handle h, int32_t channel) { return sum_chan_states(h, channel, [](const ChanState &s) { return s.pll_replays; }); }
 int64_t fmx_pll_exact_segments(fmx_handle h, int32_t channel) { return sum_chan_states(h, channel, [](const ChanState &s) { return s.pll_exact_segs; }); }
 int32_t fmx_last_front_kernel(fmx_handle h) { return h ? h->last_front_kernel : 0; }

@@ -39,7 +39,7 @@ EXPORTS = [
     "fmx_abi_version", "fmx_last_error", "fmx_create", "fmx_destroy", "fmx_set_param", "fmx_frames_for", "fmx_filter_change_due",
     "fmx_process_host", "fmx_process_device", "fmx_process_host_raw", "fmx_process_device_raw", "fmx_synchronize",
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
-    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rx_meter_enable", "fmx_rx_records", "fmx_rx_quality_of", "fmx_rds_meter_enable", "fmx_rds_meter_records", "fmx_rds_meter_cal", "fmx_rds_meter_figures", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
+    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rx_meter_enable", "fmx_rx_records", "fmx_rx_quality_of", "fmx_rds_meter_enable", "fmx_rds_meter_records", "fmx_rds_meter_cal", "fmx_rds_meter_figures", "fmx_spectrum_setup", "fmx_spectrum_enable", "fmx_spectrum_read", "fmx_spectrum_figures", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
     "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
     "fmx_wideband_survey_enable", "fmx_wideband_survey_read", "fmx_wideband_survey_stations",
     "fmx_wideband_create_rate", "fmx_wideband_outputs_for", "fmx_wideband_rate_taps", "fmx_wideband_survey_stations_rate",
@@ -86,6 +86,32 @@ SURVEY_RECORD_DTYPE = np.dtype([("index", np.int64), ("end_sample", np.int64), (
 SURVEY_STATION_DTYPE = np.dtype([("offset_hz", np.int32), ("level_db", np.float32), ("snr_db", np.float32), ("reserved", np.int32)])
 assert SURVEY_RECORD_DTYPE.itemsize == C.sizeof(FmxSurveyRecord) and SURVEY_STATION_DTYPE.itemsize == C.sizeof(FmxSurveyStation)
 SURVEY_BINS = 4096
+
+
+class FmxSpectrumRecord(C.Structure):
+    _fields_ = [("index", C.c_int64), ("end_sample", C.c_int64), ("blocks", C.c_int32), ("every", C.c_int32)]
+
+
+class FmxSpectrumMaskPoint(C.Structure):
+    _fields_ = [("offset_hz", C.c_double), ("limit_db", C.c_double)]
+
+
+class FmxSpectrumFind(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("rate_hz", C.c_int32), ("centre_hz", C.c_int32), ("raster_hz", C.c_int32), ("dc_guard_hz", C.c_int32),
+                ("rbw_hz", C.c_int32), ("obw_fraction", C.c_double), ("x_db", C.c_double), ("mask", C.POINTER(FmxSpectrumMaskPoint)),
+                ("n_mask", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FmxSpectrumFigs(C.Structure):
+    _fields_ = [("channel_db", C.c_double), ("obw_hz", C.c_double), ("obw_lower_hz", C.c_double), ("obw_upper_hz", C.c_double), ("xdb_hz", C.c_double),
+                ("centroid_hz", C.c_double), ("adj_db", C.c_double * 4), ("mask_margin_db", C.c_double), ("mask_worst_hz", C.c_double)]
+
+
+# fmx_spectrum_record as a numpy record (Fmx.spectrum_read)
+SPECTRUM_RECORD_DTYPE = np.dtype([("index", np.int64), ("end_sample", np.int64), ("blocks", np.int32), ("every", np.int32)])
+assert SPECTRUM_RECORD_DTYPE.itemsize == C.sizeof(FmxSpectrumRecord) == 24
+SPECTRUM_BINS = 4096
+SPECTRUM_RING = 4             # records the library keeps per metered stream
 
 
 class FmxMeta(C.Structure):
@@ -290,6 +316,14 @@ def load_library(path=None):
     L.fmx_rds_meter_cal.argtypes = [vp, i32, C.POINTER(FmxRdsMeterCal)]
     L.fmx_rds_meter_figures.restype = C.c_int
     L.fmx_rds_meter_figures.argtypes = [vp, i32, C.POINTER(FmxRdsMeterCal), C.c_double, C.POINTER(FmxRdsFigures)]
+    L.fmx_spectrum_setup.restype = C.c_int
+    L.fmx_spectrum_setup.argtypes = [vp, i32, i32]
+    L.fmx_spectrum_enable.restype = C.c_int
+    L.fmx_spectrum_enable.argtypes = [vp, i32, i32]
+    L.fmx_spectrum_read.restype = C.c_int
+    L.fmx_spectrum_read.argtypes = [vp, i32, vp, vp, vp, i32, C.POINTER(i32)]
+    L.fmx_spectrum_figures.restype = C.c_int
+    L.fmx_spectrum_figures.argtypes = [C.POINTER(FmxSpectrumFind), vp, vp, C.POINTER(FmxSpectrumFigs)]
     L.fmx_mod_hz_per_unit.restype = C.c_int
     L.fmx_mod_hz_per_unit.argtypes = [i32, i32, C.POINTER(C.c_double)]
     L.fmx_rds_bits.restype = C.c_int
@@ -398,6 +432,32 @@ def rx_quality(records, fmRate=192000):
     if rc != FMX_OK:
         raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
     return {name: getattr(out, name) for name, _ in FmxRxQuality._fields_}
+
+
+def spectrum_figures(mean, peak=None, rate_hz=2304000, centre_hz=0, raster_hz=100000, dc_guard_hz=0, obw_fraction=0.99, x_db=26.0, rbw_hz=10000,
+                     mask=None):
+    """The figures of one spectrum-meter record (include/fmx.h fmx_spectrum_figures; host only, needs no device): a dict of channel_db, obw_hz,
+    obw_lower_hz, obw_upper_hz, xdb_hz, centroid_hz, adj_db (a list for the offsets -2, -1, +1, +2 rasters), mask_margin_db and mask_worst_hz; frequencies
+    relative to centre_hz, -inf for a quantity that cannot be formed.  mask: the caller's break points [(|offset_hz|, limit_db), ...] or None.  Raises
+    FmxError (FMX_E_INVALID) for an argument the library refuses."""
+    L = load_library()
+    mean = np.ascontiguousarray(mean, np.float32)
+    assert mean.shape == (SPECTRUM_BINS,)
+    if peak is not None:
+        peak = np.ascontiguousarray(peak, np.float32)
+        assert peak.shape == (SPECTRUM_BINS,)
+    pts = None
+    if mask is not None:
+        pts = (FmxSpectrumMaskPoint * max(len(mask), 1))(*[FmxSpectrumMaskPoint(float(o), float(l)) for o, l in mask])
+    cfg = FmxSpectrumFind(C.sizeof(FmxSpectrumFind), int(rate_hz), int(centre_hz), int(raster_hz), int(dc_guard_hz), int(rbw_hz), float(obw_fraction),
+                          float(x_db), pts, len(mask) if mask is not None else 0, 0)
+    out = FmxSpectrumFigs()
+    rc = L.fmx_spectrum_figures(C.byref(cfg), mean.ctypes.data, peak.ctypes.data if peak is not None else None, C.byref(out))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
+    figs = {name: getattr(out, name) for name, _ in FmxSpectrumFigs._fields_}
+    figs["adj_db"] = list(out.adj_db)
+    return figs
 
 
 def rds_meter_figures(records, cal, hz_per_unit):
@@ -579,6 +639,28 @@ class Fmx:
         n = (C.c_int32 * max(count, 1))()
         self._check(self.L.fmx_rds_meter_records(self.h, first, count, out.ctypes.data, capacity, n))
         return [out[k, :n[k]].copy() for k in range(count)]
+
+    def spectrum_setup(self, blocks_per_record=16, every=1):
+        """The spectrum meter's grid, handle-wide (fmx_spectrum_setup): blocks of 4096 input samples per record and `every` (block b begins at input
+        sample 4096 * every * b).  Only while no stream's meter is on."""
+        self._check(self.L.fmx_spectrum_setup(self.h, int(blocks_per_record), int(every)))
+
+    def spectrum_meter(self, on=True, stream=-1):
+        """Switch the spectrum meter of a stream (-1: of every stream) on or off, from the next call on (fmx_spectrum_enable)."""
+        self._check(self.L.fmx_spectrum_enable(self.h, int(stream), 1 if on else 0))
+
+    spectrum_enable = spectrum_meter
+
+    def spectrum_read(self, stream=0, capacity=SPECTRUM_RING, peak=True):
+        """The records of `stream` completed since its last read, oldest first (fmx_spectrum_read) -> (records as SPECTRUM_RECORD_DTYPE, mean [n, 4096]
+        f32, peak [n, 4096] f32 or None); spectrum_figures () turns one record into bandwidth, adjacent-channel and mask figures.  The library keeps the
+        last 4 per metered stream."""
+        recs = np.zeros(max(capacity, 1), SPECTRUM_RECORD_DTYPE)
+        mean = np.zeros((max(capacity, 1), SPECTRUM_BINS), np.float32)
+        pk = np.zeros((max(capacity, 1), SPECTRUM_BINS), np.float32) if peak else None
+        n = C.c_int32()
+        self._check(self.L.fmx_spectrum_read(self.h, int(stream), recs.ctypes.data, mean.ctypes.data, pk.ctypes.data if peak else None, int(capacity), C.byref(n)))
+        return recs[:n.value].copy(), mean[:n.value].copy(), (pk[:n.value].copy() if peak else None)
 
     def rds_meter_cal(self, channel=0):
         """The calibration of a channel's RDS meter from the handle's own taps (fmx_rds_meter_cal): a dict of gain, phase0_deg and path_57k."""
@@ -915,6 +997,12 @@ class FmProcessor:
     def pollRdsMeter(self):
         """The RDS meter's records since the last poll (RDSM_DTYPE): power maximum and the second and first moments of I and Q per 2560 RDS samples."""
         return self.fmx.rds_meter_records(self.channel, 1)[0]
+
+    def setSpectrumMeter(self, on, stream=-1): self.fmx.spectrum_meter(on, stream)
+
+    def pollSpectrum(self, stream=0):
+        """The spectrum meter's records of a stream since the last poll: (records as SPECTRUM_RECORD_DTYPE, mean [n, 4096], peak [n, 4096])."""
+        return self.fmx.spectrum_read(stream)
 
     def isPilotLocked(self):
         m = self.fmx.meta(self.channel)

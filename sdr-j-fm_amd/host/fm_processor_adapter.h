@@ -222,6 +222,22 @@ public:
     static bool rdsMeterFigures(const fmx_rds_meter_record *recs, int32_t n, const fmx_rds_meter_calib *cal, double hz_per_unit, fmx_rds_figures *f) {
         return fmx_rds_meter_figures(recs, n, cal, hz_per_unit, f) == FMX_OK;
     }
+    // the spectrum meter (include/fmx.h fmx_spectrum_*; the reference hands these samples to its HF scope): setSpectrumGrid sets blocks per record and
+    // `every` while the meter is off, setSpectrumMeter switches it with the next block, pollSpectrum calls
+    // `emit_fn(const fmx_spectrum_record &, const float *mean, const float *peak)` (4096 bins each) once per record of this processor's stream completed
+    // since the last poll, oldest first; spectrumFigures makes bandwidth, adjacent-channel and mask figures of one record
+    bool setSpectrumGrid(int32_t blocks_per_record, int32_t every) { return h && check(fmx_spectrum_setup(h, blocks_per_record, every)); }
+    void setSpectrumMeter(bool on) { if (h) check(fmx_spectrum_enable(h, 0, on ? 1 : 0)); }
+    template <class F> int pollSpectrum(F emit_fn) {
+        fmx_spectrum_record r[4]; int32_t n = 0;
+        std::vector<float> mean(4 * 4096), peak(4 * 4096);
+        if (!h || fmx_spectrum_read(h, 0, r, mean.data(), peak.data(), 4, &n) != FMX_OK) return 0;
+        for (int32_t k = 0; k < n; k++) emit_fn(r[k], mean.data() + (size_t)k * 4096, peak.data() + (size_t)k * 4096);
+        return n;
+    }
+    static bool spectrumFigures(const fmx_spectrum_find *cfg, const float *mean, const float *peak, fmx_spectrum_figs *f) {
+        return fmx_spectrum_figures(cfg, mean, peak, f) == FMX_OK;
+    }
     // the RDS picture of this processor's channel(s) in one read-out of the device (fmx_rds_decode_all: the block synchroniser has run on the GPU,
     // the group decoder runs here): what the rds classes' signals carried, infos[k] for channel first + k
     bool poll_rds(fmx_rds_info *infos, int32_t first = 0, int32_t count = 1) { return h && check(fmx_rds_decode_all(h, first, count, infos)); }

@@ -1,0 +1,62 @@
+// spec_adapter_demo.cpp -- the spectrum meter through the C++ adapter (sdr-j-fm_amd/host/fm_processor_adapter.h): setSpectrumGrid (2, 1),
+// setSpectrumMeter, blocks of the file, pollSpectrum after every block, spectrumFigures over the last record.  Writes per record its index (as f32), mean
+// and peak (4096 f32 each) to the output file and prints `records <n> channel <dB> obw <Hz> centroid <Hz>`.  Used by tests/test_gpu_spectrum.py;
+// tests/test_spec_cpu.py compiles it and runs the part that needs no device.
+#include <cstdio>
+#include <cstring>
+#include "fm_processor_adapter.h"
+
+struct MemDevice : fmx_host::DeviceHandler {
+    std::vector<std::complex<float>> data; size_t pos = 0;
+    int32_t Samples() override { return (int32_t)(data.size() - pos); }
+    int32_t getSamples(std::complex<float> *dst, int32_t n) override {
+        std::memcpy(dst, data.data() + pos, sizeof(std::complex<float>) * (size_t)n); pos += (size_t)n; return n;
+    }
+};
+struct NullSink : fmx_host::AudioSink {
+    int32_t putSamples(std::complex<float> *, int32_t n) override { return n; }
+};
+
+int main(int argc, char **argv) {
+    static_assert(sizeof(fmx_spectrum_record) == 24, "fmx_spectrum_record is 24 bytes");
+    fmx_spectrum_find cfg{};
+    cfg.struct_size = (int32_t)sizeof(cfg); cfg.rate_hz = 2304000; cfg.centre_hz = 0; cfg.raster_hz = 100000; cfg.dc_guard_hz = 0; cfg.rbw_hz = 10000;
+    cfg.obw_fraction = 0.99; cfg.x_db = 26.0;
+    fmx_spectrum_figs f0;
+    std::vector<float> flat(4096, 1.0f);
+    cfg.raster_hz = 1;                                                                     // (refused, and needs no device)
+    if (fmx_host::FmProcessor::spectrumFigures(&cfg, flat.data(), nullptr, &f0)) return 4;
+    cfg.raster_hz = 100000;
+    if (!fmx_host::FmProcessor::spectrumFigures(&cfg, flat.data(), nullptr, &f0)) return 4;
+    std::printf("figures 1 centroid %.6f\n", f0.centroid_hz);
+    if (argc < 3) { std::fprintf(stderr, "usage: %s iq.f32 records.bin\n", argv[0]); return 2; }
+    MemDevice dev; NullSink sink;
+    FILE *fi = std::fopen(argv[1], "rb");
+    if (!fi) return 2;
+    std::fseek(fi, 0, SEEK_END); long bytes = std::ftell(fi); std::fseek(fi, 0, SEEK_SET);
+    dev.data.resize((size_t)bytes / sizeof(std::complex<float>));
+    if (std::fread(dev.data.data(), 1, (size_t)bytes, fi) != (size_t)bytes) return 2;
+    std::fclose(fi);
+    fmx_host::FmProcessor p(&dev, &sink);
+    if (!p.ok()) { std::printf("ok 0 error %s\n", p.lastError().c_str()); return 3; }
+    if (!p.setSpectrumGrid(2, 1)) { std::fprintf(stderr, "fmx: %s\n", p.lastError().c_str()); return 1; }
+    p.setSpectrumMeter(true);
+    FILE *fo = std::fopen(argv[2], "wb");
+    if (!fo) return 2;
+    size_t records = 0;
+    std::vector<float> last_mean(4096), last_peak(4096);
+    while (dev.Samples() >= 16384) {
+        if (!p.run_block()) { std::fprintf(stderr, "fmx: %s\n", p.lastError().c_str()); return 1; }
+        p.pollSpectrum([&](const fmx_spectrum_record &r, const float *mean, const float *peak) {
+            const float index = (float)r.index;
+            std::fwrite(&index, sizeof(float), 1, fo); std::fwrite(mean, sizeof(float), 4096, fo); std::fwrite(peak, sizeof(float), 4096, fo);
+            std::memcpy(last_mean.data(), mean, sizeof(float) * 4096); std::memcpy(last_peak.data(), peak, sizeof(float) * 4096);
+            records++;
+        });
+    }
+    std::fclose(fo);
+    fmx_spectrum_figs f{};
+    if (records && !fmx_host::FmProcessor::spectrumFigures(&cfg, last_mean.data(), last_peak.data(), &f)) return 1;
+    std::printf("records %zu channel %.17g obw %.17g centroid %.17g\n", records, f.channel_db, f.obw_hz, f.centroid_hz);
+    return 0;
+}
