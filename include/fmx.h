@@ -685,6 +685,86 @@ typedef struct fmx_spectrum_figs {
 } fmx_spectrum_figs;
 int  fmx_spectrum_figures(const fmx_spectrum_find *cfg, const float *mean, const float *peak, fmx_spectrum_figs *out);
 
+/* ---- The multiplex spectrum meter (the reference draws this picture for one channel on its LF scope, setlfPlotType (DEMODULATOR),
+ * fm-processor.cpp:597-660; contract: DESIGN.md 4.16).  Per metered CHANNEL the power spectrum of the demodulator output d [j] at fmRate -- exactly the
+ * value of FMX_TAP_DEMOD, the row stage B leaves behind (fm-processor.cpp:497) -- as a mean and a max-hold per record.
+ * Grid: j counts the handle's fm samples since fmx_create, as the taps and the modulation meter count them (all channels share it).  With S = `every`
+ * (1 .. 4096) and B = `blocks_per_record` (1 .. 4096), both handle-wide, block b is the fm samples [4096 S b, 4096 S b + 4096) and record r the blocks
+ * [r B, r B + B).  Default B = 48, S = 1: 1.024 s at 192 kS/s.
+ * Arithmetic: one block per transform, x [i] = (f32 (d [i] w [i]), 0), the band survey's window w, twiddles and 4096-point transform (fmx_survey.h,
+ * unchanged).  Bins k = 0 .. 2047 are kept, bin k at k fmRate / 4096 Hz (46.875 Hz at 192 kS/s); the Nyquist bin is dropped.  Per bin in f32
+ *     mean_r [k] = c  (p_rB [k] + p_rB+1 [k] + ... in block order, from 0),  c  = f32 (1 / (B sum w^2))
+ *     peak_r [k] = c1 max_b p_b [k],                                          c1 = f32 (1 / sum w^2)
+ * The sum of mean over bins k1 .. k2 (0 < k1) is 4096 / 2 times the power of d in that band: a line of peak amplitude A adds 4096 A^2 / 4.
+ * Carried between calls per metered channel: the 0 .. 4095 samples of a block in progress and the sum and the maximum per bin, nothing else: on the same
+ * d a record is bit for bit the same however the stream is cut into calls and a call into pieces.  (d itself depends on the cut in its last bits, see the
+ * modulation meter above, except with the PLL decoder and RF DC removal off.)
+ * Switch: per channel, from any thread, takes effect at the next call.  A channel's first block is the first that begins at or behind the first fm sample
+ * of the piece that switched it on; record r is delivered only if every one of its blocks was taken while the meter was on; switching off drops the
+ * record in progress.  A scanning channel's meter runs on, as its chain does.  The device keeps the last 4 records per metered channel: a reader that
+ * falls behind sees a gap in `index`.
+ * Rows: a metered channel needs the handle-wide rows exactly as a modulation-metered channel does: a batch with ONE metered channel writes the rows --
+ * 8 bytes per fm sample -- for EVERY channel and is no plain batch (fmx_last_second_group reads as it does with the modulation meter on).  Everything
+ * else a handle delivers -- PCM, RDS, meta, taps, peaks, scan records, the five other meters' records -- is bit for bit, or equal to, what it is without
+ * the meter on the same handle.  A handle that never switches it on allocates and launches nothing for it; memory (96 KB per channel) is allocated for
+ * the channels that are switched on. */
+typedef struct fmx_mpx_record {
+    int64_t index;        /* the record r; a gap means records that were not metered or that the reader lost */
+    int64_t end_sample;   /* one past the last fm sample read: 4096 S ((r + 1) B - 1) + 4096 */
+    int32_t blocks;       /* B */
+    int32_t every;        /* S */
+} fmx_mpx_record;   /* 24 bytes */
+/* blocks per record and `every`, handle-wide; only while no channel's meter is on, else FMX_E_INVALID.  Record indices and every channel's read cursor
+ * start over on the new grid, and records not yet read are lost. */
+int  fmx_mpx_spectrum_setup(fmx_handle h, int32_t blocks_per_record, int32_t every);
+/* switches the multiplex spectrum meter of a channel (-1: of every channel) on or off; from any thread, takes effect at the next call */
+int  fmx_mpx_spectrum_enable(fmx_handle h, int32_t channel, int32_t on);
+/* The records of channels first_channel .. first_channel + n_channels - 1 completed since this function last read each of them, oldest first, at most
+ * capacity_per_channel each (more stay for the next read), in ONE read-out of the device: channel q's record i at recs [q cap + i], its bins at
+ * mean [(q cap + i) 2048 ..] and peak likewise (peak may be NULL), their number in n_records [q].  Waits for the handle's last call only.  The records
+ * are gathered on the device and copied once (per 4096 records of a larger range); a read that fails leaves every cursor where it was. */
+int  fmx_mpx_spectrum_read(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_mpx_record *recs, float *mean, float *peak,
+                           int32_t capacity_per_channel, int32_t *n_records);
+/* The figures of one record (host only, needs no device, every sum in double).  Bin k, 1 .. 2047, lies in a band [lo, hi] when
+ * lo 4096 <= k rate_hz <= hi 4096 (a bound that is not integral is compared after multiplying by 4096 in double); bin 0 and the bins below dc_guard_hz
+ * belong to no band.  With P (band) = 2 / 4096 x the sum of mean over the band -- the power of d in it -- and u = hz_per_unit:
+ *   total_hz          u sqrt P over every usable bin: the rms deviation;
+ *   mono_hz           the same over [dc_guard_hz, 15 000]: L+R;
+ *   stereo_hz         over [23 000, 53 000] without the window 38 000 +- line_half_hz: L-R;
+ *   rds_hz            over [54 600, 59 400]: 57 kHz +- RDS_WIDTH / 2 (fm-constants.h);
+ *   aux_hz            over [61 000, min (94 000, rate_hz / 2)];
+ *   pilot_hz          u sqrt (2 P) over 19 000 +- line_half_hz: the PEAK deviation of a line;
+ *   pilot_freq_hz     the power-weighted mean frequency over that window;
+ *   carrier38_hz      u sqrt (2 P) over 38 000 +- line_half_hz;
+ *   floor_hz_rt_hz    u sqrt (P / width) over the two guards [15 500, 18 500] and [19 500, 22 500], width = the number of their bins times
+ *                     rate_hz / 4096: rms deviation per root hertz;
+ *   pilot_cn0_db      10 log10 of the pilot window's P over the guards' P / width;
+ *   band_hz [i]       u sqrt P over the caller's band i;
+ *   band_line_hz [i]  the frequency of its largest mean bin;
+ *   band_hold_line_hz [i], band_hold_over_mean_db [i]
+ *                     the frequency of its largest peak bin, and 10 log10 of that peak bin over the same bin's mean: 0 for a steady line, large for
+ *                     one that came and went.  Formed only when peak is given.
+ * What cannot be formed reads -HUGE_VAL: a band without a usable bin, a band that reaches above rate_hz / 2 (aux_hz alone is cut there), a zero
+ * denominator, the entries of bands the caller did not give.
+ * FMX_E_INVALID (fmx_last_error names the argument) for: struct_size; rate_hz outside [8000, 1 000 000]; hz_per_unit not positive and finite;
+ * dc_guard_hz outside [0, 1000]; line_half_hz outside [50, 1000]; n_bands outside [0, 16] or bands NULL with n_bands > 0; a band without
+ * 0 <= lo_hz < hi_hz <= rate_hz / 2 or with a bound that is not finite; an entry of mean or peak that is negative or not finite. */
+typedef struct fmx_mpx_band { double lo_hz, hi_hz; } fmx_mpx_band;
+typedef struct fmx_mpx_find {
+    int32_t struct_size;       /* sizeof(fmx_mpx_find) */
+    int32_t rate_hz;           /* the handle's fmRate */
+    double  hz_per_unit;       /* from fmx_mod_hz_per_unit, or 1.0 for the demodulator's own units */
+    int32_t dc_guard_hz;       /* e.g. 30 */
+    int32_t line_half_hz;      /* e.g. 250 */
+    const fmx_mpx_band *bands; /* [n_bands], or NULL */
+    int32_t n_bands, reserved;
+} fmx_mpx_find;
+typedef struct fmx_mpx_figs {
+    double total_hz, mono_hz, stereo_hz, rds_hz, aux_hz, pilot_hz, pilot_freq_hz, carrier38_hz, floor_hz_rt_hz, pilot_cn0_db;
+    double band_hz[16], band_line_hz[16], band_hold_line_hz[16], band_hold_over_mean_db[16];
+} fmx_mpx_figs;
+int  fmx_mpx_figures(const fmx_mpx_find *cfg, const float *mean, const float *peak, fmx_mpx_figs *out);
+
 /* introspection used by the parity tests: the filter taps the kernels run with.
  * which: 0 front-end polyphase taps, 1 PSS low-pass, 2 audio+resampler FIR, 3 resampler alone,
  * 4 the noise squelch's two order-20 filters: [2][10] x (A1, A2, B1, B2), then the two gains (high-pass first),

@@ -698,8 +698,8 @@ int ensure_spectrum(fmx_handle h) {
             std::vector<float> win(spec::N); std::vector<float2> W(spec::N);
             survey::make_window(win.data()); survey::make_twiddles(W.data());
             FMXCHK(h->mem.upload(h->d_spec_win, win)); FMXCHK(h->mem.upload(h->d_spec_W, W));
-            HIPCHK(hipEventCreateWithFlags(&h->ev_spec, hipEventDisableTiming));
         }
+        if (!h->ev_spec) HIPCHK(hipEventCreateWithFlags(&h->ev_spec, hipEventDisableTiming));      // (the tables may be there already: ensure_mpx)
         float2 *carry = nullptr; float *acc = nullptr, *ring = nullptr;
         FMXCHK(h->mem.alloc(carry, (size_t)need * spec::N, true));
         FMXCHK(h->mem.alloc(acc, (size_t)need * 2 * spec::N, true));
@@ -726,6 +726,51 @@ int ensure_spectrum(fmx_handle h) {
     return FMX_OK;
 }
 
+// The multiplex spectrum meter's memory (fmx_mpx.hip), under mtx, grown as ensure_spectrum grows the spectrum meter's: a slot for every channel whose meter
+// is on and has none yet -- 16 KB of carry, 16 KB of sum and maximum, 64 KB of ring --, the arrays allocated anew and the old slots copied.  The window and
+// the twiddles are the spectrum meter's, whichever of the two comes first.  The scratch of block powers holds what a piece of work_nj fm samples completes
+// for every slot, or spec::SCRATCH_BYTES where that is less (stage_mpx cuts the piece then).
+int ensure_mpx(fmx_handle h) {
+    const size_t NC = (size_t)h->channels;
+    if (h->mpx_slot.empty()) {
+        h->mpx_slot.assign(NC, -1); h->mpx_on_from.assign(NC, -1); h->mpx_tag.assign(NC * mpx::RING, -1); h->rd.mpx.assign(NC, 0); h->call_mpx.assign(NC, 0);
+    }
+    int32_t need = h->mpx_slots;
+    for (size_t c = 0; c < NC; c++) if (h->user_mpx[c] && h->mpx_slot[c] < 0) need++;
+    if (need > h->mpx_cap) {
+        HIPCHK(hipDeviceSynchronize());
+        if (!h->d_spec_win) {
+            std::vector<float> win(spec::N); std::vector<float2> W(spec::N);
+            survey::make_window(win.data()); survey::make_twiddles(W.data());
+            FMXCHK(h->mem.upload(h->d_spec_win, win)); FMXCHK(h->mem.upload(h->d_spec_W, W));
+        }
+        if (!h->ev_mpx) HIPCHK(hipEventCreateWithFlags(&h->ev_mpx, hipEventDisableTiming));
+        float *carry = nullptr, *acc = nullptr, *ring = nullptr;
+        FMXCHK(h->mem.alloc(carry, (size_t)need * mpx::N, true));
+        FMXCHK(h->mem.alloc(acc, (size_t)need * 2 * mpx::BINS, true));
+        FMXCHK(h->mem.alloc(ring, (size_t)need * mpx::RING * 2 * mpx::BINS, true));
+        if (h->mpx_slots > 0) {
+            const size_t k = (size_t)h->mpx_slots;
+            HIPCHK(hipMemcpy(carry, h->d_mpx_carry, sizeof(float) * k * mpx::N, hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(acc, h->d_mpx_acc, sizeof(float) * k * 2 * mpx::BINS, hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(ring, h->d_mpx_ring, sizeof(float) * k * mpx::RING * 2 * mpx::BINS, hipMemcpyDeviceToDevice));
+            HIPCHK(hipDeviceSynchronize());
+        }
+        h->mem.release(h->d_mpx_carry); h->mem.release(h->d_mpx_acc); h->mem.release(h->d_mpx_ring); h->mem.release(h->d_mpx_jobs);
+        h->d_mpx_carry = carry; h->d_mpx_acc = acc; h->d_mpx_ring = ring;
+        FMXCHK(h->mem.alloc(h->d_mpx_jobs, (size_t)need));
+        const int64_t want = mpx::scratch_blocks_for(need, (h->work_nj + mpx::N - 1) / mpx::N + 1);
+        if (want > h->mpx_scratch) {
+            h->mem.release(h->d_mpx_power);
+            FMXCHK(h->mem.alloc(h->d_mpx_power, (size_t)want * mpx::BINS));
+            h->mpx_scratch = want;
+        }
+        h->mpx_cap = need;
+    }
+    for (size_t c = 0; c < NC; c++) if (h->user_mpx[c] && h->mpx_slot[c] < 0) h->mpx_slot[c] = h->mpx_slots++;
+    return FMX_OK;
+}
+
 // the tiled work arrays of the demodulator pre-pass (fmx_demod.hip): limited / unlimited samples in, demodulator output out.  (Allocated by the first call
 // that needs them -- before run_call decides how the call is made: a call in pieces needs them too.)
 int ensure_prepass_arrays(fmx_handle h) {
@@ -740,7 +785,7 @@ CallNeeds summarize(fmx_handle h) {
     for (size_t c = 0; c < h->params.size(); c++) {
         const ChanParams &p = h->params[c];
         const FrontSet &fs = h->h_front_sets[(size_t)p.front_set];
-        needs_add(nd, ChanNeeds{p.decoder, p.squelch_mode, p.rds_mode, p.lo_freq, p.att_l, p.att_r, fs.nd, fs.dc_k, h->user[c].meter ? 1 : 0});
+        needs_add(nd, ChanNeeds{p.decoder, p.squelch_mode, p.rds_mode, p.lo_freq, p.att_l, p.att_r, fs.nd, fs.dc_k, (h->user[c].meter || (!h->user_mpx.empty() && h->user_mpx[c])) ? 1 : 0});
     }
     return nd;
 }
@@ -771,7 +816,9 @@ int flush_mailbox(fmx_handle h) {
     for (int c = 0; c < h->channels; c++)
         if (h->user[(size_t)c].scanning) { h->call_scan.push_back(c); h->call_scan_thr.push_back(h->user[(size_t)c].scan_thr); }
     if (!h->call_scan.empty()) { const int rc = ensure_scan(h); if (rc) return rc; }
-    if (nd.any_meter) { const int rc = ensure_meter(h); if (rc) return rc; }
+    // (any_meter says that the rows are needed: the modulation meter or the multiplex spectrum meter is on.  The modulation meter's own memory is for a handle
+    // that switches it on)
+    if (nd.any_meter && !h->meter_alloc && std::any_of(h->user.begin(), h->user.end(), [](const ChanUser &u) { return u.meter; })) { const int rc = ensure_meter(h); if (rc) return rc; }
     if (h->meter_alloc) for (int c = 0; c < h->channels; c++) h->call_meter[(size_t)c] = h->user[(size_t)c].meter ? 1 : 0;
     // (the audio meter reads the call's PCM behind everything that writes it and asks nothing of the call's plan: it is no part of CallNeeds)
     if (!h->loud_alloc && std::any_of(h->user.begin(), h->user.end(), [](const ChanUser &u) { return u.loud; })) { const int rc = ensure_audio_meter(h); if (rc) return rc; }
@@ -795,6 +842,18 @@ int flush_mailbox(fmx_handle h) {
     if (!h->user_spec.empty()) {
         if (std::any_of(h->user_spec.begin(), h->user_spec.end(), [](uint8_t on) { return on != 0; })) { const int rc = ensure_spectrum(h); if (rc) return rc; }
         if (!h->call_spec.empty()) h->call_spec = h->user_spec;
+    }
+    // (the multiplex spectrum meter reads the rows a metered channel asks for above -- ChanNeeds::metered -- and its own memory.  fmx_mpx_spectrum_setup's
+    // grid is taken over here, while no channel's meter is on: indices, cursors and what the ring held start over)
+    if (h->mpx_setup_dirty) {
+        h->mpx_B = h->mpx_B_user; h->mpx_S = h->mpx_S_user; h->mpx_setup_dirty = false;
+        std::fill(h->mpx_on_from.begin(), h->mpx_on_from.end(), -1); std::fill(h->mpx_tag.begin(), h->mpx_tag.end(), -1);
+        std::fill(h->rd.mpx.begin(), h->rd.mpx.end(), 0);
+    }
+    if (!h->user_mpx.empty()) {
+        // (mpx_live: stage_mpx has something to do -- a meter is on, or was and its channel's first sample has not been cleared yet)
+        if (std::any_of(h->user_mpx.begin(), h->user_mpx.end(), [](uint8_t on) { return on != 0; })) { const int rc = ensure_mpx(h); if (rc) return rc; h->mpx_live = true; }
+        if (!h->call_mpx.empty()) h->call_mpx = h->user_mpx;
     }
     if (nd.keep_taps && !h->w_diff_mem) {
         HIPCHK(hipDeviceSynchronize());
@@ -1103,6 +1162,51 @@ int stage_meter(fmx_handle h, const CallGeom &G, hipStream_t s) {
     return FMX_OK;
 }
 
+// The multiplex spectrum meter: the metered channels' rows of the piece through fmx_mpx.hip, on the stream stage B ran on and behind it, where stage_rds and
+// the modulation meter read the same rows.  What the piece's fm samples [J0, J1) mean on the grid is spec::piece's integers; the metered channels go in
+// groups, a group's blocks in chunks (spec::launches), so that the scratch holds every launch's block powers; the sums stay in block order, so nothing
+// depends on the cutting.  The piece's last launch of a group writes the carry: the row holds this piece's fm samples only.  The ring tags -- which record
+// a slot holds -- change under mtx with the event fmx_mpx_spectrum_read waits for.
+int stage_mpx(fmx_handle h, const CallGeom &G, hipStream_t s) {
+    const int64_t nj = G.J1 - G.J0;
+    if (nj > h->work_nj) return fail(FMX_E_TOO_LARGE, "the piece has more fm samples than stage B's rows hold");
+    std::lock_guard<std::mutex> lk(h->mtx);
+    const int32_t S = h->mpx_S, B = h->mpx_B;
+    const spec::Piece p = spec::piece(G.J0, nj, S, B);
+    h->mpx_jobs.clear();
+    for (int c = 0; c < h->channels; c++) {
+        if (!h->call_mpx[(size_t)c]) { h->mpx_on_from[(size_t)c] = -1; continue; }      // (off: the record in progress is dropped)
+        if (h->mpx_on_from[(size_t)c] < 0) h->mpx_on_from[(size_t)c] = G.J0;
+        h->mpx_jobs.push_back(MpxJob{c, h->mpx_slot[(size_t)c], spec::first_block(h->mpx_on_from[(size_t)c], S)});
+    }
+    const int64_t n_jobs = (int64_t)h->mpx_jobs.size();
+    if (n_jobs == 0) { h->mpx_live = false; return FMX_OK; }      // (every meter is off and every first sample cleared: nothing to do until one is switched on)
+    if (h->mpx_c_B != B) {                    // (c follows B: fmx_mpx_spectrum_setup)
+        std::vector<float> win(mpx::N);
+        survey::make_window(win.data());
+        h->mpx_c = survey::record_scale(win.data(), B); h->mpx_c1 = survey::record_scale(win.data(), 1); h->mpx_c_B = B;
+    }
+    // (pageable source: the copy is staged before the call returns)
+    HIPCHK(hipMemcpyAsync(h->d_mpx_jobs, h->mpx_jobs.data(), sizeof(MpxJob) * (size_t)n_jobs, hipMemcpyHostToDevice, s));
+    MpxArgs A{};
+    A.jobs = h->d_mpx_jobs; A.w_dem = h->B.w_dem; A.lin_rows = h->B.lin_rows; A.g0 = G.J0; A.n = nj; A.S = S; A.B = B;
+    A.fill = p.fill; A.fill_after = p.fill_after; A.append = p.append; A.carry_src = p.carry_src; A.c = h->mpx_c; A.c1 = h->mpx_c1;
+    A.window = h->d_spec_win; A.W = h->d_spec_W; A.carry = h->d_mpx_carry; A.acc = h->d_mpx_acc; A.ring = h->d_mpx_ring; A.power = h->d_mpx_power;
+    spec::launches(n_jobs, h->mpx_scratch, p.blocks, p.fill_after > 0, [&](int64_t j0, int64_t gn, int64_t done, int64_t nb, bool write_carry) {
+        A.job0 = (int32_t)j0; A.n_jobs = (int32_t)gn;
+        A.b = p.b0 + done; A.nb = (int32_t)nb; A.phase = (int32_t)(A.b % B);
+        A.write_carry = write_carry ? 1 : 0;
+        launch_mpx(A, s);
+    });
+    FMX_LAUNCHED();
+    HIPCHK(hipEventRecord(h->ev_mpx, s)); h->ev_mpx_set = true;
+    const int64_t r_end = p.record0 + p.records;
+    for (const MpxJob &job : h->mpx_jobs)
+        for (int64_t r = std::max(p.record0, r_end - mpx::RING); r < r_end; r++)
+            if (spec::delivered(r, B, job.first)) h->mpx_tag[(size_t)job.channel * mpx::RING + (size_t)(r & (mpx::RING - 1))] = r;
+    return FMX_OK;
+}
+
 // the reception meter: the metered channels' fm samples of the piece, out of stage A's ring, into their lane accumulators, every window that ends in it into
 // the record ring (fmx_rx.hip) -- on the stream stage A ran on, behind this piece's stage A and ahead of the next one's, as stage_scan.  The sample in front
 // of the piece's first comes from the ring: rx::ring_holds says that stage A has not yet written over it (with fmx_create's sizing of the ring it always
@@ -1296,6 +1400,7 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     if ((rc = stage_b(h, G, k, piped, second, s, sa))) return rc;
     if (rds_running && (rc = stage_rds(h, G, s))) return rc;
     if (h->meter_alloc && G.J1 > G.J0 && (rc = stage_meter(h, G, s))) return rc;
+    if (h->mpx_live && G.J1 > G.J0 && (rc = stage_mpx(h, G, s))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[2], s));
     if ((rc = stage_c(h, G, d_pcm, frames, second, s))) return rc;
     if (!h->call_scan.empty() && frames > 0 && (rc = stage_scan_mute(h, d_pcm, G.pcm_stride, frames, s))) return rc;
@@ -1646,7 +1751,7 @@ int fmx_destroy(fmx_handle h) {
     for (auto &pr : h->prof) for (int i = 0; i < 4; i++) (void)hipEventDestroy(pr.e[i]);
     for (hipEvent_t e : h->step_ev) if (e) (void)hipEventDestroy(e);
     if (h->rd_stream) { (void)hipStreamSynchronize(h->rd_stream); (void)hipStreamDestroy(h->rd_stream); }
-    for (hipEvent_t e : {h->ev_call, h->ev_spec, h->ev_in, h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {h->ev_call, h->ev_spec, h->ev_mpx, h->ev_in, h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
     for (hipStream_t st : {h->stream, h->pipe_sA, h->pipe_sP, h->pipe_sB}) if (st) (void)hipStreamDestroy(st);
     h->mem.release_all(); h->rds_mem.release_all();
     delete h;
@@ -1782,6 +1887,27 @@ int fmx_spectrum_enable(fmx_handle h, int32_t stream, int32_t on) {
     if (h->user_spec.empty()) h->user_spec.assign((size_t)h->streams, 0);
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? h->streams : stream + 1;
     for (int s = s0; s < s1; s++) h->user_spec[(size_t)s] = on != 0;
+    return FMX_OK;
+}
+
+int fmx_mpx_spectrum_setup(fmx_handle h, int32_t blocks_per_record, int32_t every) {
+    if (!h) return fail(FMX_E_INVALID, "null handle");
+    if (blocks_per_record < 1 || blocks_per_record > mpx::MAX_B) return fail(FMX_E_INVALID, "blocks_per_record must be in [1, 4096]");
+    if (every < 1 || every > mpx::MAX_S) return fail(FMX_E_INVALID, "every must be in [1, 4096]");
+    std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes the grid over at the next call)
+    if (std::any_of(h->user_mpx.begin(), h->user_mpx.end(), [](uint8_t on) { return on != 0; }))
+        return fail(FMX_E_INVALID, "fmx_mpx_spectrum_setup: a channel's multiplex spectrum meter is on");
+    h->mpx_B_user = blocks_per_record; h->mpx_S_user = every; h->mpx_setup_dirty = true;
+    return FMX_OK;
+}
+
+int fmx_mpx_spectrum_enable(fmx_handle h, int32_t channel, int32_t on) {
+    if (!h) return fail(FMX_E_INVALID, "null handle");
+    if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
+    std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
+    if (h->user_mpx.empty()) h->user_mpx.assign((size_t)h->channels, 0);
+    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
+    for (int c = c0; c < c1; c++) h->user_mpx[(size_t)c] = on != 0;
     return FMX_OK;
 }
 

@@ -13,6 +13,7 @@
 #include "fmx_rdsm.h"
 #include "fmx_rdsgroups.h"
 #include "fmx_spec.h"
+#include "fmx_mpx.h"
 
 #include <algorithm>
 #include <atomic>
@@ -121,6 +122,7 @@ struct Readers {
     std::vector<int64_t> rx;                 // fmx_rx_records: records of fmx_handle_s::rx_produced
     std::vector<int64_t> rdsm;               // fmx_rds_meter_records: records of fmx_handle_s::rdsm_produced
     std::vector<int64_t> spec;               // fmx_spectrum_read, per STREAM: the next record index it hands out (sized by the meter's first use)
+    std::vector<int64_t> mpx;                // fmx_mpx_spectrum_read, per channel: the next record index it hands out (sized by the meter's first use)
     std::vector<uint8_t> reset_dec, reset_dec_all;   // resetRds / triggerFrequencyChange asked for the group decoder's reset: fmx_rds_decode's, fmx_rds_decode_all's (under mtx)
     std::vector<RdsGroupDecoderHost> dec, dec_all;   // fmx_rds_decode's decoders (the synchroniser on the host), fmx_rds_decode_all's (on the GPU: rds_sync)
     void init(size_t channels) {
@@ -246,6 +248,21 @@ struct fmx_handle_s {
     float2 *d_spec_carry = nullptr, *d_spec_W = nullptr; float *d_spec_acc = nullptr, *d_spec_ring = nullptr, *d_spec_power = nullptr, *d_spec_win = nullptr;
     SpecJob *d_spec_jobs = nullptr; std::vector<SpecJob> spec_jobs;
     hipEvent_t ev_spec = nullptr; bool ev_spec_set = false;             // behind the last piece's spectrum kernels: what fmx_spectrum_read waits for
+    // the multiplex spectrum meter (fmx_mpx.hip, fmx_mpx.h), per CHANNEL, kept as the spectrum meter keeps its streams: the user's switch (under mtx), the
+    // channels whose meter is on in the piece being made (flush_mailbox), the fm sample of the piece that switched it on (-1: off), its slot in the meter's
+    // device memory (-1: none yet; a channel keeps its slot) and per ring slot the record it holds (-1: none).  Per slot the device keeps the carry (16 KB),
+    // sum and maximum (16 KB) and the ring (64 KB); the window and the twiddles are d_spec_win / d_spec_W, shared with the spectrum meter
+    std::vector<uint8_t> user_mpx, call_mpx;
+    std::vector<int64_t> mpx_on_from; std::vector<int32_t> mpx_slot; std::vector<int64_t> mpx_tag;
+    int32_t mpx_B = mpx::DEFAULT_B, mpx_S = 1, mpx_B_user = mpx::DEFAULT_B, mpx_S_user = 1; bool mpx_setup_dirty = false;
+    int32_t mpx_slots = 0, mpx_cap = 0; int64_t mpx_scratch = 0;        // slots in use, slots allocated, blocks of scratch allocated
+    float mpx_c = 0.f, mpx_c1 = 0.f; int32_t mpx_c_B = 0;              // 1 / (B sum w^2) for B = mpx_c_B, 1 / sum w^2
+    float *d_mpx_carry = nullptr, *d_mpx_acc = nullptr, *d_mpx_ring = nullptr, *d_mpx_power = nullptr;
+    MpxJob *d_mpx_jobs = nullptr; std::vector<MpxJob> mpx_jobs;
+    bool mpx_live = false;                                              // some channel's meter is on, or was in the last piece that looked (stage_mpx runs)
+    // the read-out's staging (fmx_mpx_spectrum_read, under mtx): which ring records to gather, where they are gathered, and the pinned copy of that
+    int32_t *d_mpx_src = nullptr; float *d_mpx_stage = nullptr, *h_mpx_stage = nullptr; int64_t mpx_stage_recs = 0; std::vector<int32_t> mpx_src;
+    hipEvent_t ev_mpx = nullptr; bool ev_mpx_set = false;               // behind the last piece's kernels: what fmx_mpx_spectrum_read waits for
     std::atomic<int> stageb_form{0};     // FMX_P_STAGEB_FORM
     std::atomic<int> front_parts{0};     // FMX_P_FRONT_PARTS
     std::atomic<int> front_kernel{0};    // FMX_P_FRONT_KERNEL

@@ -560,6 +560,32 @@ struct SpecArgs {
 };
 void launch_spec(const SpecArgs &A, hipStream_t s);
 
+// ---- the multiplex spectrum meter (fmx_mpx.hip, fmx_mpx.h) -----------------------------------------------------------
+// one metered channel of a piece: the handle's channel, its slot in the meter's memory, and the first block it takes (spec::first_block)
+struct MpxJob { int32_t channel, slot; int64_t first; };
+// One launch pair: the jobs [job0, job0 + n_jobs) and the blocks [b, b + nb) of the piece's fm samples [g0, g0 + n) -- a chunk of a group
+// (spec::launches) -- through the transform into `power`, then folded in block order into `acc` and, at record ends, into the ring.  The piece's last
+// fold (write_carry) also writes the samples carried behind the piece.
+struct MpxArgs {
+    const MpxJob *jobs;                        // [all jobs of the piece] (copied per piece on the stream of the launch)
+    const float *w_dem; int32_t lin_rows;      // stage B's demodulator rows: channel c's fm sample g0 + q at w_dem [c * lin_rows + q]
+    int64_t g0, n;
+    int32_t S, B;
+    int32_t fill, fill_after, append, write_carry;   // spec::Piece
+    int64_t carry_src;
+    int64_t b; int32_t nb, phase;              // the chunk: its first block, its blocks, b mod B
+    int32_t job0, n_jobs;
+    float c, c1;                               // 1 / (B sum w^2), 1 / sum w^2
+    const float *window; const float2 *W;      // [4096] each: the survey's
+    float *carry;                              // [slots][4096] samples of the block in progress
+    float *acc;                                // [slots][2][2048] sum, maximum
+    float *ring;                               // [slots][mpx::RING][2][2048] mean, peak
+    float *power;                              // [n_jobs][nb][2048] the chunk's block powers (at most spec::SCRATCH_BYTES)
+};
+void launch_mpx(const MpxArgs &A, hipStream_t s);
+// the read-out: ring record src [q] (slot * mpx::RING + r mod mpx::RING; 2 x 2048 floats) to out [q], q < n
+void launch_mpx_gather(const float *ring, const int32_t *src, float *out, int n, hipStream_t s);
+
 void launch_front(const DeviceTables &T, const DeviceBuffers &B, const CallGeom &G, const void *iq,
                   int channels, hipStream_t s);
 // fmx_front4.hip: whole tiles of the call front4_kernel can take (0: none), and its launch over that many

@@ -509,6 +509,81 @@ int fmx_spectrum_figures(const fmx_spectrum_find *cfg, const float *mean, const 
     return rc == FMX_OK ? FMX_OK : fail(rc, why);
 }
 
+// The multiplex spectrum meter's records of a range of channels.  Which record a ring slot holds is the host's (fmx_handle_s::mpx_tag).  The records of the
+// whole range are gathered on the device into one staging array (mpx_gather_kernel) behind the handle's last call, and leave it in ONE copy to pinned
+// memory (a range of more than MPX_READ_BATCH records: one copy per 4096 records, 64 MB of staging at the most).  The cursors move only when every copy
+// has arrived: a read that fails loses nothing.
+constexpr int64_t MPX_READ_BATCH = 4096;
+int fmx_mpx_spectrum_read(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_mpx_record *recs, float *mean, float *peak,
+                          int32_t capacity_per_channel, int32_t *n_records) {
+    if (!h || !n_records) return fail(FMX_E_INVALID, "null argument");
+    if (first_channel < 0 || n_channels < 1 || n_channels > h->channels || first_channel > h->channels - n_channels) return fail(FMX_E_INVALID, "channel range out of range");
+    for (int q = 0; q < n_channels; q++) n_records[q] = 0;
+    const int32_t cap = capacity_per_channel;
+    if (cap < 0 || (cap > 0 && (!recs || !mean))) return fail(FMX_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (h->mpx_tag.empty() || cap == 0) return FMX_OK;
+    // what the range has to hand out: per record its place in the ring and in the caller's arrays
+    h->mpx_src.clear();
+    std::vector<size_t> dst;
+    std::vector<int64_t> next((size_t)n_channels, -1);
+    std::vector<int32_t> count((size_t)n_channels, 0);
+    for (int q = 0; q < n_channels; q++) {
+        const size_t ch = (size_t)(first_channel + q);
+        int64_t have[mpx::RING]; int n = 0;
+        for (int k = 0; k < mpx::RING; k++) {
+            const int64_t r = h->mpx_tag[ch * mpx::RING + (size_t)k];
+            if (r >= h->rd.mpx[ch]) have[n++] = r;      // (older ones were read, or overwritten: the gap shows in `index`)
+        }
+        std::sort(have, have + n);
+        n = std::min<int>(n, cap);
+        for (int i = 0; i < n; i++) {
+            const int64_t r = have[i];
+            const size_t at = (size_t)q * (size_t)cap + (size_t)i;
+            recs[at] = fmx_mpx_record{r, spec::record_end(r, h->mpx_B, h->mpx_S), h->mpx_B, h->mpx_S};
+            h->mpx_src.push_back(h->mpx_slot[ch] * mpx::RING + (int32_t)(r & (mpx::RING - 1)));
+            dst.push_back(at);
+        }
+        if (n > 0) { next[(size_t)q] = have[n - 1] + 1; count[(size_t)q] = n; }
+    }
+    const int64_t total = (int64_t)dst.size();
+    if (total == 0) return FMX_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (!h->rd_stream) HIPCHK(hipStreamCreateWithFlags(&h->rd_stream, hipStreamNonBlocking));
+    if (h->ev_mpx_set) HIPCHK(hipStreamWaitEvent(h->rd_stream, h->ev_mpx, 0));
+    const int64_t batch = std::min(total, MPX_READ_BATCH);
+    if (batch > h->mpx_stage_recs) {
+        h->mem.release(h->d_mpx_src); h->mem.release(h->d_mpx_stage); h->mem.release(h->h_mpx_stage); h->mpx_stage_recs = 0;
+        FMXCHK(h->mem.alloc(h->d_mpx_src, (size_t)batch));
+        FMXCHK(h->mem.alloc(h->d_mpx_stage, (size_t)batch * 2 * mpx::BINS));
+        FMXCHK(h->mem.alloc_pinned(h->h_mpx_stage, (size_t)batch * 2 * mpx::BINS));
+        h->mpx_stage_recs = batch;
+    }
+    g_launch_err = hipSuccess;
+    for (int64_t o = 0; o < total; o += batch) {
+        const int64_t m = std::min(batch, total - o);
+        HIPCHK(hipMemcpyAsync(h->d_mpx_src, h->mpx_src.data() + o, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, h->rd_stream));
+        launch_mpx_gather(h->d_mpx_ring, h->d_mpx_src, h->d_mpx_stage, (int)m, h->rd_stream);
+        HIPCHK(g_launch_err);
+        HIPCHK(hipMemcpyAsync(h->h_mpx_stage, h->d_mpx_stage, sizeof(float) * (size_t)m * 2 * mpx::BINS, hipMemcpyDeviceToHost, h->rd_stream));
+        HIPCHK(hipStreamSynchronize(h->rd_stream));
+        for (int64_t i = 0; i < m; i++) {
+            const float *from = h->h_mpx_stage + (size_t)i * 2 * mpx::BINS;
+            std::memcpy(mean + dst[(size_t)(o + i)] * mpx::BINS, from, sizeof(float) * mpx::BINS);
+            if (peak) std::memcpy(peak + dst[(size_t)(o + i)] * mpx::BINS, from + mpx::BINS, sizeof(float) * mpx::BINS);
+        }
+    }
+    for (int q = 0; q < n_channels; q++)
+        if (count[(size_t)q] > 0) { h->rd.mpx[(size_t)(first_channel + q)] = next[(size_t)q]; n_records[q] = count[(size_t)q]; }
+    return FMX_OK;
+}
+
+int fmx_mpx_figures(const fmx_mpx_find *cfg, const float *mean, const float *peak, fmx_mpx_figs *out) {
+    const char *why = "";
+    const int rc = mpx::figures(cfg, mean, peak, out, &why);
+    return rc == FMX_OK ? FMX_OK : fail(rc, why);
+}
+
 int64_t fmx_pll_replays(fmx_handle h, int32_t channel) { return sum_chan_states(h, channel, [](const ChanState &s) { return s.pll_replays; }); }
 int64_t fmx_pll_exact_segments(fmx_handle h, int32_t channel) { return sum_chan_states(h, channel, [](const ChanState &s) { return s.pll_exact_segs; }); }
 int32_t fmx_last_front_kernel(fmx_handle h) { return h ? h->last_front_kernel : 0; }

@@ -39,7 +39,7 @@ EXPORTS = [
     "fmx_abi_version", "fmx_last_error", "fmx_create", "fmx_destroy", "fmx_set_param", "fmx_frames_for", "fmx_filter_change_due",
     "fmx_process_host", "fmx_process_device", "fmx_process_host_raw", "fmx_process_device_raw", "fmx_synchronize",
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
-    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rx_meter_enable", "fmx_rx_records", "fmx_rx_quality_of", "fmx_rds_meter_enable", "fmx_rds_meter_records", "fmx_rds_meter_cal", "fmx_rds_meter_figures", "fmx_spectrum_setup", "fmx_spectrum_enable", "fmx_spectrum_read", "fmx_spectrum_figures", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
+    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rx_meter_enable", "fmx_rx_records", "fmx_rx_quality_of", "fmx_rds_meter_enable", "fmx_rds_meter_records", "fmx_rds_meter_cal", "fmx_rds_meter_figures", "fmx_spectrum_setup", "fmx_spectrum_enable", "fmx_spectrum_read", "fmx_spectrum_figures", "fmx_mpx_spectrum_setup", "fmx_mpx_spectrum_enable", "fmx_mpx_spectrum_read", "fmx_mpx_figures", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
     "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
     "fmx_wideband_survey_enable", "fmx_wideband_survey_read", "fmx_wideband_survey_stations",
     "fmx_wideband_create_rate", "fmx_wideband_outputs_for", "fmx_wideband_rate_taps", "fmx_wideband_survey_stations_rate",
@@ -112,6 +112,33 @@ SPECTRUM_RECORD_DTYPE = np.dtype([("index", np.int64), ("end_sample", np.int64),
 assert SPECTRUM_RECORD_DTYPE.itemsize == C.sizeof(FmxSpectrumRecord) == 24
 SPECTRUM_BINS = 4096
 SPECTRUM_RING = 4             # records the library keeps per metered stream
+
+
+class FmxMpxRecord(C.Structure):
+    _fields_ = [("index", C.c_int64), ("end_sample", C.c_int64), ("blocks", C.c_int32), ("every", C.c_int32)]
+
+
+class FmxMpxBand(C.Structure):
+    _fields_ = [("lo_hz", C.c_double), ("hi_hz", C.c_double)]
+
+
+class FmxMpxFind(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("rate_hz", C.c_int32), ("hz_per_unit", C.c_double), ("dc_guard_hz", C.c_int32), ("line_half_hz", C.c_int32),
+                ("bands", C.POINTER(FmxMpxBand)), ("n_bands", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FmxMpxFigs(C.Structure):
+    _fields_ = [("total_hz", C.c_double), ("mono_hz", C.c_double), ("stereo_hz", C.c_double), ("rds_hz", C.c_double), ("aux_hz", C.c_double),
+                ("pilot_hz", C.c_double), ("pilot_freq_hz", C.c_double), ("carrier38_hz", C.c_double), ("floor_hz_rt_hz", C.c_double),
+                ("pilot_cn0_db", C.c_double), ("band_hz", C.c_double * 16), ("band_line_hz", C.c_double * 16), ("band_hold_line_hz", C.c_double * 16),
+                ("band_hold_over_mean_db", C.c_double * 16)]
+
+
+# fmx_mpx_record as a numpy record (Fmx.mpx_spectrum_read)
+MPX_RECORD_DTYPE = np.dtype([("index", np.int64), ("end_sample", np.int64), ("blocks", np.int32), ("every", np.int32)])
+assert MPX_RECORD_DTYPE.itemsize == C.sizeof(FmxMpxRecord) == 24
+MPX_BINS = 2048               # bin k at k * fmRate / 4096 Hz
+MPX_RING = 4                  # records the library keeps per metered channel
 
 
 class FmxMeta(C.Structure):
@@ -324,6 +351,14 @@ def load_library(path=None):
     L.fmx_spectrum_read.argtypes = [vp, i32, vp, vp, vp, i32, C.POINTER(i32)]
     L.fmx_spectrum_figures.restype = C.c_int
     L.fmx_spectrum_figures.argtypes = [C.POINTER(FmxSpectrumFind), vp, vp, C.POINTER(FmxSpectrumFigs)]
+    L.fmx_mpx_spectrum_setup.restype = C.c_int
+    L.fmx_mpx_spectrum_setup.argtypes = [vp, i32, i32]
+    L.fmx_mpx_spectrum_enable.restype = C.c_int
+    L.fmx_mpx_spectrum_enable.argtypes = [vp, i32, i32]
+    L.fmx_mpx_spectrum_read.restype = C.c_int
+    L.fmx_mpx_spectrum_read.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
+    L.fmx_mpx_figures.restype = C.c_int
+    L.fmx_mpx_figures.argtypes = [C.POINTER(FmxMpxFind), vp, vp, C.POINTER(FmxMpxFigs)]
     L.fmx_mod_hz_per_unit.restype = C.c_int
     L.fmx_mod_hz_per_unit.argtypes = [i32, i32, C.POINTER(C.c_double)]
     L.fmx_rds_bits.restype = C.c_int
@@ -457,6 +492,30 @@ def spectrum_figures(mean, peak=None, rate_hz=2304000, centre_hz=0, raster_hz=10
         raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
     figs = {name: getattr(out, name) for name, _ in FmxSpectrumFigs._fields_}
     figs["adj_db"] = list(out.adj_db)
+    return figs
+
+
+def mpx_figures(mean, peak=None, rate_hz=192000, hz_per_unit=1.0, dc_guard_hz=30, line_half_hz=250, bands=None):
+    """The figures of one multiplex-spectrum record (include/fmx.h fmx_mpx_figures; host only, needs no device): a dict of total_hz, mono_hz, stereo_hz,
+    rds_hz, aux_hz, pilot_hz, pilot_freq_hz, carrier38_hz, floor_hz_rt_hz, pilot_cn0_db and, one entry per caller band [(lo_hz, hi_hz), ...], the lists
+    band_hz, band_line_hz, band_hold_line_hz and band_hold_over_mean_db; -inf for a quantity that cannot be formed.  hz_per_unit: Fmx.mod_hz_per_unit's,
+    or 1.0 for the demodulator's own units.  Raises FmxError (FMX_E_INVALID) for an argument the library refuses."""
+    L = load_library()
+    mean = np.ascontiguousarray(mean, np.float32)
+    assert mean.shape == (MPX_BINS,)
+    if peak is not None:
+        peak = np.ascontiguousarray(peak, np.float32)
+        assert peak.shape == (MPX_BINS,)
+    nb = len(bands) if bands is not None else 0
+    arr = (FmxMpxBand * max(nb, 1))(*[FmxMpxBand(float(lo), float(hi)) for lo, hi in (bands or [])]) if bands is not None else None
+    cfg = FmxMpxFind(C.sizeof(FmxMpxFind), int(rate_hz), float(hz_per_unit), int(dc_guard_hz), int(line_half_hz), arr, nb, 0)
+    out = FmxMpxFigs()
+    rc = L.fmx_mpx_figures(C.byref(cfg), mean.ctypes.data, peak.ctypes.data if peak is not None else None, C.byref(out))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
+    figs = {name: getattr(out, name) for name, _ in FmxMpxFigs._fields_[:10]}
+    for name, _ in FmxMpxFigs._fields_[10:]:
+        figs[name] = list(getattr(out, name))[:min(nb, 16)]
     return figs
 
 
@@ -661,6 +720,30 @@ class Fmx:
         n = C.c_int32()
         self._check(self.L.fmx_spectrum_read(self.h, int(stream), recs.ctypes.data, mean.ctypes.data, pk.ctypes.data if peak else None, int(capacity), C.byref(n)))
         return recs[:n.value].copy(), mean[:n.value].copy(), (pk[:n.value].copy() if peak else None)
+
+    def mpx_spectrum_setup(self, blocks_per_record=48, every=1):
+        """The multiplex spectrum meter's grid, handle-wide (fmx_mpx_spectrum_setup): blocks of 4096 fm samples per record and `every` (block b begins at
+        fm sample 4096 * every * b).  Only while no channel's meter is on."""
+        self._check(self.L.fmx_mpx_spectrum_setup(self.h, int(blocks_per_record), int(every)))
+
+    def mpx_spectrum_meter(self, on=True, channel=-1):
+        """Switch the multiplex spectrum meter of a channel (-1: of every channel) on or off, from the next call on (fmx_mpx_spectrum_enable)."""
+        self._check(self.L.fmx_mpx_spectrum_enable(self.h, int(channel), 1 if on else 0))
+
+    mpx_spectrum_enable = mpx_spectrum_meter
+
+    def mpx_spectrum_read(self, first=0, count=1, capacity=MPX_RING, peak=True):
+        """The records of channels first .. first + count - 1 completed since each one's last read, oldest first, in one read-out of the device
+        (fmx_mpx_spectrum_read) -> a list with one (records as MPX_RECORD_DTYPE, mean [n, 2048] f32, peak [n, 2048] f32 or None) per channel;
+        mpx_figures () turns one record into deviation, pilot, carrier and floor figures.  The library keeps the last 4 per metered channel."""
+        cap = max(int(capacity), 1)
+        recs = np.zeros((count, cap), MPX_RECORD_DTYPE)
+        mean = np.zeros((count, cap, MPX_BINS), np.float32)
+        pk = np.zeros((count, cap, MPX_BINS), np.float32) if peak else None
+        n = np.zeros(count, np.int32)
+        self._check(self.L.fmx_mpx_spectrum_read(self.h, int(first), int(count), recs.ctypes.data, mean.ctypes.data, pk.ctypes.data if peak else None,
+                                                 int(capacity), n.ctypes.data))
+        return [(recs[q, :n[q]].copy(), mean[q, :n[q]].copy(), (pk[q, :n[q]].copy() if peak else None)) for q in range(count)]
 
     def rds_meter_cal(self, channel=0):
         """The calibration of a channel's RDS meter from the handle's own taps (fmx_rds_meter_cal): a dict of gain, phase0_deg and path_57k."""
@@ -1003,6 +1086,12 @@ class FmProcessor:
     def pollSpectrum(self, stream=0):
         """The spectrum meter's records of a stream since the last poll: (records as SPECTRUM_RECORD_DTYPE, mean [n, 4096], peak [n, 4096])."""
         return self.fmx.spectrum_read(stream)
+
+    def setMpxSpectrumMeter(self, on): self.fmx.mpx_spectrum_meter(on, self.channel)
+
+    def pollMpxSpectrum(self):
+        """The multiplex spectrum meter's records of this channel since the last poll: (records as MPX_RECORD_DTYPE, mean [n, 2048], peak [n, 2048])."""
+        return self.fmx.mpx_spectrum_read(self.channel, 1)[0]
 
     def isPilotLocked(self):
         m = self.fmx.meta(self.channel)

@@ -238,6 +238,22 @@ public:
     static bool spectrumFigures(const fmx_spectrum_find *cfg, const float *mean, const float *peak, fmx_spectrum_figs *f) {
         return fmx_spectrum_figures(cfg, mean, peak, f) == FMX_OK;
     }
+    // the multiplex spectrum meter (include/fmx.h fmx_mpx_*; the reference's LF scope with setlfPlotType (DEMODULATOR), fm-processor.cpp:597-660):
+    // setMpxSpectrumGrid sets blocks per record and `every` while the meter is off, setMpxSpectrumMeter switches it with the next block, pollMpxSpectrum
+    // calls `emit_fn(const fmx_mpx_record &, const float *mean, const float *peak)` (2048 bins each, bin k at k fmRate / 4096 Hz) once per record of this
+    // processor's channel completed since the last poll, oldest first; mpxFigures makes deviation, pilot, carrier and floor figures of one record
+    bool setMpxSpectrumGrid(int32_t blocks_per_record, int32_t every) { return h && check(fmx_mpx_spectrum_setup(h, blocks_per_record, every)); }
+    void setMpxSpectrumMeter(bool on) { if (h) check(fmx_mpx_spectrum_enable(h, 0, on ? 1 : 0)); }
+    template <class F> int pollMpxSpectrum(F emit_fn) {
+        fmx_mpx_record r[4]; int32_t n = 0;
+        std::vector<float> mean(4 * 2048), peak(4 * 2048);
+        if (!h || fmx_mpx_spectrum_read(h, 0, 1, r, mean.data(), peak.data(), 4, &n) != FMX_OK) return 0;
+        for (int32_t k = 0; k < n; k++) emit_fn(r[k], mean.data() + (size_t)k * 2048, peak.data() + (size_t)k * 2048);
+        return n;
+    }
+    static bool mpxFigures(const fmx_mpx_find *cfg, const float *mean, const float *peak, fmx_mpx_figs *f) {
+        return fmx_mpx_figures(cfg, mean, peak, f) == FMX_OK;
+    }
     // the RDS picture of this processor's channel(s) in one read-out of the device (fmx_rds_decode_all: the block synchroniser has run on the GPU,
     // the group decoder runs here): what the rds classes' signals carried, infos[k] for channel first + k
     bool poll_rds(fmx_rds_info *infos, int32_t first = 0, int32_t count = 1) { return h && check(fmx_rds_decode_all(h, first, count, infos)); }
