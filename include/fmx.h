@@ -765,6 +765,72 @@ typedef struct fmx_mpx_figs {
 } fmx_mpx_figs;
 int  fmx_mpx_figures(const fmx_mpx_find *cfg, const float *mean, const float *peak, fmx_mpx_figs *out);
 
+/* ---- The sub-carrier decoder (no counterpart in the reference, which stops at 59.4 kHz; contract: DESIGN.md 4.17).  Per decoding CHANNEL the audio of
+ * an FM sub-carrier (SCA) at centre_hz -- 67, 76 or 82 kHz at 192 kS/s -- of the demodulator output d [j] at R = fmRate: exactly the value of
+ * FMX_TAP_DEMOD, the row stage B leaves behind.  j counts the handle's fm samples since fmx_create.
+ * Taps, designed in double on the host and rounded to f32, the same for every channel (fmx_sca_taps hands them out):
+ *   g [0 .. 191]  the band filter: a Kaiser (beta = 7) windowed sinc with its 6 dB point at half_band_hz + 2000 at rate R, normalised to sum 1;
+ *   a [0 .. 127]  the audio filter: an 81-tap Kaiser (beta = 7) low-pass with its 6 dB point at audio_cut_hz + 1300 at rate R / 4, convolved with the
+ *                 first 48 values of (1 - alpha) alpha^i, alpha = exp (-4 / (R tau)) (tau = 0: the unit impulse), normalised to sum 1.  The de-emphasis
+ *                 is part of this FIR: nothing recursive is carried between calls.
+ * Arithmetic:
+ *     y [m] = sum_k g [k] d [4 m - k] exp (-2 pi i ((centre_hz (4 m - k)) mod R) / R)          (rate R / 4)
+ *     u [m] = arg (y [m] conj (y [m - 1])) R / (8 pi deviation_hz),  arg (0) = 0
+ *     s [n] = sum_k a [k] u [2 n - k]                                                           (audio, rate R / 8: 24 kS/s)
+ *     level [b] = the mean of |y [m]|^2 over m in [480 b, 480 b + 480)
+ * The form of the f32 arithmetic: the mix is folded into per-channel complex taps c [k] = f32 (g [k] exp (+2 pi i ((centre_hz k) mod R) / R)), formed in
+ * double with the phase reduced in integers; y' [m] = sum_k c [k] d [4 m - k] (fmaf, k ascending) equals y [m] up to a rotation of modulus one, so
+ * |y'|^2 = |y|^2 and y [m] conj (y [m - 1]) = y' [m] conj (y' [m - 1]) rot with the one constant rot = f32 (exp (-2 pi i ((4 centre_hz) mod R) / R)) per
+ * channel.  No per-sample phase exists, so the arithmetic is the same at any j, beyond 2^32 fm samples too.
+ * The peak injection of the sub-carrier is 2 sqrt (level) in d's units; times fmx_mod_hz_per_unit: in Hz.
+ * Blocks: block b is the audio samples [240 b, 240 b + 240); they belong to the fm samples [1920 b, 1920 b + 1920) (10 ms at 192 kS/s).  A block is a pure
+ * function of d [1920 b - 703, 1920 b + 1920) (LOOKBACK = 191 + 4 x 128 = 703) and is computed when the piece that holds its last fm sample has run.
+ * Carried between pieces per decoding channel: the up to 703 + 1919 samples of d not yet consumed, nothing else: on the same d a block is bit for bit the
+ * same however the stream is cut into calls and a call into pieces.
+ * Switch: per channel, from any thread, takes effect at the next call.  The first delivered block is the first with 1920 b - 703 >= the first fm sample of
+ * the piece that switched the channel on: every delivered sample has its whole history from real d.  Switching off drops the block in progress.  A scanning
+ * channel decodes on.  The device keeps the last 128 blocks (1.28 s) per channel.
+ * Rows: a decoding channel needs the handle-wide rows exactly as a modulation-metered channel does (see fmx_mod_meter_enable).  Everything else a handle
+ * delivers -- PCM, RDS, meta, taps, peaks, scan records, the six meters' records -- is bit for bit, or equal to, what it is on the same handle with a
+ * modulation meter instead of the decoder.  A handle that never decodes allocates and launches nothing; memory (135 432 bytes per channel: 128 blocks of
+ * 240 + 1 f32, the carry, the mixed taps) is allocated for the channels that are switched on. */
+typedef struct fmx_sca_config {
+    int32_t struct_size;       /* sizeof(fmx_sca_config) */
+    int32_t half_band_hz;      /* half width of the band filter, default 9000 */
+    int32_t audio_cut_hz;      /* audio low-pass cut-off, default 5000 */
+    int32_t deviation_hz;      /* the deviation that maps to an output of +-1.0, default 6000 */
+    int32_t deemphasis_us;     /* de-emphasis time constant, default 150; 0: none */
+} fmx_sca_config;
+typedef struct fmx_sca_info_t {
+    int32_t audio_rate_hz;     /* fmRate / 8 */
+    int32_t block_audio;       /* 240 audio samples per block */
+    int32_t block_fm;          /* 1920 fm samples per block */
+    int32_t lookback_fm;       /* 703 */
+    double  delay_fm;          /* the linear-phase delay in fm samples: 95.5 + 4 x 40 (the de-emphasis adds its own, frequency-dependent) */
+    int32_t ring_blocks;       /* 128 */
+    int32_t bytes_per_channel; /* device memory per decoding channel */
+} fmx_sca_info_t;
+/* the setup, handle-wide (cfg NULL: the defaults); only while no channel decodes, else FMX_E_INVALID.  Blocks not yet read are lost. */
+int  fmx_sca_setup(fmx_handle h, const fmx_sca_config *cfg);
+/* switches the decoder of a channel (-1: of every channel) on at centre_hz, or off with centre_hz = 0; from any thread, takes effect at the next call.
+ * FMX_E_INVALID unless centre_hz - half_band_hz + 2000 >= 59 400 (the pass band's lower edge may come within the filter's 2000 Hz transition of the top of
+ * the RDS band: with the defaults 66 400 Hz and up) and centre_hz + half_band_hz + 2000 <= fmRate / 2 (with the defaults at 192 kS/s 85 000 Hz and down:
+ * 67, 76 and 82 kHz are admitted, 92 kHz is refused); fmx_last_error says which.  At 67 kHz the filter's skirt overlaps the RDS band (54.6 .. 59.4 kHz):
+ * under a programme with RDS about 0.02 rms of the output is that band. */
+int  fmx_sca_enable(fmx_handle h, int32_t channel, int32_t centre_hz);
+/* The consecutive blocks of channels first_channel .. first_channel + n_channels - 1 completed since this function last read each of them, oldest first,
+ * at most capacity_blocks_per_channel each, in ONE read-out of the device: channel q's run begins at block first_block [q] and has n_blocks [q] blocks,
+ * block i's audio at audio [(q cap + i) 240 ..], its level at level [q cap + i] (level may be NULL).  A run ends at a gap -- blocks the reader lost, or
+ * that fell while the channel was off --; the rest comes with the next read, and the gap shows in first_block.  Waits for the handle's last call only.
+ * A read that fails moves no cursor. */
+int  fmx_sca_read(fmx_handle h, int32_t first_channel, int32_t n_channels, int64_t *first_block, float *audio, float *level,
+                  int32_t capacity_blocks_per_channel, int32_t *n_blocks);
+/* host only, no device: the taps a handle with that setup runs at fmRate (cfg NULL: the defaults).  which 0: g (192), 1: a (128).  Copies
+ * min (capacity, count) floats to dst (dst may be NULL with capacity 0) and stores the count in *n. */
+int  fmx_sca_taps(const fmx_sca_config *cfg, int32_t fmRate, int32_t which, float *dst, int32_t capacity, int32_t *n);
+/* host only, no device */
+int  fmx_sca_info(int32_t fmRate, fmx_sca_info_t *out);
+
 /* introspection used by the parity tests: the filter taps the kernels run with.
  * which: 0 front-end polyphase taps, 1 PSS low-pass, 2 audio+resampler FIR, 3 resampler alone,
  * 4 the noise squelch's two order-20 filters: [2][10] x (A1, A2, B1, B2), then the two gains (high-pass first),

@@ -771,6 +771,50 @@ int ensure_mpx(fmx_handle h) {
     return FMX_OK;
 }
 
+// The sub-carrier decoder's memory (fmx_sca.hip), under mtx, grown as ensure_mpx grows the multiplex spectrum meter's: a slot for every channel that decodes
+// and has none yet -- sca::BYTES_PER_CHANNEL: the ring's audio and levels, the carry, the mixed taps --, the arrays allocated anew and the old slots copied.
+// The audio filter is one per handle; a slot's mixed taps are made by stage_sca when its channel is switched on.
+int ensure_sca(fmx_handle h) {
+    const size_t NC = (size_t)h->channels;
+    if (h->sca_slot.empty()) {
+        h->sca_slot.assign(NC, -1); h->sca_slot_centre.assign(NC, 0); h->sca_on_from.assign(NC, -1); h->sca_tag.assign(NC * sca::RING, -1);
+        h->rd.sca.assign(NC, 0); h->call_sca.assign(NC, 0);
+    }
+    if (h->sca_taps_stale) {
+        HIPCHK(hipDeviceSynchronize());
+        h->sca_g = sca::design_band(h->sca_cfg, h->cfg.fmRate);
+        h->mem.release(h->d_sca_a);
+        FMXCHK(h->mem.upload(h->d_sca_a, sca::design_audio(h->sca_cfg, h->cfg.fmRate)));
+        std::fill(h->sca_slot_centre.begin(), h->sca_slot_centre.end(), 0);      // (every slot's mixed taps are made anew)
+        h->sca_taps_stale = false;
+    }
+    int32_t need = h->sca_slots;
+    for (size_t c = 0; c < NC; c++) if (h->user_sca[c] && h->sca_slot[c] < 0) need++;
+    if (need > h->sca_cap) {
+        HIPCHK(hipDeviceSynchronize());
+        if (!h->ev_sca) HIPCHK(hipEventCreateWithFlags(&h->ev_sca, hipEventDisableTiming));
+        float *carry = nullptr, *audio = nullptr, *level = nullptr; float2 *taps = nullptr;
+        FMXCHK(h->mem.alloc(carry, (size_t)need * sca::CARRY_STRIDE, true));
+        FMXCHK(h->mem.alloc(audio, (size_t)need * sca::RING * sca::BLOCK_AUDIO, true));
+        FMXCHK(h->mem.alloc(level, (size_t)need * sca::RING, true));
+        FMXCHK(h->mem.alloc(taps, (size_t)need * (sca::NG + 1), true));
+        if (h->sca_slots > 0) {
+            const size_t k = (size_t)h->sca_slots;
+            HIPCHK(hipMemcpy(carry, h->d_sca_carry, sizeof(float) * k * sca::CARRY_STRIDE, hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(audio, h->d_sca_audio, sizeof(float) * k * sca::RING * sca::BLOCK_AUDIO, hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(level, h->d_sca_level, sizeof(float) * k * sca::RING, hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(taps, h->d_sca_taps, sizeof(float2) * k * (sca::NG + 1), hipMemcpyDeviceToDevice));
+            HIPCHK(hipDeviceSynchronize());
+        }
+        h->mem.release(h->d_sca_carry); h->mem.release(h->d_sca_audio); h->mem.release(h->d_sca_level); h->mem.release(h->d_sca_taps); h->mem.release(h->d_sca_jobs);
+        h->d_sca_carry = carry; h->d_sca_audio = audio; h->d_sca_level = level; h->d_sca_taps = taps;
+        FMXCHK(h->mem.alloc(h->d_sca_jobs, (size_t)need));
+        h->sca_cap = need;
+    }
+    for (size_t c = 0; c < NC; c++) if (h->user_sca[c] && h->sca_slot[c] < 0) h->sca_slot[c] = h->sca_slots++;
+    return FMX_OK;
+}
+
 // the tiled work arrays of the demodulator pre-pass (fmx_demod.hip): limited / unlimited samples in, demodulator output out.  (Allocated by the first call
 // that needs them -- before run_call decides how the call is made: a call in pieces needs them too.)
 int ensure_prepass_arrays(fmx_handle h) {
@@ -785,7 +829,7 @@ CallNeeds summarize(fmx_handle h) {
     for (size_t c = 0; c < h->params.size(); c++) {
         const ChanParams &p = h->params[c];
         const FrontSet &fs = h->h_front_sets[(size_t)p.front_set];
-        needs_add(nd, ChanNeeds{p.decoder, p.squelch_mode, p.rds_mode, p.lo_freq, p.att_l, p.att_r, fs.nd, fs.dc_k, (h->user[c].meter || (!h->user_mpx.empty() && h->user_mpx[c])) ? 1 : 0});
+        needs_add(nd, ChanNeeds{p.decoder, p.squelch_mode, p.rds_mode, p.lo_freq, p.att_l, p.att_r, fs.nd, fs.dc_k, (h->user[c].meter || (!h->user_mpx.empty() && h->user_mpx[c]) || (!h->user_sca.empty() && h->user_sca[c])) ? 1 : 0});
     }
     return nd;
 }
@@ -854,6 +898,18 @@ int flush_mailbox(fmx_handle h) {
         // (mpx_live: stage_mpx has something to do -- a meter is on, or was and its channel's first sample has not been cleared yet)
         if (std::any_of(h->user_mpx.begin(), h->user_mpx.end(), [](uint8_t on) { return on != 0; })) { const int rc = ensure_mpx(h); if (rc) return rc; h->mpx_live = true; }
         if (!h->call_mpx.empty()) h->call_mpx = h->user_mpx;
+    }
+    // (the sub-carrier decoder reads the rows a decoding channel asks for above -- ChanNeeds::metered -- and its own memory.  fmx_sca_setup's values are
+    // taken over here, while no channel decodes: cursors and what the ring held start over.  sca_live: stage_sca has something to do -- a channel decodes,
+    // or did and its first sample has not been cleared yet)
+    if (h->sca_setup_dirty) {
+        h->sca_cfg = h->sca_cfg_user; h->sca_setup_dirty = false; h->sca_taps_stale = true;
+        std::fill(h->sca_on_from.begin(), h->sca_on_from.end(), -1); std::fill(h->sca_tag.begin(), h->sca_tag.end(), -1);
+        std::fill(h->rd.sca.begin(), h->rd.sca.end(), 0);
+    }
+    if (!h->user_sca.empty()) {
+        if (std::any_of(h->user_sca.begin(), h->user_sca.end(), [](int32_t hz) { return hz != 0; })) { const int rc = ensure_sca(h); if (rc) return rc; h->sca_live = true; }
+        if (!h->call_sca.empty()) h->call_sca = h->user_sca;
     }
     if (nd.keep_taps && !h->w_diff_mem) {
         HIPCHK(hipDeviceSynchronize());
@@ -1207,6 +1263,46 @@ int stage_mpx(fmx_handle h, const CallGeom &G, hipStream_t s) {
     return FMX_OK;
 }
 
+// The sub-carrier decoder: the decoding channels' rows of the piece through fmx_sca.hip, on the stream stage B ran on and behind it, where stage_rds, the
+// modulation meter and the multiplex spectrum meter read the same rows.  What the piece's fm samples [J0, J1) mean per channel is sca::piece's integers,
+// which the kernels form again from {channel, slot, first block}.  A channel switched on -- or to another centre -- by this piece gets its mixed taps here.
+// Of a piece that completes more than 128 blocks only the last 128 are formed.  The ring tags -- which block a slot holds -- change under mtx with the
+// event fmx_sca_read waits for.
+int stage_sca(fmx_handle h, const CallGeom &G, hipStream_t s) {
+    const int64_t nj = G.J1 - G.J0;
+    if (nj > h->work_nj) return fail(FMX_E_TOO_LARGE, "the piece has more fm samples than stage B's rows hold");
+    std::lock_guard<std::mutex> lk(h->mtx);
+    h->sca_jobs.clear();
+    for (int c = 0; c < h->channels; c++) {
+        const int32_t centre = h->call_sca[(size_t)c];
+        if (!centre) { h->sca_on_from[(size_t)c] = -1; continue; }          // (off: the block in progress is dropped)
+        const int32_t slot = h->sca_slot[(size_t)c];
+        if (h->sca_slot_centre[(size_t)c] != centre) {                       // (another centre is another sub-carrier: it starts as a channel switched on does)
+            std::vector<float2> taps = sca::mixed_taps(h->sca_g, centre, h->cfg.fmRate);
+            taps.push_back(sca::rotation(centre, h->cfg.fmRate));
+            // (pageable source: the copy is staged before the call returns)
+            HIPCHK(hipMemcpyAsync(h->d_sca_taps + (size_t)slot * (sca::NG + 1), taps.data(), sizeof(float2) * taps.size(), hipMemcpyHostToDevice, s));
+            h->sca_slot_centre[(size_t)c] = centre; h->sca_on_from[(size_t)c] = -1;
+        }
+        if (h->sca_on_from[(size_t)c] < 0) h->sca_on_from[(size_t)c] = G.J0;
+        h->sca_jobs.push_back(ScaJob{c, slot, sca::first_block(h->sca_on_from[(size_t)c])});
+    }
+    const int64_t n_jobs = (int64_t)h->sca_jobs.size();
+    if (n_jobs == 0) { h->sca_live = false; return FMX_OK; }      // (no channel decodes and every first sample is cleared: nothing to do until one is switched on)
+    HIPCHK(hipMemcpyAsync(h->d_sca_jobs, h->sca_jobs.data(), sizeof(ScaJob) * (size_t)n_jobs, hipMemcpyHostToDevice, s));
+    const int64_t bn = G.J0 / sca::BLOCK_FM, be = G.J1 / sca::BLOCK_FM;
+    ScaArgs A{};
+    A.jobs = h->d_sca_jobs; A.n_jobs = (int32_t)n_jobs; A.w_dem = h->B.w_dem; A.lin_rows = h->B.lin_rows; A.J0 = G.J0; A.nj = nj;
+    A.b_lo = std::max(bn, be - sca::RING); A.nb = (int32_t)(be - A.b_lo);
+    A.scale = sca::u_scale(h->sca_cfg, h->cfg.fmRate); A.a = h->d_sca_a; A.taps = h->d_sca_taps;
+    A.carry = h->d_sca_carry; A.audio = h->d_sca_audio; A.level = h->d_sca_level;
+    launch_sca(A, s);
+    HIPCHK(hipEventRecord(h->ev_sca, s)); h->ev_sca_set = true;
+    for (const ScaJob &job : h->sca_jobs)
+        for (int64_t b = std::max(A.b_lo, job.first); b < be; b++) h->sca_tag[(size_t)job.channel * sca::RING + (size_t)(b % sca::RING)] = b;
+    return FMX_OK;
+}
+
 // the reception meter: the metered channels' fm samples of the piece, out of stage A's ring, into their lane accumulators, every window that ends in it into
 // the record ring (fmx_rx.hip) -- on the stream stage A ran on, behind this piece's stage A and ahead of the next one's, as stage_scan.  The sample in front
 // of the piece's first comes from the ring: rx::ring_holds says that stage A has not yet written over it (with fmx_create's sizing of the ring it always
@@ -1401,6 +1497,7 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     if (rds_running && (rc = stage_rds(h, G, s))) return rc;
     if (h->meter_alloc && G.J1 > G.J0 && (rc = stage_meter(h, G, s))) return rc;
     if (h->mpx_live && G.J1 > G.J0 && (rc = stage_mpx(h, G, s))) return rc;
+    if (h->sca_live && G.J1 > G.J0 && (rc = stage_sca(h, G, s))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[2], s));
     if ((rc = stage_c(h, G, d_pcm, frames, second, s))) return rc;
     if (!h->call_scan.empty() && frames > 0 && (rc = stage_scan_mute(h, d_pcm, G.pcm_stride, frames, s))) return rc;
@@ -1751,7 +1848,7 @@ int fmx_destroy(fmx_handle h) {
     for (auto &pr : h->prof) for (int i = 0; i < 4; i++) (void)hipEventDestroy(pr.e[i]);
     for (hipEvent_t e : h->step_ev) if (e) (void)hipEventDestroy(e);
     if (h->rd_stream) { (void)hipStreamSynchronize(h->rd_stream); (void)hipStreamDestroy(h->rd_stream); }
-    for (hipEvent_t e : {h->ev_call, h->ev_spec, h->ev_mpx, h->ev_in, h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {h->ev_call, h->ev_spec, h->ev_mpx, h->ev_sca, h->ev_in, h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
     for (hipStream_t st : {h->stream, h->pipe_sA, h->pipe_sP, h->pipe_sB}) if (st) (void)hipStreamDestroy(st);
     h->mem.release_all(); h->rds_mem.release_all();
     delete h;
@@ -1908,6 +2005,32 @@ int fmx_mpx_spectrum_enable(fmx_handle h, int32_t channel, int32_t on) {
     if (h->user_mpx.empty()) h->user_mpx.assign((size_t)h->channels, 0);
     const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
     for (int c = c0; c < c1; c++) h->user_mpx[(size_t)c] = on != 0;
+    return FMX_OK;
+}
+
+int fmx_sca_setup(fmx_handle h, const fmx_sca_config *cfg) {
+    if (!h) return fail(FMX_E_INVALID, "null handle");
+    const fmx_sca_config want = cfg ? *cfg : sca::default_config();
+    if (const char *why = sca::config_error(&want, h->cfg.fmRate)) return fail(FMX_E_INVALID, std::string("fmx_sca_setup: ") + why);
+    std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes the values over at the next call)
+    if (std::any_of(h->user_sca.begin(), h->user_sca.end(), [](int32_t hz) { return hz != 0; }))
+        return fail(FMX_E_INVALID, "fmx_sca_setup: a channel's sub-carrier decoder is on");
+    h->sca_cfg_user = want; h->sca_setup_dirty = true;
+    return FMX_OK;
+}
+
+int fmx_sca_enable(fmx_handle h, int32_t channel, int32_t centre_hz) {
+    if (!h) return fail(FMX_E_INVALID, "null handle");
+    if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
+    if (centre_hz < 0) return fail(FMX_E_INVALID, "centre_hz must not be negative");
+    std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
+    const fmx_sca_config &cfg = h->sca_setup_dirty ? h->sca_cfg_user : h->sca_cfg;
+    if (const char *why = sca::centre_error(centre_hz, cfg.half_band_hz, h->cfg.fmRate))
+        return fail(FMX_E_INVALID, "fmx_sca_enable: centre_hz " + std::to_string(centre_hz) + " with half_band_hz " + std::to_string(cfg.half_band_hz) + " at fmRate " +
+                                       std::to_string(h->cfg.fmRate) + ": " + why);
+    if (h->user_sca.empty()) h->user_sca.assign((size_t)h->channels, 0);
+    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
+    for (int c = c0; c < c1; c++) h->user_sca[(size_t)c] = centre_hz;
     return FMX_OK;
 }
 

@@ -14,6 +14,7 @@
 #include "fmx_rdsgroups.h"
 #include "fmx_spec.h"
 #include "fmx_mpx.h"
+#include "fmx_sca.h"
 
 #include <algorithm>
 #include <atomic>
@@ -123,6 +124,7 @@ struct Readers {
     std::vector<int64_t> rdsm;               // fmx_rds_meter_records: records of fmx_handle_s::rdsm_produced
     std::vector<int64_t> spec;               // fmx_spectrum_read, per STREAM: the next record index it hands out (sized by the meter's first use)
     std::vector<int64_t> mpx;                // fmx_mpx_spectrum_read, per channel: the next record index it hands out (sized by the meter's first use)
+    std::vector<int64_t> sca;                // fmx_sca_read, per channel: the next block it hands out (sized by the decoder's first use)
     std::vector<uint8_t> reset_dec, reset_dec_all;   // resetRds / triggerFrequencyChange asked for the group decoder's reset: fmx_rds_decode's, fmx_rds_decode_all's (under mtx)
     std::vector<RdsGroupDecoderHost> dec, dec_all;   // fmx_rds_decode's decoders (the synchroniser on the host), fmx_rds_decode_all's (on the GPU: rds_sync)
     void init(size_t channels) {
@@ -263,6 +265,21 @@ struct fmx_handle_s {
     // the read-out's staging (fmx_mpx_spectrum_read, under mtx): which ring records to gather, where they are gathered, and the pinned copy of that
     int32_t *d_mpx_src = nullptr; float *d_mpx_stage = nullptr, *h_mpx_stage = nullptr; int64_t mpx_stage_recs = 0; std::vector<int32_t> mpx_src;
     hipEvent_t ev_mpx = nullptr; bool ev_mpx_set = false;               // behind the last piece's kernels: what fmx_mpx_spectrum_read waits for
+    // the sub-carrier decoder (fmx_sca.hip, fmx_sca.h), per CHANNEL, kept as the multiplex spectrum meter keeps its channels: the user's centre frequency
+    // (0: off; under mtx), the centres of the piece being made (flush_mailbox), the fm sample of the piece that switched the channel on (-1: off), its slot
+    // in the decoder's device memory (-1: none yet; a channel keeps its slot), the centre its slot's taps were made for, and per ring slot the block it holds
+    // (-1: none).  Per slot the device keeps the ring's audio (120 KB) and levels, the carry (10.25 KB) and the mixed taps with the rotation (1544 bytes)
+    std::vector<int32_t> user_sca, call_sca, sca_slot, sca_slot_centre;
+    std::vector<int64_t> sca_on_from, sca_tag;
+    fmx_sca_config sca_cfg = sca::default_config(), sca_cfg_user = sca::default_config(); bool sca_setup_dirty = false;
+    bool sca_taps_stale = true;                                          // d_sca_a is not sca_cfg's (the setup changed, or nothing was uploaded yet)
+    int32_t sca_slots = 0, sca_cap = 0;
+    std::vector<float> sca_g;                                            // the band filter of sca_cfg (the mixed taps are made from it per centre)
+    float *d_sca_a = nullptr, *d_sca_carry = nullptr, *d_sca_audio = nullptr, *d_sca_level = nullptr; float2 *d_sca_taps = nullptr;
+    ScaJob *d_sca_jobs = nullptr; std::vector<ScaJob> sca_jobs;
+    bool sca_live = false;                                               // some channel decodes, or did in the last piece that looked (stage_sca runs)
+    int32_t *d_sca_src = nullptr; float *d_sca_stage = nullptr, *h_sca_stage = nullptr; int64_t sca_stage_blocks = 0; std::vector<int32_t> sca_src;
+    hipEvent_t ev_sca = nullptr; bool ev_sca_set = false;                // behind the last piece's kernels: what fmx_sca_read waits for
     std::atomic<int> stageb_form{0};     // FMX_P_STAGEB_FORM
     std::atomic<int> front_parts{0};     // FMX_P_FRONT_PARTS
     std::atomic<int> front_kernel{0};    // FMX_P_FRONT_KERNEL

@@ -586,6 +586,28 @@ void launch_mpx(const MpxArgs &A, hipStream_t s);
 // the read-out: ring record src [q] (slot * mpx::RING + r mod mpx::RING; 2 x 2048 floats) to out [q], q < n
 void launch_mpx_gather(const float *ring, const int32_t *src, float *out, int n, hipStream_t s);
 
+// ---- the sub-carrier decoder (fmx_sca.hip, fmx_sca.h) ------------------------------------------------------------------
+// one decoding channel of a piece: the handle's channel, its slot in the decoder's memory, and the first block it delivers (sca::first_block)
+struct ScaJob { int32_t channel, slot; int64_t first; };
+// One piece [J0, J0 + nj): the blocks [b_lo, b_lo + nb) -- every block some job completes in it; a job skips those in front of its own first -- become ring
+// slots; then every job's carry is rewritten (sca::piece).
+struct ScaArgs {
+    const ScaJob *jobs;                        // [n_jobs] (copied per piece on the stream of the launch)
+    int32_t n_jobs;
+    const float *w_dem; int32_t lin_rows;      // stage B's demodulator rows: channel c's fm sample J0 + q at w_dem [c * lin_rows + q]
+    int64_t J0, nj;
+    int64_t b_lo; int32_t nb;
+    float scale;                               // sca::u_scale
+    const float *a;                            // [128] the audio filter
+    const float2 *taps;                        // [slots][193]: the channel's 192 mixed taps, then rot
+    float *carry;                              // [slots][sca::CARRY_STRIDE]
+    float *audio;                              // [slots][sca::RING][240]
+    float *level;                              // [slots][sca::RING]
+};
+void launch_sca(const ScaArgs &A, hipStream_t s);
+// the read-out: block src [q] (slot * sca::RING + b mod sca::RING) to out [q] as 240 audio samples and the level (241 floats), q < n
+void launch_sca_gather(const float *audio, const float *level, const int32_t *src, float *out, int n, hipStream_t s);
+
 void launch_front(const DeviceTables &T, const DeviceBuffers &B, const CallGeom &G, const void *iq,
                   int channels, hipStream_t s);
 // fmx_front4.hip: whole tiles of the call front4_kernel can take (0: none), and its launch over that many

@@ -1,6 +1,6 @@
 // fmx_needs.h -- what a handle's settings mean for its next call: which values a setter accepts and what it derives from them, the one summary of the
 // channels' settings a call's kernels and buffers are chosen from (CallNeeds), stage A's kernel, the plain batch, and the cursors of the rings the
-// read-outs hand out.  A metered channel (fmx_mod_meter_enable or fmx_mpx_spectrum_enable) sets rows_on as an RDS channel does: the rows w_dem / w_cur are handle-wide, so a batch with
+// read-outs hand out.  A metered channel (fmx_mod_meter_enable, fmx_mpx_spectrum_enable or fmx_sca_enable) sets rows_on as an RDS channel does: the rows w_dem / w_cur are handle-wide, so a batch with
 // one metered channel writes 8 bytes per fm sample for EVERY channel and takes the non-plain call shape.  Plain C++ (no HIP, no handle, no allocation, no lock): fmx_api.hip decides with these functions, tests/needs_check.cpp checks
 // them on the CPU.
 #pragma once
@@ -110,7 +110,7 @@ struct ChanNeeds {                     // what the summary reads of one channel:
     int32_t decoder, squelch_mode, rds_mode, lo_freq;
     float   att_l, att_r;
     int32_t nd, dc_k;                  // ... and of its FrontSet
-    int32_t metered;                   // ... and whether its modulation meter or its multiplex spectrum meter is on (fmx_mod_meter_enable, fmx_mpx_spectrum_enable)
+    int32_t metered;                   // ... and whether its modulation meter, its multiplex spectrum meter or its sub-carrier decoder is on (fmx_mod_meter_enable, fmx_mpx_spectrum_enable, fmx_sca_enable)
 };
 struct CallNeeds {
     bool any_lo;                       // some channel has a local oscillator (the LO table; stage A's complex-tap variant)
@@ -120,7 +120,7 @@ struct CallNeeds {
     int  prepass_var;                  // DeviceBuffers::prepass_var
     bool any_nsq;                      // some channel runs the noise squelch (its filters' coefficients)
     bool keep_taps, rows_on, peaks_on; // FMX_P_SCOPE_TAPS resolved; DeviceBuffers::rows_on, ::peaks_on
-    bool any_meter;                    // some channel's modulation meter or multiplex spectrum meter is on
+    bool any_meter;                    // some channel's modulation meter, multiplex spectrum meter or sub-carrier decoder is on
 };
 inline CallNeeds needs_begin(int channels, int twins, bool ola_mode, int scope_taps) {
     CallNeeds n{};

@@ -584,6 +584,97 @@ int fmx_mpx_figures(const fmx_mpx_find *cfg, const float *mean, const float *pea
     return rc == FMX_OK ? FMX_OK : fail(rc, why);
 }
 
+// The sub-carrier decoder's blocks of a range of channels.  Which block a ring slot holds is the host's (fmx_handle_s::sca_tag).  Per channel the run of
+// consecutive blocks from the oldest one not yet read; the runs of the whole range are gathered on the device into one staging array (sca_gather_kernel)
+// behind the handle's last call, and leave it in ONE copy to pinned memory (a range of more than SCA_READ_BATCH blocks: one copy per 65 536 blocks, 63 MB
+// of staging at the most).  The cursors move only when every copy has arrived: a read that fails loses nothing.
+constexpr int64_t SCA_READ_BATCH = 65536;
+int fmx_sca_read(fmx_handle h, int32_t first_channel, int32_t n_channels, int64_t *first_block, float *audio, float *level,
+                 int32_t capacity_blocks_per_channel, int32_t *n_blocks) {
+    if (!h || !n_blocks || !first_block) return fail(FMX_E_INVALID, "null argument");
+    if (first_channel < 0 || n_channels < 1 || n_channels > h->channels || first_channel > h->channels - n_channels) return fail(FMX_E_INVALID, "channel range out of range");
+    for (int q = 0; q < n_channels; q++) { n_blocks[q] = 0; first_block[q] = -1; }
+    const int32_t cap = capacity_blocks_per_channel;
+    if (cap < 0 || (cap > 0 && !audio)) return fail(FMX_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mtx);
+    if (h->sca_tag.empty() || cap == 0) return FMX_OK;
+    constexpr int REC = sca::BLOCK_AUDIO + 1;
+    h->sca_src.clear();
+    std::vector<size_t> dst;
+    std::vector<int64_t> from((size_t)n_channels, -1);
+    std::vector<int32_t> count((size_t)n_channels, 0);
+    for (int q = 0; q < n_channels; q++) {
+        const size_t ch = (size_t)(first_channel + q);
+        int64_t oldest = -1;
+        for (int k = 0; k < sca::RING; k++) {
+            const int64_t b = h->sca_tag[ch * sca::RING + (size_t)k];
+            if (b >= h->rd.sca[ch] && (oldest < 0 || b < oldest)) oldest = b;      // (older ones were read, or overwritten: the gap shows in first_block)
+        }
+        if (oldest < 0) continue;
+        int32_t n = 0;
+        while (n < cap && n < sca::RING && h->sca_tag[ch * sca::RING + (size_t)((oldest + n) % sca::RING)] == oldest + n) {      // (the run ends at a gap)
+            h->sca_src.push_back(h->sca_slot[ch] * sca::RING + (int32_t)((oldest + n) % sca::RING));
+            dst.push_back((size_t)q * (size_t)cap + (size_t)n);
+            n++;
+        }
+        from[(size_t)q] = oldest; count[(size_t)q] = n;
+    }
+    const int64_t total = (int64_t)dst.size();
+    if (total == 0) return FMX_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (!h->rd_stream) HIPCHK(hipStreamCreateWithFlags(&h->rd_stream, hipStreamNonBlocking));
+    if (h->ev_sca_set) HIPCHK(hipStreamWaitEvent(h->rd_stream, h->ev_sca, 0));
+    const int64_t batch = std::min(total, SCA_READ_BATCH);
+    if (batch > h->sca_stage_blocks) {
+        h->mem.release(h->d_sca_src); h->mem.release(h->d_sca_stage); h->mem.release(h->h_sca_stage); h->sca_stage_blocks = 0;
+        FMXCHK(h->mem.alloc(h->d_sca_src, (size_t)batch));
+        FMXCHK(h->mem.alloc(h->d_sca_stage, (size_t)batch * REC));
+        FMXCHK(h->mem.alloc_pinned(h->h_sca_stage, (size_t)batch * REC));
+        h->sca_stage_blocks = batch;
+    }
+    g_launch_err = hipSuccess;
+    for (int64_t o = 0; o < total; o += batch) {
+        const int64_t m = std::min(batch, total - o);
+        HIPCHK(hipMemcpyAsync(h->d_sca_src, h->sca_src.data() + o, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, h->rd_stream));
+        launch_sca_gather(h->d_sca_audio, h->d_sca_level, h->d_sca_src, h->d_sca_stage, (int)m, h->rd_stream);
+        HIPCHK(g_launch_err);
+        HIPCHK(hipMemcpyAsync(h->h_sca_stage, h->d_sca_stage, sizeof(float) * (size_t)m * REC, hipMemcpyDeviceToHost, h->rd_stream));
+        HIPCHK(hipStreamSynchronize(h->rd_stream));
+        for (int64_t i = 0; i < m; i++) {
+            const float *src = h->h_sca_stage + (size_t)i * REC;
+            std::memcpy(audio + dst[(size_t)(o + i)] * sca::BLOCK_AUDIO, src, sizeof(float) * sca::BLOCK_AUDIO);
+            if (level) level[dst[(size_t)(o + i)]] = src[sca::BLOCK_AUDIO];
+        }
+    }
+    for (int q = 0; q < n_channels; q++)
+        if (count[(size_t)q] > 0) {
+            h->rd.sca[(size_t)(first_channel + q)] = from[(size_t)q] + count[(size_t)q];
+            first_block[q] = from[(size_t)q]; n_blocks[q] = count[(size_t)q];
+        }
+    return FMX_OK;
+}
+
+int fmx_sca_taps(const fmx_sca_config *cfg, int32_t fmRate, int32_t which, float *dst, int32_t capacity, int32_t *n) {
+    if (!n) return fail(FMX_E_INVALID, "fmx_sca_taps: n is null");
+    const fmx_sca_config want = cfg ? *cfg : sca::default_config();
+    if (const char *why = sca::config_error(&want, fmRate)) return fail(FMX_E_INVALID, std::string("fmx_sca_taps: ") + why);
+    if (which != 0 && which != 1) return fail(FMX_E_INVALID, "fmx_sca_taps: which must be 0 (g) or 1 (a)");
+    if (capacity < 0 || (capacity > 0 && !dst)) return fail(FMX_E_INVALID, "fmx_sca_taps: dst is null");
+    const std::vector<float> t = which == 0 ? sca::design_band(want, fmRate) : sca::design_audio(want, fmRate);
+    *n = (int32_t)t.size();
+    std::copy(t.begin(), t.begin() + std::min<int32_t>(capacity, *n), dst);
+    return FMX_OK;
+}
+
+int fmx_sca_info(int32_t fmRate, fmx_sca_info_t *out) {
+    if (!out) return fail(FMX_E_INVALID, "fmx_sca_info: out is null");
+    if (fmRate < 8000 || fmRate > 1000000 || fmRate % 8 != 0) return fail(FMX_E_INVALID, "fmx_sca_info: fmRate must be a multiple of 8 in [8000, 1000000]");
+    out->audio_rate_hz = fmRate / (sca::D1 * sca::D2); out->block_audio = sca::BLOCK_AUDIO; out->block_fm = sca::BLOCK_FM; out->lookback_fm = sca::LOOKBACK;
+    out->delay_fm = (sca::NG - 1) / 2.0 + sca::D1 * ((sca::NLP - 1) / 2.0);
+    out->ring_blocks = sca::RING; out->bytes_per_channel = (int32_t)sca::BYTES_PER_CHANNEL;
+    return FMX_OK;
+}
+
 int64_t fmx_pll_replays(fmx_handle h, int32_t channel) { return sum_chan_states(h, channel, [](const ChanState &s) { return s.pll_replays; }); }
 int64_t fmx_pll_exact_segments(fmx_handle h, int32_t channel) { return sum_chan_states(h, channel, [](const ChanState &s) { return s.pll_exact_segs; }); }
 int32_t fmx_last_front_kernel(fmx_handle h) { return h ? h->last_front_kernel : 0; }

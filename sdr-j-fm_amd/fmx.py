@@ -39,7 +39,7 @@ EXPORTS = [
     "fmx_abi_version", "fmx_last_error", "fmx_create", "fmx_destroy", "fmx_set_param", "fmx_frames_for", "fmx_filter_change_due",
     "fmx_process_host", "fmx_process_device", "fmx_process_host_raw", "fmx_process_device_raw", "fmx_synchronize",
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
-    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rx_meter_enable", "fmx_rx_records", "fmx_rx_quality_of", "fmx_rds_meter_enable", "fmx_rds_meter_records", "fmx_rds_meter_cal", "fmx_rds_meter_figures", "fmx_spectrum_setup", "fmx_spectrum_enable", "fmx_spectrum_read", "fmx_spectrum_figures", "fmx_mpx_spectrum_setup", "fmx_mpx_spectrum_enable", "fmx_mpx_spectrum_read", "fmx_mpx_figures", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
+    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rx_meter_enable", "fmx_rx_records", "fmx_rx_quality_of", "fmx_rds_meter_enable", "fmx_rds_meter_records", "fmx_rds_meter_cal", "fmx_rds_meter_figures", "fmx_spectrum_setup", "fmx_spectrum_enable", "fmx_spectrum_read", "fmx_spectrum_figures", "fmx_mpx_spectrum_setup", "fmx_mpx_spectrum_enable", "fmx_mpx_spectrum_read", "fmx_mpx_figures", "fmx_sca_setup", "fmx_sca_enable", "fmx_sca_read", "fmx_sca_taps", "fmx_sca_info", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
     "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
     "fmx_wideband_survey_enable", "fmx_wideband_survey_read", "fmx_wideband_survey_stations",
     "fmx_wideband_create_rate", "fmx_wideband_outputs_for", "fmx_wideband_rate_taps", "fmx_wideband_survey_stations_rate",
@@ -139,6 +139,21 @@ MPX_RECORD_DTYPE = np.dtype([("index", np.int64), ("end_sample", np.int64), ("bl
 assert MPX_RECORD_DTYPE.itemsize == C.sizeof(FmxMpxRecord) == 24
 MPX_BINS = 2048               # bin k at k * fmRate / 4096 Hz
 MPX_RING = 4                  # records the library keeps per metered channel
+
+
+class FmxScaConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("half_band_hz", C.c_int32), ("audio_cut_hz", C.c_int32), ("deviation_hz", C.c_int32), ("deemphasis_us", C.c_int32)]
+
+
+class FmxScaInfo(C.Structure):
+    _fields_ = [("audio_rate_hz", C.c_int32), ("block_audio", C.c_int32), ("block_fm", C.c_int32), ("lookback_fm", C.c_int32), ("delay_fm", C.c_double),
+                ("ring_blocks", C.c_int32), ("bytes_per_channel", C.c_int32)]
+
+
+SCA_BLOCK_AUDIO = 240         # audio samples per block, at fmRate / 8
+SCA_BLOCK_FM = 1920           # fm samples per block
+SCA_LOOKBACK = 703            # fm samples a block reads in front of its first
+SCA_RING = 128                # blocks the library keeps per decoding channel
 
 
 class FmxMeta(C.Structure):
@@ -359,6 +374,16 @@ def load_library(path=None):
     L.fmx_mpx_spectrum_read.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
     L.fmx_mpx_figures.restype = C.c_int
     L.fmx_mpx_figures.argtypes = [C.POINTER(FmxMpxFind), vp, vp, C.POINTER(FmxMpxFigs)]
+    L.fmx_sca_setup.restype = C.c_int
+    L.fmx_sca_setup.argtypes = [vp, C.POINTER(FmxScaConfig)]
+    L.fmx_sca_enable.restype = C.c_int
+    L.fmx_sca_enable.argtypes = [vp, i32, i32]
+    L.fmx_sca_read.restype = C.c_int
+    L.fmx_sca_read.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
+    L.fmx_sca_taps.restype = C.c_int
+    L.fmx_sca_taps.argtypes = [C.POINTER(FmxScaConfig), i32, i32, vp, i32, C.POINTER(i32)]
+    L.fmx_sca_info.restype = C.c_int
+    L.fmx_sca_info.argtypes = [i32, C.POINTER(FmxScaInfo)]
     L.fmx_mod_hz_per_unit.restype = C.c_int
     L.fmx_mod_hz_per_unit.argtypes = [i32, i32, C.POINTER(C.c_double)]
     L.fmx_rds_bits.restype = C.c_int
@@ -517,6 +542,35 @@ def mpx_figures(mean, peak=None, rate_hz=192000, hz_per_unit=1.0, dc_guard_hz=30
     for name, _ in FmxMpxFigs._fields_[10:]:
         figs[name] = list(getattr(out, name))[:min(nb, 16)]
     return figs
+
+
+def _sca_config(half_band_hz=9000, audio_cut_hz=5000, deviation_hz=6000, deemphasis_us=150):
+    return FmxScaConfig(C.sizeof(FmxScaConfig), int(half_band_hz), int(audio_cut_hz), int(deviation_hz), int(deemphasis_us))
+
+
+def sca_taps(which, rate_hz=192000, **setup):
+    """The taps a handle with that setup (half_band_hz, audio_cut_hz, deviation_hz, deemphasis_us) runs its sub-carrier decoder with (fmx_sca_taps;
+    host only, needs no device): which 0 or "g" -> the 192-tap band filter at fmRate, 1 or "a" -> the 128-tap audio filter at fmRate / 4."""
+    L = load_library()
+    which = {"g": 0, "a": 1}.get(which, which)
+    cfg = _sca_config(**setup)
+    out = np.zeros(192, np.float32)
+    n = C.c_int32()
+    rc = L.fmx_sca_taps(C.byref(cfg), int(rate_hz), int(which), out.ctypes.data, out.size, C.byref(n))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
+    return out[:n.value].copy()
+
+
+def sca_info(rate_hz=192000):
+    """The sub-carrier decoder's numbers at fmRate (fmx_sca_info; host only): a dict of audio_rate_hz, block_audio, block_fm, lookback_fm, delay_fm,
+    ring_blocks and bytes_per_channel."""
+    L = load_library()
+    out = FmxScaInfo()
+    rc = L.fmx_sca_info(int(rate_hz), C.byref(out))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
+    return {name: getattr(out, name) for name, _ in FmxScaInfo._fields_}
 
 
 def rds_meter_figures(records, cal, hz_per_unit):
@@ -744,6 +798,28 @@ class Fmx:
         self._check(self.L.fmx_mpx_spectrum_read(self.h, int(first), int(count), recs.ctypes.data, mean.ctypes.data, pk.ctypes.data if peak else None,
                                                  int(capacity), n.ctypes.data))
         return [(recs[q, :n[q]].copy(), mean[q, :n[q]].copy(), (pk[q, :n[q]].copy() if peak else None)) for q in range(count)]
+
+    def sca_setup(self, half_band_hz=9000, audio_cut_hz=5000, deviation_hz=6000, deemphasis_us=150):
+        """The sub-carrier decoder's setup, handle-wide (fmx_sca_setup).  Only while no channel decodes."""
+        cfg = _sca_config(half_band_hz, audio_cut_hz, deviation_hz, deemphasis_us)
+        self._check(self.L.fmx_sca_setup(self.h, C.byref(cfg)))
+
+    def sca_enable(self, centre_hz=67000, channel=-1):
+        """Switch the sub-carrier decoder of a channel (-1: of every channel) on at centre_hz, or off with 0, from the next call on (fmx_sca_enable)."""
+        self._check(self.L.fmx_sca_enable(self.h, int(channel), int(centre_hz)))
+
+    def sca_read(self, first=0, count=1, capacity=SCA_RING, level=True):
+        """The consecutive blocks of channels first .. first + count - 1 completed since each one's last read, oldest first, in one read-out of the device
+        (fmx_sca_read) -> a list with one (first_block or -1, audio [n, 240] f32 at fmRate / 8, level [n] f32 or None) per channel.  A run ends at a
+        gap; the rest comes with the next read.  The library keeps the last 128 blocks per decoding channel."""
+        cap = max(int(capacity), 1)
+        first_block = np.zeros(count, np.int64)
+        audio = np.zeros((count, cap, SCA_BLOCK_AUDIO), np.float32)
+        lv = np.zeros((count, cap), np.float32) if level else None
+        n = np.zeros(count, np.int32)
+        self._check(self.L.fmx_sca_read(self.h, int(first), int(count), first_block.ctypes.data, audio.ctypes.data, lv.ctypes.data if level else None,
+                                        int(capacity), n.ctypes.data))
+        return [(int(first_block[q]), audio[q, :n[q]].copy(), (lv[q, :n[q]].copy() if level else None)) for q in range(count)]
 
     def rds_meter_cal(self, channel=0):
         """The calibration of a channel's RDS meter from the handle's own taps (fmx_rds_meter_cal): a dict of gain, phase0_deg and path_57k."""
@@ -1092,6 +1168,12 @@ class FmProcessor:
     def pollMpxSpectrum(self):
         """The multiplex spectrum meter's records of this channel since the last poll: (records as MPX_RECORD_DTYPE, mean [n, 2048], peak [n, 2048])."""
         return self.fmx.mpx_spectrum_read(self.channel, 1)[0]
+
+    def setScaDecoder(self, centre_hz): self.fmx.sca_enable(centre_hz, self.channel)
+
+    def pollSca(self):
+        """The sub-carrier decoder's blocks of this channel since the last poll: (first_block or -1, audio [n, 240] at fmRate / 8, level [n])."""
+        return self.fmx.sca_read(self.channel, 1)[0]
 
     def isPilotLocked(self):
         m = self.fmx.meta(self.channel)

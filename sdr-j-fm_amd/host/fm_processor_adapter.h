@@ -254,6 +254,19 @@ public:
     static bool mpxFigures(const fmx_mpx_find *cfg, const float *mean, const float *peak, fmx_mpx_figs *f) {
         return fmx_mpx_figures(cfg, mean, peak, f) == FMX_OK;
     }
+    // the sub-carrier decoder (include/fmx.h fmx_sca_*; no counterpart in the reference): setScaSetup sets the filters and the deviation while no channel
+    // decodes (NULL: the defaults), setScaDecoder switches this processor's channel on at centre_hz (67 000, 76 000, 82 000 at 192 kS/s; 0: off) with the next
+    // call, pollSca calls `emit_fn(int64_t block, const float *audio, float level)` (240 samples at fmRate / 8) once per block completed since the last
+    // poll, oldest first, up to a gap
+    bool setScaSetup(const fmx_sca_config *cfg) { return h && check(fmx_sca_setup(h, cfg)); }
+    bool setScaDecoder(int32_t centre_hz) { return h && check(fmx_sca_enable(h, 0, centre_hz)); }
+    template <class F> int pollSca(F emit_fn) {
+        int64_t first = -1; int32_t n = 0;
+        std::vector<float> audio((size_t)128 * 240), level(128);
+        if (!h || fmx_sca_read(h, 0, 1, &first, audio.data(), level.data(), 128, &n) != FMX_OK) return 0;
+        for (int32_t k = 0; k < n; k++) emit_fn(first + k, audio.data() + (size_t)k * 240, level[(size_t)k]);
+        return n;
+    }
     // the RDS picture of this processor's channel(s) in one read-out of the device (fmx_rds_decode_all: the block synchroniser has run on the GPU,
     // the group decoder runs here): what the rds classes' signals carried, infos[k] for channel first + k
     bool poll_rds(fmx_rds_info *infos, int32_t first = 0, int32_t count = 1) { return h && check(fmx_rds_decode_all(h, first, count, infos)); }
