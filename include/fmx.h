@@ -831,6 +831,66 @@ int  fmx_sca_taps(const fmx_sca_config *cfg, int32_t fmRate, int32_t which, floa
 /* host only, no device */
 int  fmx_sca_info(int32_t fmRate, fmx_sca_info_t *out);
 
+/* ---- The monitoring feed (no counterpart in the reference; contract: DESIGN.md 4.18).  Per feeding CHANNEL 16 kS/s mono audio, the form speech-to-text,
+ * music and advert recognition and logging recorders take, so that the 48 kHz stereo PCM can stay on the device.
+ * Input: the feeding channel's PCM, exactly the frames the call delivers, as d_pcm holds them behind both channel groups' audio kernels, the gain
+ * correction and the scan mute -- where the programme audio meter reads them.  A scanning channel's zeros are included.  Frame m counts the handle's PCM
+ * frames since fmx_create (fmx_meta.pcm_frames).  A handle with audioRate != 48000 answers FMX_E_UNSUPPORTED, as the audio meter does.
+ * Taps: one filter h [0 .. 143], designed in double on the host and rounded to f32, the same for every channel and every handle (fmx_feed_taps hands it
+ * out): a Kaiser (beta = 8) windowed sinc with its 6 dB point at 8000 Hz at 48 000 frames/s, normalised to sum 1 -- within +-0.0006 dB up to 7 kHz,
+ * -81.96 dB and below from 9 kHz (the band that folds onto 0 .. 7 kHz), sum of |h| = 2.112.
+ * Arithmetic (IEEE f32, subnormals kept, no contraction other than the fmaf written here):
+ *     v [m] = 0.5f * (xL [m] + xR [m])   mode 1 (one rounding: the sum);   xL [m]: mode 2;   xR [m]: mode 3
+ *     y [n] = sum_k h [k] v [3 n - k]     fmaf, k ascending from an accumulator of 0.0f;  feed sample n <-> frame 3 n
+ *     power [b] = the mean of y [n]^2 over n in [160 b, 160 b + 160): the products rounded to f32 and summed in one fixed tree (csrc/fmx_feed.h states it)
+ * No per-sample phase and no recursion: the arithmetic is the same at any m, beyond 2^32 frames too.
+ * Blocks: block b is the feed samples [160 b, 160 b + 160), 10 ms; they belong to the frames [480 b, 480 b + 480).  A block is a pure function of
+ * v [480 b - 143, 480 b + 480) (LOOKBACK = 143) and is computed when the piece that holds its last frame has run.  Carried between pieces per feeding
+ * channel: the up to 143 + 479 values of v not yet consumed, nothing else: on the same PCM a block is bit for bit the same however the stream is cut into
+ * calls and a call into pieces.  (The PCM itself depends on the cut in its last bits: DESIGN.md 4.12.)
+ * Switch: per channel, from any thread, takes effect at the next call.  The first delivered block is the first with 480 b - 143 >= the first frame of the
+ * piece that switched the channel on: every delivered sample has its whole history from real PCM.  Switching off drops the block in progress and the
+ * carry.  A call that finds a channel on in another mode than it runs in restarts it at that piece, as if it had been switched off and on.
+ * Ring: the device keeps the last 128 blocks (1.28 s) per channel.  A handle that never feeds allocates and launches nothing; memory (84 928 bytes per
+ * channel: 128 blocks of 160 + 1 f32, the carry) is allocated for the channels that are switched on.
+ * Isolation: everything else a handle delivers -- PCM, RDS, meta, taps, peaks, scan records, every meter's records, SCA blocks -- is bit for bit what it
+ * is without the feed. */
+typedef enum { FMX_FEED_F32 = 0, FMX_FEED_S16 = 1 } fmx_feed_format;
+typedef struct fmx_feed_info_t {
+    int32_t rate_hz;           /* 16000 */
+    int32_t block_samples;     /* 160 feed samples per block */
+    int32_t block_frames;      /* 480 PCM frames per block */
+    int32_t lookback_frames;   /* 143 */
+    double  delay_frames;      /* the linear-phase delay in PCM frames: 71.5 */
+    int32_t ring_blocks;       /* 128 */
+    int32_t bytes_per_channel; /* device memory per feeding channel */
+} fmx_feed_info_t;
+/* switches the feed of a channel (-1: of every channel): mode 0 off, 1 (L + R) / 2, 2 left, 3 right; from any thread, takes effect at the next call.
+ * FMX_E_INVALID for another mode or a channel out of range, FMX_E_UNSUPPORTED on a handle with audioRate != 48000. */
+int  fmx_feed_enable(fmx_handle h, int32_t channel, int32_t mode);
+/* The consecutive blocks of channels first_channel .. first_channel + n_channels - 1 completed since fmx_feed_read or fmx_feed_read_device last read each
+ * of them, oldest first, at most capacity_blocks_per_channel each, in ONE read-out of the device: channel q's run begins at block first_block [q] (-1:
+ * none) and has n_blocks [q] blocks; block i of channel q is at element (q cap + i) 160 of audio, its power at power [q cap + i] (power may be NULL).
+ * format FMX_FEED_F32: the ring's values; FMX_FEED_S16: (int16) min (32767, max (-32768, rintf (y * 32768.0f))), round half to even, converted on the
+ * device, so that two bytes per sample cross to the host.  A run ends at a gap -- blocks the reader lost, or that fell while the channel was off --; the
+ * rest comes with the next read, and the gap shows in first_block.  Waits for the handle's last call only.  A read that fails -- a range outside the
+ * handle's channels, a null first_block or n_blocks, a negative capacity, a capacity with a null audio or a capacity of 0 with an audio, an unknown format:
+ * FMX_E_INVALID; n_channels x capacity_blocks_per_channel above 2^31 - 1 blocks: FMX_E_TOO_LARGE -- moves no cursor. */
+int  fmx_feed_read(fmx_handle h, int32_t first_channel, int32_t n_channels, int64_t *first_block, void *audio, int32_t format,
+                   float *power, int32_t capacity_blocks_per_channel, int32_t *n_blocks);
+/* The same gather written to the caller's DEVICE buffers d_audio and d_power (d_power may be NULL), asynchronous on hip_stream (NULL: the handle's own
+ * stream), with the stream rule of fmx_process_device: the gather runs behind the handle's last call and behind what hip_stream holds; what reads the
+ * buffers runs on hip_stream behind it, or synchronises.  first_block and n_blocks are HOST arrays and are known on return: they come from the host's
+ * tags.  A consumer on the device -- a PyTorch tensor [channels, blocks x 160] -- takes the feed without the audio ever leaving the device's memory. */
+int  fmx_feed_read_device(fmx_handle h, int32_t first_channel, int32_t n_channels, int64_t *first_block, void *d_audio, int32_t format,
+                          float *d_power, int32_t capacity_blocks_per_channel, int32_t *n_blocks, void *hip_stream);
+/* host only, no device: the feed's 144 taps.  Copies min (capacity, 144) floats to dst (dst may be NULL with capacity 0) and stores 144 in *n. */
+int  fmx_feed_taps(float *dst, int32_t capacity, int32_t *n);
+/* host only, no device */
+int  fmx_feed_info(fmx_feed_info_t *out);
+/* the bytes of device memory the handle has allocated for the feed's rings and carries (0: it never fed) */
+int64_t fmx_feed_allocated(fmx_handle h);
+
 /* introspection used by the parity tests: the filter taps the kernels run with.
  * which: 0 front-end polyphase taps, 1 PSS low-pass, 2 audio+resampler FIR, 3 resampler alone,
  * 4 the noise squelch's two order-20 filters: [2][10] x (A1, A2, B1, B2), then the two gains (high-pass first),

@@ -7,6 +7,6 @@ fmProcessor interface).  Import with ``importlib.import_module("sdr-j-fm_amd")``
 import os as _os
 
 
-from .fmx import (Fmx, FmProcessor, FmxError, Wideband, survey_stations, spectrum_figures, mpx_figures, sca_taps, sca_info, load_library, EXPORTS, LIB_PATH)  # noqa: F401
+from .fmx import (Fmx, FmProcessor, FmxError, Wideband, survey_stations, spectrum_figures, mpx_figures, sca_taps, sca_info, feed_taps, feed_info, load_library, EXPORTS, LIB_PATH)  # noqa: F401
 from . import fmx, shard  # noqa: F401
 from .filesource import WavFileSource  # noqa: F401

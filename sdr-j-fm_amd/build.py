@@ -33,6 +33,7 @@ SOURCES = [
     ("fmx_spec.hip", []),                          # (the spectrum meter shares the survey's transform: compiled as the survey is)
     ("fmx_mpx.hip", []),                           # (the multiplex spectrum meter: the same transform, compiled the same way)
     ("fmx_sca.hip", []),                           # (the sub-carrier decoder: every product an explicit fmaf)
+    ("fmx_feed.hip", ["-ffp-contract=off"]),       # (the monitoring feed: the only fused operations are its explicit fmaf)
     # the host files (fmx_host.h): they design filters through fmx_design.h, whose taps must not depend on contraction either
     ("fmx_api.hip", ["-ffp-contract=off"]),
     ("fmx_readout.hip", ["-ffp-contract=off"]),

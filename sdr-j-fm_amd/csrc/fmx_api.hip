@@ -815,6 +815,41 @@ int ensure_sca(fmx_handle h) {
     return FMX_OK;
 }
 
+// The monitoring feed's memory (fmx_feed.hip), under mtx, grown as ensure_sca grows the sub-carrier decoder's: a slot for every channel that feeds and has
+// none yet -- feed::BYTES_PER_CHANNEL: the ring's audio and powers, the carry --, the arrays allocated anew and the old slots copied.  The taps are one
+// array per handle, uploaded with the first slot.
+int ensure_feed(fmx_handle h) {
+    const size_t NC = (size_t)h->channels;
+    if (h->feed_slot.empty()) {
+        h->feed_slot.assign(NC, -1); h->feed_mode.assign(NC, 0); h->feed_on_from.assign(NC, -1); h->feed_tag.assign(NC * feed::RING, -1);
+        h->rd.feed.assign(NC, 0); h->call_feed.assign(NC, 0);
+    }
+    int32_t need = h->feed_slots;
+    for (size_t c = 0; c < NC; c++) if (h->user_feed[c] && h->feed_slot[c] < 0) need++;
+    if (need > h->feed_cap) {
+        HIPCHK(hipDeviceSynchronize());
+        if (!h->ev_feed) HIPCHK(hipEventCreateWithFlags(&h->ev_feed, hipEventDisableTiming));
+        if (!h->d_feed_h) FMXCHK(h->mem.upload(h->d_feed_h, feed::design()));
+        float *carry = nullptr, *audio = nullptr, *power = nullptr;
+        FMXCHK(h->mem.alloc(carry, (size_t)need * feed::CARRY_STRIDE, true));
+        FMXCHK(h->mem.alloc(audio, (size_t)need * feed::RING * feed::BLOCK, true));
+        FMXCHK(h->mem.alloc(power, (size_t)need * feed::RING, true));
+        if (h->feed_slots > 0) {
+            const size_t k = (size_t)h->feed_slots;
+            HIPCHK(hipMemcpy(carry, h->d_feed_carry, sizeof(float) * k * feed::CARRY_STRIDE, hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(audio, h->d_feed_audio, sizeof(float) * k * feed::RING * feed::BLOCK, hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemcpy(power, h->d_feed_power, sizeof(float) * k * feed::RING, hipMemcpyDeviceToDevice));
+            HIPCHK(hipDeviceSynchronize());
+        }
+        h->mem.release(h->d_feed_carry); h->mem.release(h->d_feed_audio); h->mem.release(h->d_feed_power); h->mem.release(h->d_feed_jobs);
+        h->d_feed_carry = carry; h->d_feed_audio = audio; h->d_feed_power = power;
+        FMXCHK(h->mem.alloc(h->d_feed_jobs, (size_t)need));
+        h->feed_cap = need;
+    }
+    for (size_t c = 0; c < NC; c++) if (h->user_feed[c] && h->feed_slot[c] < 0) h->feed_slot[c] = h->feed_slots++;
+    return FMX_OK;
+}
+
 // the tiled work arrays of the demodulator pre-pass (fmx_demod.hip): limited / unlimited samples in, demodulator output out.  (Allocated by the first call
 // that needs them -- before run_call decides how the call is made: a call in pieces needs them too.)
 int ensure_prepass_arrays(fmx_handle h) {
@@ -910,6 +945,12 @@ int flush_mailbox(fmx_handle h) {
     if (!h->user_sca.empty()) {
         if (std::any_of(h->user_sca.begin(), h->user_sca.end(), [](int32_t hz) { return hz != 0; })) { const int rc = ensure_sca(h); if (rc) return rc; h->sca_live = true; }
         if (!h->call_sca.empty()) h->call_sca = h->user_sca;
+    }
+    // (the monitoring feed reads the call's PCM behind everything that writes it, as the audio meter does, and its own memory: no part of CallNeeds.
+    // feed_live: stage_feed has something to do -- a channel feeds, or did and its first frame has not been cleared yet)
+    if (!h->user_feed.empty()) {
+        if (std::any_of(h->user_feed.begin(), h->user_feed.end(), [](int32_t mode) { return mode != 0; })) { const int rc = ensure_feed(h); if (rc) return rc; h->feed_live = true; }
+        if (!h->call_feed.empty()) h->call_feed = h->user_feed;
     }
     if (nd.keep_taps && !h->w_diff_mem) {
         HIPCHK(hipDeviceSynchronize());
@@ -1413,6 +1454,39 @@ int stage_audio_meter(fmx_handle h, const CallGeom &G, const float2 *d_pcm, int6
     return FMX_OK;
 }
 
+// The monitoring feed: the feeding channels' frames of the piece, as d_pcm now holds them, through fmx_feed.hip -- on `s`, right beside the audio meter:
+// behind both channel groups' audio kernels, the gain correction and the scan mute.  What the piece's frames [M0, M0 + frames) mean per channel is
+// feed::piece's integers, which the kernels form again from {channel, slot, mode, first block}.  A channel found on in another mode than it runs in starts
+// as a channel switched on does.  A piece without a frame only takes the switches over.  Of a piece that completes more than 128 blocks only the last 128
+// are formed.  The ring tags -- which block a slot holds -- change under mtx with the event the read-outs wait for.
+int stage_feed(fmx_handle h, const CallGeom &G, const float2 *d_pcm, int64_t frames, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(h->mtx);
+    h->feed_jobs.clear();
+    for (int c = 0; c < h->channels; c++) {
+        const int32_t mode = h->call_feed[(size_t)c];
+        if (!mode) { h->feed_on_from[(size_t)c] = -1; h->feed_mode[(size_t)c] = 0; continue; }      // (off: the block in progress and the carry are dropped)
+        if (h->feed_mode[(size_t)c] != mode) { h->feed_mode[(size_t)c] = mode; h->feed_on_from[(size_t)c] = -1; }
+        if (h->feed_on_from[(size_t)c] < 0) h->feed_on_from[(size_t)c] = G.M0;
+        h->feed_jobs.push_back(FeedJob{c, h->feed_slot[(size_t)c], mode, 0, feed::first_block(h->feed_on_from[(size_t)c])});
+    }
+    const int64_t n_jobs = (int64_t)h->feed_jobs.size();
+    if (n_jobs == 0) { h->feed_live = false; return FMX_OK; }      // (no channel feeds and every first frame is cleared: nothing to do until one is switched on)
+    if (frames <= 0) return FMX_OK;
+    if (h->ev_feed_rd_set) HIPCHK(hipStreamWaitEvent(s, h->ev_feed_rd, 0));      // (a fmx_feed_read_device still gathering on another stream reads the ring first)
+    // (pageable source: the copy is staged before the call returns)
+    HIPCHK(hipMemcpyAsync(h->d_feed_jobs, h->feed_jobs.data(), sizeof(FeedJob) * (size_t)n_jobs, hipMemcpyHostToDevice, s));
+    const int64_t be = (G.M0 + frames) / feed::BLOCK_FRAMES;
+    FeedArgs A{};
+    A.jobs = h->d_feed_jobs; A.n_jobs = (int32_t)n_jobs; A.pcm = d_pcm; A.pcm_stride = G.pcm_stride; A.M0 = G.M0; A.frames = (int32_t)frames;
+    A.b_lo = feed::formed_from(G.M0, frames); A.nb = (int32_t)(be - A.b_lo);
+    A.h = h->d_feed_h; A.carry = h->d_feed_carry; A.audio = h->d_feed_audio; A.power = h->d_feed_power;
+    launch_feed(A, s);
+    HIPCHK(hipEventRecord(h->ev_feed, s)); h->ev_feed_set = true;
+    for (const FeedJob &job : h->feed_jobs)
+        for (int64_t b = std::max(A.b_lo, job.first); b < be; b++) h->feed_tag[(size_t)job.channel * feed::RING + (size_t)feed::ring_slot(b)] = b;
+    return FMX_OK;
+}
+
 // stage C: the audio filter and resampler (the block machines: the audio low-pass and the de-emphasis in front of it), a gain change's correction, the
 // second converter
 int stage_c(fmx_handle h, CallGeom &G, float2 *d_pcm, int64_t frames, int second, hipStream_t s) {
@@ -1502,6 +1576,7 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     if ((rc = stage_c(h, G, d_pcm, frames, second, s))) return rc;
     if (!h->call_scan.empty() && frames > 0 && (rc = stage_scan_mute(h, d_pcm, G.pcm_stride, frames, s))) return rc;
     if (h->loud_alloc && frames > 0 && (rc = stage_audio_meter(h, G, d_pcm, frames, s))) return rc;
+    if (h->feed_live && (rc = stage_feed(h, G, d_pcm, frames, s))) return rc;
     if (prof) { HIPCHK(hipEventRecord(pr.e[3], s)); h->prof.push_back(pr); }
     FMX_LAUNCHED();
     HIPCHK(g_launch_err);
@@ -1848,7 +1923,7 @@ int fmx_destroy(fmx_handle h) {
     for (auto &pr : h->prof) for (int i = 0; i < 4; i++) (void)hipEventDestroy(pr.e[i]);
     for (hipEvent_t e : h->step_ev) if (e) (void)hipEventDestroy(e);
     if (h->rd_stream) { (void)hipStreamSynchronize(h->rd_stream); (void)hipStreamDestroy(h->rd_stream); }
-    for (hipEvent_t e : {h->ev_call, h->ev_spec, h->ev_mpx, h->ev_sca, h->ev_in, h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {h->ev_call, h->ev_spec, h->ev_mpx, h->ev_sca, h->ev_feed, h->ev_feed_rd, h->ev_in, h->pipe_ev0, h->pipe_evA, h->pipe_evD, h->pipe_evP, h->pipe_evE, h->pipe_evB[0], h->pipe_evB[1]}) if (e) (void)hipEventDestroy(e);
     for (hipStream_t st : {h->stream, h->pipe_sA, h->pipe_sP, h->pipe_sB}) if (st) (void)hipStreamDestroy(st);
     h->mem.release_all(); h->rds_mem.release_all();
     delete h;
@@ -2032,6 +2107,25 @@ int fmx_sca_enable(fmx_handle h, int32_t channel, int32_t centre_hz) {
     const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
     for (int c = c0; c < c1; c++) h->user_sca[(size_t)c] = centre_hz;
     return FMX_OK;
+}
+
+int fmx_feed_enable(fmx_handle h, int32_t channel, int32_t mode) {
+    if (!h) return fail(FMX_E_INVALID, "null handle");
+    if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
+    if (mode < feed::MODE_OFF || mode > feed::MODE_RIGHT) return fail(FMX_E_INVALID, "fmx_feed_enable: mode must be 0 (off), 1 ((L + R) / 2), 2 (left) or 3 (right)");
+    if (h->cv_nt != 0 || h->cfg.audioRate != 48000)
+        return fail(FMX_E_UNSUPPORTED, "the feed's filter and its divide by 3 are those of 48000 frames/s: not on a handle with another audioRate");
+    std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
+    if (h->user_feed.empty()) h->user_feed.assign((size_t)h->channels, 0);
+    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
+    for (int c = c0; c < c1; c++) h->user_feed[(size_t)c] = mode;
+    return FMX_OK;
+}
+
+int64_t fmx_feed_allocated(fmx_handle h) {
+    if (!h) return 0;
+    std::lock_guard<std::mutex> lk(h->mtx);
+    return (int64_t)h->feed_cap * feed::BYTES_PER_CHANNEL;
 }
 
 int64_t fmx_filter_change_due(fmx_handle h) {

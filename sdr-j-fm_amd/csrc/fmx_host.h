@@ -15,6 +15,7 @@
 #include "fmx_spec.h"
 #include "fmx_mpx.h"
 #include "fmx_sca.h"
+#include "fmx_feed.h"
 
 #include <algorithm>
 #include <atomic>
@@ -125,6 +126,7 @@ struct Readers {
     std::vector<int64_t> spec;               // fmx_spectrum_read, per STREAM: the next record index it hands out (sized by the meter's first use)
     std::vector<int64_t> mpx;                // fmx_mpx_spectrum_read, per channel: the next record index it hands out (sized by the meter's first use)
     std::vector<int64_t> sca;                // fmx_sca_read, per channel: the next block it hands out (sized by the decoder's first use)
+    std::vector<int64_t> feed;               // fmx_feed_read / fmx_feed_read_device, per channel: the next block they hand out (sized by the feed's first use)
     std::vector<uint8_t> reset_dec, reset_dec_all;   // resetRds / triggerFrequencyChange asked for the group decoder's reset: fmx_rds_decode's, fmx_rds_decode_all's (under mtx)
     std::vector<RdsGroupDecoderHost> dec, dec_all;   // fmx_rds_decode's decoders (the synchroniser on the host), fmx_rds_decode_all's (on the GPU: rds_sync)
     void init(size_t channels) {
@@ -280,6 +282,21 @@ struct fmx_handle_s {
     bool sca_live = false;                                               // some channel decodes, or did in the last piece that looked (stage_sca runs)
     int32_t *d_sca_src = nullptr; float *d_sca_stage = nullptr, *h_sca_stage = nullptr; int64_t sca_stage_blocks = 0; std::vector<int32_t> sca_src;
     hipEvent_t ev_sca = nullptr; bool ev_sca_set = false;                // behind the last piece's kernels: what fmx_sca_read waits for
+    // the monitoring feed (fmx_feed.hip, fmx_feed.h), per CHANNEL, kept as the sub-carrier decoder keeps its channels: the user's mode (0: off; under mtx),
+    // the modes of the piece being made (flush_mailbox), the mode the channel runs in, the frame of the piece that switched it on (-1: off), its slot in the
+    // feed's device memory (-1: none yet; a channel keeps its slot), and per ring slot the block it holds (-1: none).  Per slot the device keeps the ring's
+    // audio (80 KB) and powers and the carry (2496 bytes); the taps are one array per handle
+    std::vector<int32_t> user_feed, call_feed, feed_slot, feed_mode;
+    std::vector<int64_t> feed_on_from, feed_tag;
+    int32_t feed_slots = 0, feed_cap = 0;
+    float *d_feed_h = nullptr, *d_feed_carry = nullptr, *d_feed_audio = nullptr, *d_feed_power = nullptr;
+    FeedJob *d_feed_jobs = nullptr; std::vector<FeedJob> feed_jobs;
+    bool feed_live = false;                                              // some channel feeds, or did in the last piece that looked (stage_feed runs)
+    // the read-outs' staging (under mtx): which ring blocks to gather and where to, where the host read-out gathers them, and the pinned copy of that
+    int32_t *d_feed_src = nullptr; int64_t feed_src_cap = 0; std::vector<int32_t> feed_src, feed_dst;
+    float *d_feed_stage = nullptr, *h_feed_stage = nullptr; int64_t feed_stage_blocks = 0;
+    hipEvent_t ev_feed = nullptr; bool ev_feed_set = false;              // behind the last piece's kernels: what the read-outs wait for
+    hipEvent_t ev_feed_rd = nullptr; bool ev_feed_rd_set = false;        // behind the last fmx_feed_read_device's gather: what the next use of d_feed_src, and the next piece's kernels, wait for
     std::atomic<int> stageb_form{0};     // FMX_P_STAGEB_FORM
     std::atomic<int> front_parts{0};     // FMX_P_FRONT_PARTS
     std::atomic<int> front_kernel{0};    // FMX_P_FRONT_KERNEL

@@ -608,6 +608,29 @@ void launch_sca(const ScaArgs &A, hipStream_t s);
 // the read-out: block src [q] (slot * sca::RING + b mod sca::RING) to out [q] as 240 audio samples and the level (241 floats), q < n
 void launch_sca_gather(const float *audio, const float *level, const int32_t *src, float *out, int n, hipStream_t s);
 
+// ---- the monitoring feed (fmx_feed.hip, fmx_feed.h) ---------------------------------------------------------------------
+// one feeding channel of a piece: the handle's channel, its slot in the feed's memory, its mode (1: (L + R) / 2, 2: left, 3: right) and the first block
+// it delivers (feed::first_block)
+struct FeedJob { int32_t channel, slot, mode, pad; int64_t first; };
+// One piece [M0, M0 + frames) of PCM frames: the blocks [b_lo, b_lo + nb) -- every block some job completes in it; a job skips those in front of its own
+// first -- become ring slots; then every job's carry is rewritten (feed::piece).
+struct FeedArgs {
+    const FeedJob *jobs;                       // [n_jobs] (copied per piece on the stream of the launch)
+    int32_t n_jobs;
+    const float2 *pcm; int64_t pcm_stride;     // the piece's frames as the call delivers them: channel c's frame M0 + q at pcm [c * pcm_stride + q]
+    int64_t M0; int32_t frames;
+    int64_t b_lo; int32_t nb;
+    const float *h;                            // [144] the filter
+    float *carry;                              // [slots][feed::CARRY_STRIDE]
+    float *audio;                              // [slots][feed::RING][160]
+    float *power;                              // [slots][feed::RING]
+};
+void launch_feed(const FeedArgs &A, hipStream_t s);
+// the read-out: ring block src [q] (slot * feed::RING + b mod feed::RING) to block dst [q] of out_audio (160 samples each, f32 or converted to s16:
+// fmx_feed_format) and its power to out_power [dst [q]] (out_power may be null), q < n
+void launch_feed_gather(const float *audio, const float *power, const int32_t *src, const int32_t *dst, void *out_audio, int format, float *out_power, int n,
+                        hipStream_t s);
+
 void launch_front(const DeviceTables &T, const DeviceBuffers &B, const CallGeom &G, const void *iq,
                   int channels, hipStream_t s);
 // fmx_front4.hip: whole tiles of the call front4_kernel can take (0: none), and its launch over that many

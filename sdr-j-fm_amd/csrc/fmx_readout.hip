@@ -675,6 +675,169 @@ int fmx_sca_info(int32_t fmRate, fmx_sca_info_t *out) {
     return FMX_OK;
 }
 
+// The monitoring feed's blocks of a range of channels, for both read-outs.  Which block a ring slot holds is the host's (fmx_handle_s::feed_tag).  Per
+// channel the run of consecutive blocks from the oldest one not yet read.  fmx_feed_read gathers the runs of the whole range on the device into one
+// staging array (feed_gather_kernel, which converts the format) behind the handle's last call, and they leave it in one copy of the audio and one of the
+// powers to pinned memory (a range of more than FEED_READ_BATCH blocks: a pair of copies per 65 536 blocks, 42 MB of staging at the most);
+// fmx_feed_read_device gathers them straight to their places in the caller's device buffers on the caller's stream.  The cursors move only when everything
+// is queued or has arrived: a read that fails loses nothing.
+namespace {
+
+constexpr int64_t FEED_READ_BATCH = 65536;
+
+struct FeedRuns {
+    std::vector<int64_t> from;                 // per channel of the range: the run's first block (-1: none)
+    std::vector<int32_t> count;
+};
+
+// under mtx, lists the runs: ring block h->feed_src [i] goes to block h->feed_dst [i] (q cap + n) of the output; both lists are the handle's, so that
+// an asynchronous upload never reads a vector that has gone
+void feed_runs(fmx_handle h, int32_t first_channel, int32_t n_channels, int32_t cap, FeedRuns &runs) {
+    runs.from.assign((size_t)n_channels, -1); runs.count.assign((size_t)n_channels, 0);
+    h->feed_src.clear(); h->feed_dst.clear();
+    if (h->feed_tag.empty() || cap == 0) return;
+    for (int q = 0; q < n_channels; q++) {
+        const size_t ch = (size_t)(first_channel + q);
+        int64_t oldest = -1;
+        for (int k = 0; k < feed::RING; k++) {
+            const int64_t b = h->feed_tag[ch * feed::RING + (size_t)k];
+            if (b >= h->rd.feed[ch] && (oldest < 0 || b < oldest)) oldest = b;      // (older ones were read, or overwritten: the gap shows in first_block)
+        }
+        if (oldest < 0) continue;
+        int32_t n = 0;
+        while (n < cap && n < feed::RING && h->feed_tag[ch * feed::RING + (size_t)((oldest + n) % feed::RING)] == oldest + n) {      // (the run ends at a gap)
+            h->feed_src.push_back(h->feed_slot[ch] * feed::RING + (int32_t)((oldest + n) % feed::RING));
+            h->feed_dst.push_back((int32_t)((int64_t)q * cap + n));
+            n++;
+        }
+        runs.from[(size_t)q] = oldest; runs.count[(size_t)q] = n;
+    }
+}
+
+int feed_check(fmx_handle h, int32_t first_channel, int32_t n_channels, int64_t *first_block, const void *audio, int32_t format, int32_t cap, int32_t *n_blocks,
+               const char *who) {
+    if (!h || !n_blocks || !first_block) return fail(FMX_E_INVALID, std::string(who) + ": null argument");
+    if (first_channel < 0 || n_channels < 1 || n_channels > h->channels || first_channel > h->channels - n_channels)
+        return fail(FMX_E_INVALID, std::string(who) + ": channel range out of range");
+    for (int q = 0; q < n_channels; q++) { n_blocks[q] = 0; first_block[q] = -1; }
+    if (format != FMX_FEED_F32 && format != FMX_FEED_S16) return fail(FMX_E_INVALID, std::string(who) + ": format must be FMX_FEED_F32 or FMX_FEED_S16");
+    if (cap < 0) return fail(FMX_E_INVALID, std::string(who) + ": capacity_blocks_per_channel is negative");
+    if (cap > 0 && !audio) return fail(FMX_E_INVALID, std::string(who) + ": audio is null");
+    if (cap == 0 && audio) return fail(FMX_E_INVALID, std::string(who) + ": capacity_blocks_per_channel is 0 with an audio buffer");
+    if ((int64_t)n_channels * cap > INT32_MAX) return fail(FMX_E_TOO_LARGE, std::string(who) + ": n_channels x capacity_blocks_per_channel exceeds 2^31 - 1 blocks");
+    return FMX_OK;
+}
+
+// the index arrays of a gather: src then dst, feed_src_cap entries each, behind whatever still reads them
+int feed_index_arrays(fmx_handle h, int64_t n, hipStream_t s) {
+    if (h->ev_feed_rd_set) HIPCHK(hipStreamWaitEvent(s, h->ev_feed_rd, 0));
+    if (n > h->feed_src_cap) {
+        if (h->ev_feed_rd_set) HIPCHK(hipEventSynchronize(h->ev_feed_rd));
+        h->mem.release(h->d_feed_src); h->feed_src_cap = 0;
+        FMXCHK(h->mem.alloc(h->d_feed_src, (size_t)(2 * n)));
+        h->feed_src_cap = n;
+    }
+    return FMX_OK;
+}
+
+void feed_commit(fmx_handle h, int32_t first_channel, int32_t n_channels, const FeedRuns &runs, int64_t *first_block, int32_t *n_blocks) {
+    for (int q = 0; q < n_channels; q++)
+        if (runs.count[(size_t)q] > 0) {
+            h->rd.feed[(size_t)(first_channel + q)] = runs.from[(size_t)q] + runs.count[(size_t)q];
+            first_block[q] = runs.from[(size_t)q]; n_blocks[q] = runs.count[(size_t)q];
+        }
+}
+
+}  // namespace
+
+int fmx_feed_read(fmx_handle h, int32_t first_channel, int32_t n_channels, int64_t *first_block, void *audio, int32_t format, float *power,
+                  int32_t capacity_blocks_per_channel, int32_t *n_blocks) {
+    const int32_t cap = capacity_blocks_per_channel;
+    FMXCHK(feed_check(h, first_channel, n_channels, first_block, audio, format, cap, n_blocks, "fmx_feed_read"));
+    std::lock_guard<std::mutex> lk(h->mtx);
+    FeedRuns runs;
+    feed_runs(h, first_channel, n_channels, cap, runs);
+    const int64_t total = (int64_t)h->feed_dst.size();
+    if (total == 0) return FMX_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (!h->rd_stream) HIPCHK(hipStreamCreateWithFlags(&h->rd_stream, hipStreamNonBlocking));
+    if (h->ev_feed_set) HIPCHK(hipStreamWaitEvent(h->rd_stream, h->ev_feed, 0));
+    const int64_t batch = std::min(total, FEED_READ_BATCH);
+    FMXCHK(feed_index_arrays(h, batch, h->rd_stream));
+    if (batch > h->feed_stage_blocks) {
+        h->mem.release(h->d_feed_stage); h->mem.release(h->h_feed_stage); h->feed_stage_blocks = 0;
+        FMXCHK(h->mem.alloc(h->d_feed_stage, (size_t)batch * (feed::BLOCK + 1)));
+        FMXCHK(h->mem.alloc_pinned(h->h_feed_stage, (size_t)batch * (feed::BLOCK + 1)));
+        h->feed_stage_blocks = batch;
+    }
+    // (the staging array: the audio of the batch's blocks one behind the other in the asked format, then, from float feed_stage_blocks x 160 on, the powers)
+    const size_t esize = format == FMX_FEED_S16 ? sizeof(int16_t) : sizeof(float);
+    const size_t pw_at = (size_t)h->feed_stage_blocks * feed::BLOCK;
+    std::vector<int32_t> seq((size_t)batch);
+    for (int64_t i = 0; i < batch; i++) seq[(size_t)i] = (int32_t)i;
+    g_launch_err = hipSuccess;
+    for (int64_t o = 0; o < total; o += batch) {
+        const int64_t m = std::min(batch, total - o);
+        HIPCHK(hipMemcpyAsync(h->d_feed_src, h->feed_src.data() + o, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, h->rd_stream));
+        HIPCHK(hipMemcpyAsync(h->d_feed_src + h->feed_src_cap, seq.data(), sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, h->rd_stream));
+        launch_feed_gather(h->d_feed_audio, h->d_feed_power, h->d_feed_src, h->d_feed_src + h->feed_src_cap, h->d_feed_stage, format,
+                           power ? h->d_feed_stage + pw_at : nullptr, (int)m, h->rd_stream);
+        HIPCHK(g_launch_err);
+        HIPCHK(hipMemcpyAsync(h->h_feed_stage, h->d_feed_stage, esize * (size_t)m * feed::BLOCK, hipMemcpyDeviceToHost, h->rd_stream));
+        if (power) HIPCHK(hipMemcpyAsync(h->h_feed_stage + pw_at, h->d_feed_stage + pw_at, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost, h->rd_stream));
+        HIPCHK(hipStreamSynchronize(h->rd_stream));
+        for (int64_t i = 0; i < m; i++) {
+            const size_t to = (size_t)h->feed_dst[(size_t)(o + i)];
+            std::memcpy(static_cast<char *>(audio) + to * feed::BLOCK * esize, reinterpret_cast<const char *>(h->h_feed_stage) + (size_t)i * feed::BLOCK * esize,
+                        esize * feed::BLOCK);
+            if (power) power[to] = h->h_feed_stage[pw_at + (size_t)i];
+        }
+    }
+    feed_commit(h, first_channel, n_channels, runs, first_block, n_blocks);
+    return FMX_OK;
+}
+
+int fmx_feed_read_device(fmx_handle h, int32_t first_channel, int32_t n_channels, int64_t *first_block, void *d_audio, int32_t format, float *d_power,
+                         int32_t capacity_blocks_per_channel, int32_t *n_blocks, void *hip_stream) {
+    const int32_t cap = capacity_blocks_per_channel;
+    FMXCHK(feed_check(h, first_channel, n_channels, first_block, d_audio, format, cap, n_blocks, "fmx_feed_read_device"));
+    std::lock_guard<std::mutex> lk(h->mtx);
+    FeedRuns runs;
+    feed_runs(h, first_channel, n_channels, cap, runs);
+    const int64_t total = (int64_t)h->feed_dst.size();
+    if (total == 0) return FMX_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    if (h->ev_feed_set) HIPCHK(hipStreamWaitEvent(s, h->ev_feed, 0));
+    FMXCHK(feed_index_arrays(h, total, s));
+    if (!h->ev_feed_rd) HIPCHK(hipEventCreateWithFlags(&h->ev_feed_rd, hipEventDisableTiming));
+    g_launch_err = hipSuccess;
+    // (pageable sources: the copies are staged before the call returns)
+    HIPCHK(hipMemcpyAsync(h->d_feed_src, h->feed_src.data(), sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->d_feed_src + h->feed_src_cap, h->feed_dst.data(), sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
+    launch_feed_gather(h->d_feed_audio, h->d_feed_power, h->d_feed_src, h->d_feed_src + h->feed_src_cap, d_audio, format, d_power, (int)total, s);
+    HIPCHK(g_launch_err);
+    HIPCHK(hipEventRecord(h->ev_feed_rd, s)); h->ev_feed_rd_set = true;
+    feed_commit(h, first_channel, n_channels, runs, first_block, n_blocks);
+    return FMX_OK;
+}
+
+int fmx_feed_taps(float *dst, int32_t capacity, int32_t *n) {
+    if (!n) return fail(FMX_E_INVALID, "fmx_feed_taps: n is null");
+    if (capacity < 0 || (capacity > 0 && !dst)) return fail(FMX_E_INVALID, "fmx_feed_taps: dst is null");
+    const std::vector<float> t = feed::design();
+    *n = (int32_t)t.size();
+    std::copy(t.begin(), t.begin() + std::min<int32_t>(capacity, *n), dst);
+    return FMX_OK;
+}
+
+int fmx_feed_info(fmx_feed_info_t *out) {
+    if (!out) return fail(FMX_E_INVALID, "fmx_feed_info: out is null");
+    out->rate_hz = feed::RATE; out->block_samples = feed::BLOCK; out->block_frames = feed::BLOCK_FRAMES; out->lookback_frames = feed::LOOKBACK;
+    out->delay_frames = feed::DELAY_FRAMES; out->ring_blocks = feed::RING; out->bytes_per_channel = (int32_t)feed::BYTES_PER_CHANNEL;
+    return FMX_OK;
+}
+
 int64_t fmx_pll_replays(fmx_handle h, int32_t channel) { return sum_chan_states(h, channel, [](const ChanState &s) { return s.pll_replays; }); }
 int64_t fmx_pll_exact_segments(fmx_handle h, int32_t channel) { return sum_chan_states(h, channel, [](const ChanState &s) { return s.pll_exact_segs; }); }
 int32_t fmx_last_front_kernel(fmx_handle h) { return h ? h->last_front_kernel : 0; }

@@ -39,7 +39,7 @@ EXPORTS = [
     "fmx_abi_version", "fmx_last_error", "fmx_create", "fmx_destroy", "fmx_set_param", "fmx_frames_for", "fmx_filter_change_due",
     "fmx_process_host", "fmx_process_device", "fmx_process_host_raw", "fmx_process_device_raw", "fmx_synchronize",
     "fmx_get_meta", "fmx_get_tap", "fmx_get_peaks",
-    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rx_meter_enable", "fmx_rx_records", "fmx_rx_quality_of", "fmx_rds_meter_enable", "fmx_rds_meter_records", "fmx_rds_meter_cal", "fmx_rds_meter_figures", "fmx_spectrum_setup", "fmx_spectrum_enable", "fmx_spectrum_read", "fmx_spectrum_figures", "fmx_mpx_spectrum_setup", "fmx_mpx_spectrum_enable", "fmx_mpx_spectrum_read", "fmx_mpx_figures", "fmx_sca_setup", "fmx_sca_enable", "fmx_sca_read", "fmx_sca_taps", "fmx_sca_info", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
+    "fmx_scan_results", "fmx_mod_meter_enable", "fmx_mod_records", "fmx_mod_hz_per_unit", "fmx_audio_meter_enable", "fmx_audio_records", "fmx_audio_loudness", "fmx_rx_meter_enable", "fmx_rx_records", "fmx_rx_quality_of", "fmx_rds_meter_enable", "fmx_rds_meter_records", "fmx_rds_meter_cal", "fmx_rds_meter_figures", "fmx_spectrum_setup", "fmx_spectrum_enable", "fmx_spectrum_read", "fmx_spectrum_figures", "fmx_mpx_spectrum_setup", "fmx_mpx_spectrum_enable", "fmx_mpx_spectrum_read", "fmx_mpx_figures", "fmx_sca_setup", "fmx_sca_enable", "fmx_sca_read", "fmx_sca_taps", "fmx_sca_info", "fmx_feed_enable", "fmx_feed_read", "fmx_feed_read_device", "fmx_feed_taps", "fmx_feed_info", "fmx_feed_allocated", "fmx_rds_bits", "fmx_rds_symbols", "fmx_last_fm_samples", "fmx_pll_replays", "fmx_pll_exact_segments", "fmx_last_front_kernel", "fmx_last_call_pieces", "fmx_last_second_group", "fmx_last_rds_samples", "fmx_last_rds_samples_of", "fmx_rds_decode", "fmx_rds_decode_all", "fmx_rds_groups", "fmx_rds_decode_bits", "fmx_rds_pty_name", "fmx_rds_map_char", "fmx_rds_prepare_text", "fmx_get_taps", "fmx_profile_enable", "fmx_profile_read",
     "fmx_wideband_create", "fmx_wideband_destroy", "fmx_wideband_set_offset", "fmx_wideband_process_device_raw", "fmx_wideband_process_host_raw", "fmx_wideband_taps",
     "fmx_wideband_survey_enable", "fmx_wideband_survey_read", "fmx_wideband_survey_stations",
     "fmx_wideband_create_rate", "fmx_wideband_outputs_for", "fmx_wideband_rate_taps", "fmx_wideband_survey_stations_rate",
@@ -154,6 +154,19 @@ SCA_BLOCK_AUDIO = 240         # audio samples per block, at fmRate / 8
 SCA_BLOCK_FM = 1920           # fm samples per block
 SCA_LOOKBACK = 703            # fm samples a block reads in front of its first
 SCA_RING = 128                # blocks the library keeps per decoding channel
+
+
+class FmxFeedInfo(C.Structure):
+    _fields_ = [("rate_hz", C.c_int32), ("block_samples", C.c_int32), ("block_frames", C.c_int32), ("lookback_frames", C.c_int32), ("delay_frames", C.c_double),
+                ("ring_blocks", C.c_int32), ("bytes_per_channel", C.c_int32)]
+
+
+FEED_F32, FEED_S16 = 0, 1     # fmx_feed_format
+FEED_OFF, FEED_MIX, FEED_LEFT, FEED_RIGHT = 0, 1, 2, 3
+FEED_BLOCK = 160              # feed samples per block, at 16 kS/s
+FEED_BLOCK_FRAMES = 480       # PCM frames per block
+FEED_LOOKBACK = 143           # PCM frames a block reads in front of its first
+FEED_RING = 128               # blocks the library keeps per feeding channel
 
 
 class FmxMeta(C.Structure):
@@ -384,6 +397,18 @@ def load_library(path=None):
     L.fmx_sca_taps.argtypes = [C.POINTER(FmxScaConfig), i32, i32, vp, i32, C.POINTER(i32)]
     L.fmx_sca_info.restype = C.c_int
     L.fmx_sca_info.argtypes = [i32, C.POINTER(FmxScaInfo)]
+    L.fmx_feed_enable.restype = C.c_int
+    L.fmx_feed_enable.argtypes = [vp, i32, i32]
+    L.fmx_feed_read.restype = C.c_int
+    L.fmx_feed_read.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp]
+    L.fmx_feed_read_device.restype = C.c_int
+    L.fmx_feed_read_device.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]
+    L.fmx_feed_taps.restype = C.c_int
+    L.fmx_feed_taps.argtypes = [vp, i32, C.POINTER(i32)]
+    L.fmx_feed_info.restype = C.c_int
+    L.fmx_feed_info.argtypes = [C.POINTER(FmxFeedInfo)]
+    L.fmx_feed_allocated.restype = C.c_int64
+    L.fmx_feed_allocated.argtypes = [vp]
     L.fmx_mod_hz_per_unit.restype = C.c_int
     L.fmx_mod_hz_per_unit.argtypes = [i32, i32, C.POINTER(C.c_double)]
     L.fmx_rds_bits.restype = C.c_int
@@ -571,6 +596,35 @@ def sca_info(rate_hz=192000):
     if rc != FMX_OK:
         raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
     return {name: getattr(out, name) for name, _ in FmxScaInfo._fields_}
+
+
+def feed_taps():
+    """The monitoring feed's 144 taps at 48 000 frames/s (fmx_feed_taps; host only, needs no device)."""
+    L = load_library()
+    out = np.zeros(144, np.float32)
+    n = C.c_int32()
+    rc = L.fmx_feed_taps(out.ctypes.data, out.size, C.byref(n))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
+    return out[:n.value].copy()
+
+
+def feed_info():
+    """The monitoring feed's numbers (fmx_feed_info; host only): a dict of rate_hz, block_samples, block_frames, lookback_frames, delay_frames, ring_blocks
+    and bytes_per_channel."""
+    L = load_library()
+    out = FmxFeedInfo()
+    rc = L.fmx_feed_info(C.byref(out))
+    if rc != FMX_OK:
+        raise FmxError(rc, L.fmx_last_error().decode("utf-8", "replace"))
+    return {name: getattr(out, name) for name, _ in FmxFeedInfo._fields_}
+
+
+def _device_ptr(x):
+    """an address, or whatever has a data_ptr () (a torch tensor on the device), or None"""
+    if x is None:
+        return None
+    return C.c_void_p(int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x))
 
 
 def rds_meter_figures(records, cal, hz_per_unit):
@@ -820,6 +874,40 @@ class Fmx:
         self._check(self.L.fmx_sca_read(self.h, int(first), int(count), first_block.ctypes.data, audio.ctypes.data, lv.ctypes.data if level else None,
                                         int(capacity), n.ctypes.data))
         return [(int(first_block[q]), audio[q, :n[q]].copy(), (lv[q, :n[q]].copy() if level else None)) for q in range(count)]
+
+    def feed(self, mode=1, channel=-1):
+        """Switch the monitoring feed of a channel (-1: of every channel) from the next call on (fmx_feed_enable): mode 0 off, 1 (L + R) / 2, 2 left,
+        3 right.  16 kS/s mono in blocks of 160 samples; block b belongs to the PCM frames [480 b, 480 b + 480)."""
+        self._check(self.L.fmx_feed_enable(self.h, int(channel), int(mode)))
+
+    def feed_read(self, first=0, count=1, capacity=FEED_RING, fmt="f32", power=True, device=None):
+        """The consecutive blocks of channels first .. first + count - 1 completed since each one's last read, oldest first, in one read-out of the device.
+        device None (fmx_feed_read) -> a list with one (first_block or -1, audio [n, 160] f32 or int16, power [n] f32 or None) per channel.
+        device = (audio, power or None[, hip_stream]) -- addresses, or torch tensors on the device, of [count, capacity x 160] samples of `fmt` and
+        [count, capacity] f32 -- (fmx_feed_read_device): the same gather into those buffers, asynchronous on hip_stream -> a list with one
+        (first_block or -1, n) per channel; block i of channel q is at audio [q, 160 i : 160 i + 160].  A run ends at a gap; the rest comes with the next
+        read.  The library keeps the last 128 blocks per feeding channel."""
+        code = {"f32": FEED_F32, "s16": FEED_S16}.get(fmt, fmt)
+        first_block = np.zeros(count, np.int64)
+        n = np.zeros(count, np.int32)
+        if device is not None:
+            d_audio, d_power, stream = (tuple(device) + (None, None))[:3] if isinstance(device, (tuple, list)) else (device, None, None)
+            self._check(self.L.fmx_feed_read_device(self.h, int(first), int(count), first_block.ctypes.data, _device_ptr(d_audio), int(code), _device_ptr(d_power),
+                                                    int(capacity), n.ctypes.data, _device_ptr(stream)))
+            return [(int(first_block[q]), int(n[q])) for q in range(count)]
+        cap = max(int(capacity), 1)
+        audio = np.zeros((count, cap, FEED_BLOCK), np.int16 if code == FEED_S16 else np.float32)
+        pw = np.zeros((count, cap), np.float32) if power else None
+        self._check(self.L.fmx_feed_read(self.h, int(first), int(count), first_block.ctypes.data, audio.ctypes.data if capacity > 0 else None, int(code),
+                                         pw.ctypes.data if power else None, int(capacity), n.ctypes.data))
+        return [(int(first_block[q]), audio[q, :n[q]].copy(), (pw[q, :n[q]].copy() if power else None)) for q in range(count)]
+
+    def feed_allocated(self):
+        """the bytes of device memory the handle holds for the feed (fmx_feed_allocated; 0: it never fed)"""
+        return int(self.L.fmx_feed_allocated(self.h))
+
+    feed_taps = staticmethod(feed_taps)
+    feed_info = staticmethod(feed_info)
 
     def rds_meter_cal(self, channel=0):
         """The calibration of a channel's RDS meter from the handle's own taps (fmx_rds_meter_cal): a dict of gain, phase0_deg and path_57k."""
@@ -1174,6 +1262,12 @@ class FmProcessor:
     def pollSca(self):
         """The sub-carrier decoder's blocks of this channel since the last poll: (first_block or -1, audio [n, 240] at fmRate / 8, level [n])."""
         return self.fmx.sca_read(self.channel, 1)[0]
+
+    def setFeed(self, mode): self.fmx.feed(mode, self.channel)
+
+    def pollFeed(self, fmt="f32"):
+        """The monitoring feed's blocks of this channel since the last poll: (first_block or -1, audio [n, 160] at 16 kS/s, power [n])."""
+        return self.fmx.feed_read(self.channel, 1, fmt=fmt)[0]
 
     def isPilotLocked(self):
         m = self.fmx.meta(self.channel)

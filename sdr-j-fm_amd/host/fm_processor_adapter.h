@@ -267,6 +267,25 @@ public:
         for (int32_t k = 0; k < n; k++) emit_fn(first + k, audio.data() + (size_t)k * 240, level[(size_t)k]);
         return n;
     }
+    // the monitoring feed (include/fmx.h fmx_feed_*; no counterpart in the reference): setFeed switches this processor's channel's 16 kS/s mono feed with
+    // the next call (0: off, 1: (L + R) / 2, 2: left, 3: right); pollFeed calls `emit_fn(int64_t block, const float *audio, float power)` (160 samples;
+    // block b belongs to the PCM frames [480 b, 480 b + 480)) once per block completed since the last poll, oldest first, up to a gap; pollFeedS16 the same
+    // with `const int16_t *audio`, converted on the device
+    bool setFeed(int32_t mode) { return h && check(fmx_feed_enable(h, 0, mode)); }
+    template <class F> int pollFeed(F emit_fn) {
+        int64_t first = -1; int32_t n = 0;
+        std::vector<float> audio((size_t)128 * 160), power(128);
+        if (!h || fmx_feed_read(h, 0, 1, &first, audio.data(), FMX_FEED_F32, power.data(), 128, &n) != FMX_OK) return 0;
+        for (int32_t k = 0; k < n; k++) emit_fn(first + k, audio.data() + (size_t)k * 160, power[(size_t)k]);
+        return n;
+    }
+    template <class F> int pollFeedS16(F emit_fn) {
+        int64_t first = -1; int32_t n = 0;
+        std::vector<int16_t> audio((size_t)128 * 160); std::vector<float> power(128);
+        if (!h || fmx_feed_read(h, 0, 1, &first, audio.data(), FMX_FEED_S16, power.data(), 128, &n) != FMX_OK) return 0;
+        for (int32_t k = 0; k < n; k++) emit_fn(first + k, audio.data() + (size_t)k * 160, power[(size_t)k]);
+        return n;
+    }
     // the RDS picture of this processor's channel(s) in one read-out of the device (fmx_rds_decode_all: the block synchroniser has run on the GPU,
     // the group decoder runs here): what the rds classes' signals carried, infos[k] for channel first + k
     bool poll_rds(fmx_rds_info *infos, int32_t first = 0, int32_t count = 1) { return h && check(fmx_rds_decode_all(h, first, count, infos)); }
