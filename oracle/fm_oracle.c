@@ -1715,6 +1715,19 @@ void fmo_demod_run(int32_t rate, int decoder, const float *z, long n, float *out
     if (carrier) *carrier = d->am_carr_ampl;
     fmo_demod_free(d);
 }
+/* the next n samples through a long-lived demodulator (a decoder change between two runs is the reference's combo box); per sample, where asked
+ * for, get_DcComponent () and the carrier level behind it */
+void fmo_demod_feed(fmo_demod *d, const float *z, long n, float *out, float *dc, float *carrier) {
+    for (long i = 0; i < n; i++) {
+        out[i] = fmo_demod_demodulate(d, C(z[2 * i], z[2 * i + 1]));
+        if (dc) dc[i] = d->fm_afc;
+        if (carrier) carrier[i] = d->am_carr_ampl;
+    }
+}
+/* TEST HOOK, off everywhere else: the demodulator's own SinCos table (pllC's NCO) replaced by `table` [rateIn] (cos, sin) */
+void fmo_demod_test_set_sincos(fmo_demod *d, const fmo_c32 *table) {
+    memcpy(d->tab->tab, table, sizeof(c32) * (size_t)d->rateIn);
+}
 void fmo_pilot_run(int32_t rate, float omega, float gain, const float *pilot, long n,
                    float *phase, uint8_t *locked, float *strength) {
     fmo_sincos *tab = fmo_sincos_new(rate);

@@ -103,6 +103,12 @@ float fmo_demod_demodulate(fmo_demod *, fmo_c32 z);
 float fmo_demod_dc(const fmo_demod *);
 float fmo_demod_carrier(const fmo_demod *);
 float fmo_demod_kfm(const fmo_demod *);
+/* the next n samples through a long-lived demodulator; per sample (where not NULL) fm_afc and am_carr_ampl behind it */
+void  fmo_demod_feed(fmo_demod *, const float *z, long n, float *out, float *dc, float *carrier);
+/* TEST HOOK (never called by a parity comparison: the demodulator is the reference's, bit for bit).  pllC takes its NCO from the SinCos table; libfmx takes
+ * it from the GPU's sine unit, within 1.2e-7 of the entry (include/fmx.h).  This replaces the demodulator's own table [rateIn] (cos, sin), so that
+ * tests/prepass_model.py can measure what such a table does to the reference's own loop. */
+void  fmo_demod_test_set_sincos(fmo_demod *, const fmo_c32 *table);
 
 /* ---------- pilot PLL (pilot-recover.cpp:28-83) ---------- */
 typedef struct fmo_pilot fmo_pilot;

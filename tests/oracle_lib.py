@@ -123,6 +123,8 @@ def oracle():
         "fmo_demod_dc": (f32, [vp]),
         "fmo_demod_carrier": (f32, [vp]),
         "fmo_demod_kfm": (f32, [vp]),
+        "fmo_demod_feed": (None, [vp, c_float_p, lng, c_float_p, c_float_p, c_float_p]),
+        "fmo_demod_test_set_sincos": (None, [vp, c_float_p]),
         "fmo_pilot_new": (vp, [i32, f32, f32, vp]),
         "fmo_pilot_free": (None, [vp]),
         "fmo_pilot_phase": (f32, [vp, f32]),

@@ -61,13 +61,18 @@ TAPS = (("z", M.TAP_FM_IQ), ("demod", M.TAP_DEMOD), ("phase", M.TAP_PILOT_PHASE)
 
 class Run:
     """The calls of one case: the five taps of every probed channel after every call, where every call begins, the PSS shift of every
-    metaData snapshot; twins (groups of channels with equal settings on one stream): PCM and taps bit-identical after every call."""
+    metaData snapshot; twins (groups of channels with equal settings on one stream): PCM and taps bit-identical after every call.
+    calls, taps: another call list (input samples per call) and another choice of taps than this module's (tests/test_gpu_prepass_per_sample.py);
+    before_call (k), after_call (k, fm samples of the call): hooks, for a setter at a call boundary and for a per-call read-out."""
 
-    def __init__(self, f, iq, probe, twins=()):
+    def __init__(self, f, iq, probe, twins=(), calls=None, taps=None, before_call=None, after_call=None):
+        CALLS, TAPS = (globals()["CALLS"] if calls is None else calls), (globals()["TAPS"] if taps is None else taps)
         self.t = {c: {k: [] for k, _ in TAPS} for c in probe}
         self.starts, self.shift = [], {c: [] for c in probe}
         pos = j = 0
         for k, s in enumerate(CALLS):
+            if before_call is not None:
+                before_call(k)
             pcm = f.process_host(iq[:, pos:pos + s])
             pos += s
             nj = f.last_fm_samples()
@@ -82,6 +87,8 @@ class Run:
                     for other in group:
                         for name, tap in TAPS:
                             assert other == c or np.array_equal(f.tap(tap, nj, other), self.t[c][name][-1]), ("tap %s of twins" % name, k, c, other)
+            if after_call is not None:
+                after_call(k, nj)
             j += nj
         self.fm_samples = j
         assert pos == sum(CALLS) and j == pos // 12
