@@ -201,8 +201,11 @@ typedef enum {
     FMX_TAP_FM_IQ = 0,         /* complex @fmRate after fmBand_2 (IF_FILTERED scope, :601-604)   */
     FMX_TAP_DEMOD = 1,         /* float   @fmRate after demodulate (DEMODULATOR scope, :605-607) */
     FMX_TAP_LR_RAW = 2,        /* complex @fmRate (sum,diff) (AF_SUM/AF_DIFF scopes, :608-613)   */
-    FMX_TAP_PRE_RESAMPLER = 3, /* complex @fmRate after de-emphasis (:594-595), before gain; this
-                                  build applies the audio low-pass AFTER this point */
+    FMX_TAP_PRE_RESAMPLER = 3, /* complex @fmRate after de-emphasis (:594-595), before gain.  On a handle
+                                  that runs the folded filters the audio low-pass is applied AFTER this
+                                  point (stage C); on a block-machine handle (FMX_P_FILTER_RESTARTS, a
+                                  promoted batch) the tap holds the reference's own value, behind
+                                  fmAudioFilter AND the de-emphasis (:589-595) */
     FMX_TAP_RDS_IQ = 4,        /* complex @24 kS/s after rdsDecimator (RDS_INPUT scope, :566-569)        */
     FMX_TAP_PILOT_PHASE = 5,   /* float   @fmRate currentPilotPhase (:695; the value the RDS mixer's phase buffer takes, :747) */
 } fmx_tap_id;

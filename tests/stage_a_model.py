@@ -190,12 +190,21 @@ def balance(c, att):
 
 
 # ------------------------------------------------------------------------------------------------ the filters, unfolded
-def filters(v, D, direct=False):
+def filters(v, D, direct=False, filtered=None):
     """Input filter (a linear convolution, 65285 samples late, zeros in front), fmBand_1, fmBand_2: an output when the counter reaches
     D, y[m] = sum_l k[l] v[D m + D - 1 - l] (fir-filters.cpp:397-424).  direct: the convolutions as plain float64 sums, whose rounding is relative to an output's own terms -- a
-    transform's is relative to the stream's peak and would drown a quiet stretch a million times below it (the level-step case)."""
+    transform's is relative to the stream's peak and would drown a quiet stretch a million times below it (the level-step case).
+    filtered: a hook for tests/ola_model.py -- the filtered stream [n] itself, or a function of v that makes it, in the place of the LTI
+    input filter (the reference's block machine across restarts); the decimators then run over it as it is."""
     n = v.shape[0]
     conv = np.convolve if direct else fm.fftconv
+    if filtered is not None:
+        w = np.asarray(filtered(v) if callable(filtered) else filtered, np.complex128)
+        assert w.shape == (n,)
+        if D.decim == 1:
+            return w
+        y = conv(w, D.k1)[D.d1 * np.arange(n // D.d1, dtype=np.int64) + D.d1 - 1]
+        return conv(y, D.k2)[D.d2 * np.arange(y.shape[0] // D.d2, dtype=np.int64) + D.d2 - 1]
     w = v if D.h_in is None else fm.delayed(conv(v, D.h_in), IN_DELAY, n)
     if D.decim == 1:
         return w
@@ -206,19 +215,20 @@ def filters(v, D, direct=False):
     return z
 
 
-def stage_a(D, x, calls=None, lo=0, att=(1.0, 1.0), dc_remove=1, form="front", behind=None, dc_columns_late=0, direct=False):
+def stage_a(D, x, calls=None, lo=0, att=(1.0, 1.0), dc_remove=1, form="front", behind=None, dc_columns_late=0, direct=False, filtered=None):
     """The fm-rate IQ [n / decim] complex128 of one channel over the whole stream x ([n, 2] f32 or complex).  lo and dc_remove: one value,
     or one per call (calls = the calls' lengths in input samples).  form: "front", "behind", or "mixed" with `behind` a boolean per fm
     sample (the outputs a kernel of the second form wrote).  dc_columns_late: a seed for the detector, the second form's RF DC value taken that many
-    columns late."""
+    columns late.  filtered: filters ()'s hook, form "front" only."""
     x = as_complex(x)
     n = x.shape[0]
+    assert filtered is None or form == "front"
     lo_runs, dc_runs = per_call(lo, calls), per_call(dc_remove, calls)
     LO, _ = oscillator(n, D.rate, lo_runs)
     R = rf_dc(x, D.rate, dc_runs)
     out = {}
     if form in ("front", "mixed"):
-        out["front"] = filters(balance(x - clamp(R[1:]), att) * LO, D, direct)
+        out["front"] = filters(balance(x - clamp(R[1:]), att) * LO, D, direct, filtered)
     if form in ("behind", "mixed"):
         F = D.front_set()
         z = filters(balance(x, att) * LO, D, direct)
