@@ -630,156 +630,97 @@ int ensure_scan(fmx_handle h) {
     return FMX_OK;
 }
 
-// the modulation meter's buffers (fmx_meter.hip), allocated by the first call in which a channel's meter is on
-int ensure_meter(fmx_handle h) {
-    if (h->meter_alloc) return FMX_OK;
+// A record meter's device side (fmx_taps.h), allocated by the first call in which a channel's meter is on: per channel `state_n` floats of the window in
+// progress, `ring_n` records and a job
+template <class R, class J> int ensure_record_tap(fmx_handle h, RecordTap &T, size_t state_n, size_t ring_n, float *&state, R *&ring, J *&jobs) {
+    if (T.alloc) return FMX_OK;
     const size_t C = (size_t)h->channels;
     HIPCHK(hipDeviceSynchronize());
-    FMXCHK(h->mem.alloc(h->d_meter_state, C * meter::QUANT * meter::LANES, true));
-    FMXCHK(h->mem.alloc(h->d_meter_ring, C * meter::RING, true));
-    FMXCHK(h->mem.alloc(h->d_meter_jobs, C));
-    h->call_meter.assign(C, 0); h->meter_on_from.assign(C, -1); h->meter_produced.assign(C, 0); h->rd.mod.assign(C, 0);
-    h->meter_alloc = true;
+    FMXCHK(h->mem.alloc(state, C * state_n, true));
+    FMXCHK(h->mem.alloc(ring, C * ring_n, true));
+    FMXCHK(h->mem.alloc(jobs, C));
+    T.start(C);
+    return FMX_OK;
+}
+// ... by flush_mailbox (under mtx), where `may` allows it, and the switches of the piece being made
+template <class R, class J> int flush_record_tap(fmx_handle h, RecordTap &T, bool may, size_t state_n, size_t ring_n, float *&state, R *&ring, J *&jobs) {
+    if (may && !T.alloc && T.any_on()) FMXCHK(ensure_record_tap(h, T, state_n, ring_n, state, ring, jobs));
+    T.take_switches();
     return FMX_OK;
 }
 
-// the programme audio meter's buffers (fmx_loud.hip), allocated by the first call in which a channel's audio meter is on
-int ensure_audio_meter(fmx_handle h) {
-    if (h->loud_alloc) return FMX_OK;
-    const size_t C = (size_t)h->channels;
-    HIPCHK(hipDeviceSynchronize());
-    FMXCHK(h->mem.alloc(h->d_loud_state, C * loud::STATE, true));
-    FMXCHK(h->mem.alloc(h->d_loud_ring, C * loud::RING, true));
-    FMXCHK(h->mem.alloc(h->d_loud_jobs, C));
-    h->call_loud.assign(C, 0); h->loud_on_from.assign(C, -1); h->loud_produced.assign(C, 0); h->rd.audio.assign(C, 0);
-    h->loud_alloc = true;
-    return FMX_OK;
+int ensure_spec_tables(fmx_handle h) {      // (the window and the twiddles, the two spectrum meters': whichever comes first)
+    if (h->d_spec_win) return FMX_OK;
+    std::vector<float> win(spec::N); std::vector<float2> W(spec::N);
+    survey::make_window(win.data()); survey::make_twiddles(W.data());
+    FMXCHK(h->mem.upload(h->d_spec_win, win));
+    return h->mem.upload(h->d_spec_W, W);
 }
-
-// the reception meter's buffers (fmx_rx.hip), allocated by the first call in which a channel's reception meter is on
-int ensure_rx_meter(fmx_handle h) {
-    if (h->rx_alloc) return FMX_OK;
-    const size_t C = (size_t)h->channels;
-    HIPCHK(hipDeviceSynchronize());
-    FMXCHK(h->mem.alloc(h->d_rx_state, C * rx::QUANT * meter::LANES, true));
-    FMXCHK(h->mem.alloc(h->d_rx_ring, C * rx::RING, true));
-    FMXCHK(h->mem.alloc(h->d_rx_jobs, C));
-    h->call_rx.assign(C, 0); h->rx_on_from.assign(C, -1); h->rx_produced.assign(C, 0); h->rd.rx.assign(C, 0);
-    h->rx_alloc = true;
-    return FMX_OK;
-}
-
-// the RDS meter's buffers (fmx_rdsm.hip), allocated by the first call in which a channel's RDS meter is on and a decoder runs
-int ensure_rds_meter(fmx_handle h) {
-    if (h->rdsm_alloc) return FMX_OK;
-    const size_t C = (size_t)h->channels;
-    HIPCHK(hipDeviceSynchronize());
-    FMXCHK(h->mem.alloc(h->d_rdsm_state, C * rdsm::QUANT * rdsm::LANES, true));
-    FMXCHK(h->mem.alloc(h->d_rdsm_ring, C * rdsm::RING, true));
-    FMXCHK(h->mem.alloc(h->d_rdsm_jobs, C));
-    h->call_rdsm.assign(C, 0); h->rdsm_on_from.assign(C, -1); h->rdsm_produced.assign(C, 0); h->rd.rdsm.assign(C, 0);
-    h->rdsm_alloc = true;
-    return FMX_OK;
-}
-
 // The spectrum meter's memory (fmx_spec.hip), under mtx: a slot for every stream whose meter is on and has none yet.  Memory is per slot -- 32 KB of carry,
-// 32 KB of sum and maximum, 128 KB of ring -- and grows to the slots in use: the arrays are allocated anew and the old slots copied.  The scratch of block
+// 32 KB of sum and maximum, 128 KB of ring -- and grows to the slots in use (grow_slots).  The scratch of block
 // powers holds what a call of max_block samples completes for every slot, or spec::SCRATCH_BYTES where that is less (stage_spectrum cuts the piece then).
 int ensure_spectrum(fmx_handle h) {
-    const size_t NS = (size_t)h->streams;
-    if (h->spec_slot.empty()) {
-        h->spec_slot.assign(NS, -1); h->spec_on_from.assign(NS, -1); h->spec_tag.assign(NS * spec::RING, -1); h->rd.spec.assign(NS, 0); h->call_spec.assign(NS, 0);
-    }
-    int32_t need = h->spec_slots;
-    for (size_t s = 0; s < NS; s++) if (h->user_spec[s] && h->spec_slot[s] < 0) need++;
-    if (need > h->spec_cap) {
+    SlotTap &T = h->spec_tap;
+    T.start((size_t)h->streams, spec::RING);
+    const size_t old = (size_t)T.slots, need = old + (size_t)T.slots_needed();
+    if ((int32_t)need > T.cap) {
         HIPCHK(hipDeviceSynchronize());
-        if (!h->d_spec_win) {
-            std::vector<float> win(spec::N); std::vector<float2> W(spec::N);
-            survey::make_window(win.data()); survey::make_twiddles(W.data());
-            FMXCHK(h->mem.upload(h->d_spec_win, win)); FMXCHK(h->mem.upload(h->d_spec_W, W));
-        }
-        if (!h->ev_spec) HIPCHK(hipEventCreateWithFlags(&h->ev_spec, hipEventDisableTiming));      // (the tables may be there already: ensure_mpx)
-        float2 *carry = nullptr; float *acc = nullptr, *ring = nullptr;
-        FMXCHK(h->mem.alloc(carry, (size_t)need * spec::N, true));
-        FMXCHK(h->mem.alloc(acc, (size_t)need * 2 * spec::N, true));
-        FMXCHK(h->mem.alloc(ring, (size_t)need * spec::RING * 2 * spec::N, true));
-        if (h->spec_slots > 0) {
-            const size_t k = (size_t)h->spec_slots;
-            HIPCHK(hipMemcpy(carry, h->d_spec_carry, sizeof(float2) * k * spec::N, hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(acc, h->d_spec_acc, sizeof(float) * k * 2 * spec::N, hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(ring, h->d_spec_ring, sizeof(float) * k * spec::RING * 2 * spec::N, hipMemcpyDeviceToDevice));
-            HIPCHK(hipDeviceSynchronize());
-        }
-        h->mem.release(h->d_spec_carry); h->mem.release(h->d_spec_acc); h->mem.release(h->d_spec_ring); h->mem.release(h->d_spec_jobs);
-        h->d_spec_carry = carry; h->d_spec_acc = acc; h->d_spec_ring = ring;
-        FMXCHK(h->mem.alloc(h->d_spec_jobs, (size_t)need));
-        const int64_t want = spec::scratch_blocks_for(need, (h->cfg.max_block + spec::N - 1) / spec::N + 1);
+        FMXCHK(ensure_spec_tables(h));
+        if (!h->ev_spec) HIPCHK(hipEventCreateWithFlags(&h->ev_spec, hipEventDisableTiming));
+        FMXCHK(grow_slots(h->mem, h->d_spec_carry, old, need, spec::N));
+        FMXCHK(grow_slots(h->mem, h->d_spec_acc, old, need, 2 * spec::N));
+        FMXCHK(grow_slots(h->mem, h->d_spec_ring, old, need, spec::RING * 2 * spec::N));
+        if (old > 0) HIPCHK(hipDeviceSynchronize());
+        h->mem.release(h->d_spec_jobs);
+        FMXCHK(h->mem.alloc(h->d_spec_jobs, need));
+        const int64_t want = spec::scratch_blocks_for((int32_t)need, (h->cfg.max_block + spec::N - 1) / spec::N + 1);
         if (want > h->spec_scratch) {
             h->mem.release(h->d_spec_power);
             FMXCHK(h->mem.alloc(h->d_spec_power, (size_t)want * spec::N));
             h->spec_scratch = want;
         }
-        h->spec_cap = need;
+        T.cap = (int32_t)need;
     }
-    for (size_t s = 0; s < NS; s++) if (h->user_spec[s] && h->spec_slot[s] < 0) h->spec_slot[s] = h->spec_slots++;
+    T.assign_slots();
     return FMX_OK;
 }
 
 // The multiplex spectrum meter's memory (fmx_mpx.hip), under mtx, grown as ensure_spectrum grows the spectrum meter's: a slot for every channel whose meter
-// is on and has none yet -- 16 KB of carry, 16 KB of sum and maximum, 64 KB of ring --, the arrays allocated anew and the old slots copied.  The window and
-// the twiddles are the spectrum meter's, whichever of the two comes first.  The scratch of block powers holds what a piece of work_nj fm samples completes
-// for every slot, or spec::SCRATCH_BYTES where that is less (stage_mpx cuts the piece then).
+// is on and has none yet -- 16 KB of carry, 16 KB of sum and maximum, 64 KB of ring.  The scratch of block powers holds what a piece of work_nj fm samples
+// completes for every slot, or spec::SCRATCH_BYTES where that is less (stage_mpx cuts the piece then).
 int ensure_mpx(fmx_handle h) {
-    const size_t NC = (size_t)h->channels;
-    if (h->mpx_slot.empty()) {
-        h->mpx_slot.assign(NC, -1); h->mpx_on_from.assign(NC, -1); h->mpx_tag.assign(NC * mpx::RING, -1); h->rd.mpx.assign(NC, 0); h->call_mpx.assign(NC, 0);
-    }
-    int32_t need = h->mpx_slots;
-    for (size_t c = 0; c < NC; c++) if (h->user_mpx[c] && h->mpx_slot[c] < 0) need++;
-    if (need > h->mpx_cap) {
+    SlotTap &T = h->mpx_tap;
+    T.start((size_t)h->channels, mpx::RING);
+    const size_t old = (size_t)T.slots, need = old + (size_t)T.slots_needed();
+    if ((int32_t)need > T.cap) {
         HIPCHK(hipDeviceSynchronize());
-        if (!h->d_spec_win) {
-            std::vector<float> win(spec::N); std::vector<float2> W(spec::N);
-            survey::make_window(win.data()); survey::make_twiddles(W.data());
-            FMXCHK(h->mem.upload(h->d_spec_win, win)); FMXCHK(h->mem.upload(h->d_spec_W, W));
-        }
+        FMXCHK(ensure_spec_tables(h));
         if (!h->ev_mpx) HIPCHK(hipEventCreateWithFlags(&h->ev_mpx, hipEventDisableTiming));
-        float *carry = nullptr, *acc = nullptr, *ring = nullptr;
-        FMXCHK(h->mem.alloc(carry, (size_t)need * mpx::N, true));
-        FMXCHK(h->mem.alloc(acc, (size_t)need * 2 * mpx::BINS, true));
-        FMXCHK(h->mem.alloc(ring, (size_t)need * mpx::RING * 2 * mpx::BINS, true));
-        if (h->mpx_slots > 0) {
-            const size_t k = (size_t)h->mpx_slots;
-            HIPCHK(hipMemcpy(carry, h->d_mpx_carry, sizeof(float) * k * mpx::N, hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(acc, h->d_mpx_acc, sizeof(float) * k * 2 * mpx::BINS, hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(ring, h->d_mpx_ring, sizeof(float) * k * mpx::RING * 2 * mpx::BINS, hipMemcpyDeviceToDevice));
-            HIPCHK(hipDeviceSynchronize());
-        }
-        h->mem.release(h->d_mpx_carry); h->mem.release(h->d_mpx_acc); h->mem.release(h->d_mpx_ring); h->mem.release(h->d_mpx_jobs);
-        h->d_mpx_carry = carry; h->d_mpx_acc = acc; h->d_mpx_ring = ring;
-        FMXCHK(h->mem.alloc(h->d_mpx_jobs, (size_t)need));
-        const int64_t want = mpx::scratch_blocks_for(need, (h->work_nj + mpx::N - 1) / mpx::N + 1);
+        FMXCHK(grow_slots(h->mem, h->d_mpx_carry, old, need, mpx::N));
+        FMXCHK(grow_slots(h->mem, h->d_mpx_acc, old, need, 2 * mpx::BINS));
+        FMXCHK(grow_slots(h->mem, h->d_mpx_ring, old, need, mpx::RING * 2 * mpx::BINS));
+        if (old > 0) HIPCHK(hipDeviceSynchronize());
+        h->mem.release(h->d_mpx_jobs);
+        FMXCHK(h->mem.alloc(h->d_mpx_jobs, need));
+        const int64_t want = mpx::scratch_blocks_for((int32_t)need, (h->work_nj + mpx::N - 1) / mpx::N + 1);
         if (want > h->mpx_scratch) {
             h->mem.release(h->d_mpx_power);
             FMXCHK(h->mem.alloc(h->d_mpx_power, (size_t)want * mpx::BINS));
             h->mpx_scratch = want;
         }
-        h->mpx_cap = need;
+        T.cap = (int32_t)need;
     }
-    for (size_t c = 0; c < NC; c++) if (h->user_mpx[c] && h->mpx_slot[c] < 0) h->mpx_slot[c] = h->mpx_slots++;
+    T.assign_slots();
     return FMX_OK;
 }
 
-// The sub-carrier decoder's memory (fmx_sca.hip), under mtx, grown as ensure_mpx grows the multiplex spectrum meter's: a slot for every channel that decodes
-// and has none yet -- sca::BYTES_PER_CHANNEL: the ring's audio and levels, the carry, the mixed taps --, the arrays allocated anew and the old slots copied.
-// The audio filter is one per handle; a slot's mixed taps are made by stage_sca when its channel is switched on.
+// The sub-carrier decoder's memory (fmx_sca.hip), under mtx, grown likewise: a slot for every channel that decodes and has none yet --
+// sca::BYTES_PER_CHANNEL: the ring's audio and levels, the carry, the mixed taps.  The audio filter is one per handle; a slot's mixed taps are made by
+// stage_sca when its channel is switched on.
 int ensure_sca(fmx_handle h) {
-    const size_t NC = (size_t)h->channels;
-    if (h->sca_slot.empty()) {
-        h->sca_slot.assign(NC, -1); h->sca_slot_centre.assign(NC, 0); h->sca_on_from.assign(NC, -1); h->sca_tag.assign(NC * sca::RING, -1);
-        h->rd.sca.assign(NC, 0); h->call_sca.assign(NC, 0);
-    }
+    SlotTap &T = h->sca_tap;
+    if (!T.started()) h->sca_slot_centre.assign((size_t)h->channels, 0);
+    T.start((size_t)h->channels, sca::RING);
     if (h->sca_taps_stale) {
         HIPCHK(hipDeviceSynchronize());
         h->sca_g = sca::design_band(h->sca_cfg, h->cfg.fmRate);
@@ -788,65 +729,49 @@ int ensure_sca(fmx_handle h) {
         std::fill(h->sca_slot_centre.begin(), h->sca_slot_centre.end(), 0);      // (every slot's mixed taps are made anew)
         h->sca_taps_stale = false;
     }
-    int32_t need = h->sca_slots;
-    for (size_t c = 0; c < NC; c++) if (h->user_sca[c] && h->sca_slot[c] < 0) need++;
-    if (need > h->sca_cap) {
+    const size_t old = (size_t)T.slots, need = old + (size_t)T.slots_needed();
+    if ((int32_t)need > T.cap) {
         HIPCHK(hipDeviceSynchronize());
         if (!h->ev_sca) HIPCHK(hipEventCreateWithFlags(&h->ev_sca, hipEventDisableTiming));
-        float *carry = nullptr, *audio = nullptr, *level = nullptr; float2 *taps = nullptr;
-        FMXCHK(h->mem.alloc(carry, (size_t)need * sca::CARRY_STRIDE, true));
-        FMXCHK(h->mem.alloc(audio, (size_t)need * sca::RING * sca::BLOCK_AUDIO, true));
-        FMXCHK(h->mem.alloc(level, (size_t)need * sca::RING, true));
-        FMXCHK(h->mem.alloc(taps, (size_t)need * (sca::NG + 1), true));
-        if (h->sca_slots > 0) {
-            const size_t k = (size_t)h->sca_slots;
-            HIPCHK(hipMemcpy(carry, h->d_sca_carry, sizeof(float) * k * sca::CARRY_STRIDE, hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(audio, h->d_sca_audio, sizeof(float) * k * sca::RING * sca::BLOCK_AUDIO, hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(level, h->d_sca_level, sizeof(float) * k * sca::RING, hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(taps, h->d_sca_taps, sizeof(float2) * k * (sca::NG + 1), hipMemcpyDeviceToDevice));
-            HIPCHK(hipDeviceSynchronize());
-        }
-        h->mem.release(h->d_sca_carry); h->mem.release(h->d_sca_audio); h->mem.release(h->d_sca_level); h->mem.release(h->d_sca_taps); h->mem.release(h->d_sca_jobs);
-        h->d_sca_carry = carry; h->d_sca_audio = audio; h->d_sca_level = level; h->d_sca_taps = taps;
-        FMXCHK(h->mem.alloc(h->d_sca_jobs, (size_t)need));
-        h->sca_cap = need;
+        FMXCHK(grow_slots(h->mem, h->d_sca_carry, old, need, sca::CARRY_STRIDE));
+        FMXCHK(grow_slots(h->mem, h->d_sca_audio, old, need, sca::RING * sca::BLOCK_AUDIO));
+        FMXCHK(grow_slots(h->mem, h->d_sca_level, old, need, sca::RING));
+        FMXCHK(grow_slots(h->mem, h->d_sca_taps, old, need, sca::NG + 1));
+        if (old > 0) HIPCHK(hipDeviceSynchronize());
+        h->mem.release(h->d_sca_jobs);
+        FMXCHK(h->mem.alloc(h->d_sca_jobs, need));
+        T.cap = (int32_t)need;
     }
-    for (size_t c = 0; c < NC; c++) if (h->user_sca[c] && h->sca_slot[c] < 0) h->sca_slot[c] = h->sca_slots++;
+    T.assign_slots();
     return FMX_OK;
 }
 
-// The monitoring feed's memory (fmx_feed.hip), under mtx, grown as ensure_sca grows the sub-carrier decoder's: a slot for every channel that feeds and has
-// none yet -- feed::BYTES_PER_CHANNEL: the ring's audio and powers, the carry --, the arrays allocated anew and the old slots copied.  The taps are one
-// array per handle, uploaded with the first slot.
+// The monitoring feed's memory (fmx_feed.hip), under mtx, grown likewise: a slot for every channel that feeds and has none yet -- feed::BYTES_PER_CHANNEL:
+// the ring's audio and powers, the carry.  The taps are one array per handle, uploaded with the first slot.
 int ensure_feed(fmx_handle h) {
-    const size_t NC = (size_t)h->channels;
-    if (h->feed_slot.empty()) {
-        h->feed_slot.assign(NC, -1); h->feed_mode.assign(NC, 0); h->feed_on_from.assign(NC, -1); h->feed_tag.assign(NC * feed::RING, -1);
-        h->rd.feed.assign(NC, 0); h->call_feed.assign(NC, 0);
-    }
-    int32_t need = h->feed_slots;
-    for (size_t c = 0; c < NC; c++) if (h->user_feed[c] && h->feed_slot[c] < 0) need++;
-    if (need > h->feed_cap) {
+    SlotTap &T = h->feed_tap;
+    if (!T.started()) h->feed_mode.assign((size_t)h->channels, 0);
+    T.start((size_t)h->channels, feed::RING);
+    const size_t old = (size_t)T.slots, need = old + (size_t)T.slots_needed();
+    if ((int32_t)need > T.cap) {
         HIPCHK(hipDeviceSynchronize());
         if (!h->ev_feed) HIPCHK(hipEventCreateWithFlags(&h->ev_feed, hipEventDisableTiming));
         if (!h->d_feed_h) FMXCHK(h->mem.upload(h->d_feed_h, feed::design()));
-        float *carry = nullptr, *audio = nullptr, *power = nullptr;
-        FMXCHK(h->mem.alloc(carry, (size_t)need * feed::CARRY_STRIDE, true));
-        FMXCHK(h->mem.alloc(audio, (size_t)need * feed::RING * feed::BLOCK, true));
-        FMXCHK(h->mem.alloc(power, (size_t)need * feed::RING, true));
-        if (h->feed_slots > 0) {
-            const size_t k = (size_t)h->feed_slots;
-            HIPCHK(hipMemcpy(carry, h->d_feed_carry, sizeof(float) * k * feed::CARRY_STRIDE, hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(audio, h->d_feed_audio, sizeof(float) * k * feed::RING * feed::BLOCK, hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(power, h->d_feed_power, sizeof(float) * k * feed::RING, hipMemcpyDeviceToDevice));
-            HIPCHK(hipDeviceSynchronize());
-        }
-        h->mem.release(h->d_feed_carry); h->mem.release(h->d_feed_audio); h->mem.release(h->d_feed_power); h->mem.release(h->d_feed_jobs);
-        h->d_feed_carry = carry; h->d_feed_audio = audio; h->d_feed_power = power;
-        FMXCHK(h->mem.alloc(h->d_feed_jobs, (size_t)need));
-        h->feed_cap = need;
+        FMXCHK(grow_slots(h->mem, h->d_feed_carry, old, need, feed::CARRY_STRIDE));
+        FMXCHK(grow_slots(h->mem, h->d_feed_audio, old, need, feed::RING * feed::BLOCK));
+        FMXCHK(grow_slots(h->mem, h->d_feed_power, old, need, feed::RING));
+        if (old > 0) HIPCHK(hipDeviceSynchronize());
+        h->mem.release(h->d_feed_jobs);
+        FMXCHK(h->mem.alloc(h->d_feed_jobs, need));
+        T.cap = (int32_t)need;
     }
-    for (size_t c = 0; c < NC; c++) if (h->user_feed[c] && h->feed_slot[c] < 0) h->feed_slot[c] = h->feed_slots++;
+    T.assign_slots();
+    return FMX_OK;
+}
+// ... by flush_mailbox (under mtx) while a unit is on, and the values of the piece being made.  `live`: the tap's stage runs while SlotTap::live
+template <class Ensure> int flush_slot_tap(fmx_handle h, SlotTap &T, Ensure ensure, bool live) {
+    if (T.any_on()) { FMXCHK(ensure(h)); if (live) T.live = true; }
+    T.take_switches();
     return FMX_OK;
 }
 
@@ -864,7 +789,7 @@ CallNeeds summarize(fmx_handle h) {
     for (size_t c = 0; c < h->params.size(); c++) {
         const ChanParams &p = h->params[c];
         const FrontSet &fs = h->h_front_sets[(size_t)p.front_set];
-        needs_add(nd, ChanNeeds{p.decoder, p.squelch_mode, p.rds_mode, p.lo_freq, p.att_l, p.att_r, fs.nd, fs.dc_k, (h->user[c].meter || (!h->user_mpx.empty() && h->user_mpx[c]) || (!h->user_sca.empty() && h->user_sca[c])) ? 1 : 0});
+        needs_add(nd, ChanNeeds{p.decoder, p.squelch_mode, p.rds_mode, p.lo_freq, p.att_l, p.att_r, fs.nd, fs.dc_k, (h->mod_tap.user[c] || h->mpx_tap.user[c] || h->sca_tap.user[c]) ? 1 : 0});
     }
     return nd;
 }
@@ -897,61 +822,33 @@ int flush_mailbox(fmx_handle h) {
     if (!h->call_scan.empty()) { const int rc = ensure_scan(h); if (rc) return rc; }
     // (any_meter says that the rows are needed: the modulation meter or the multiplex spectrum meter is on.  The modulation meter's own memory is for a handle
     // that switches it on)
-    if (nd.any_meter && !h->meter_alloc && std::any_of(h->user.begin(), h->user.end(), [](const ChanUser &u) { return u.meter; })) { const int rc = ensure_meter(h); if (rc) return rc; }
-    if (h->meter_alloc) for (int c = 0; c < h->channels; c++) h->call_meter[(size_t)c] = h->user[(size_t)c].meter ? 1 : 0;
+    FMXCHK(flush_record_tap(h, h->mod_tap, nd.any_meter, meter::QUANT * meter::LANES, meter::RING, h->d_meter_state, h->d_meter_ring, h->d_meter_jobs));
     // (the audio meter reads the call's PCM behind everything that writes it and asks nothing of the call's plan: it is no part of CallNeeds)
-    if (!h->loud_alloc && std::any_of(h->user.begin(), h->user.end(), [](const ChanUser &u) { return u.loud; })) { const int rc = ensure_audio_meter(h); if (rc) return rc; }
-    if (h->loud_alloc) for (int c = 0; c < h->channels; c++) h->call_loud[(size_t)c] = h->user[(size_t)c].loud ? 1 : 0;
+    FMXCHK(flush_record_tap(h, h->audio_tap, true, loud::STATE, loud::RING, h->d_loud_state, h->d_loud_ring, h->d_loud_jobs));
     // (the reception meter reads stage A's ring, which every handle keeps in every mode: no part of CallNeeds either)
-    if (!h->rx_alloc && std::any_of(h->user.begin(), h->user.end(), [](const ChanUser &u) { return u.rx; })) { const int rc = ensure_rx_meter(h); if (rc) return rc; }
-    if (h->rx_alloc) for (int c = 0; c < h->channels; c++) h->call_rx[(size_t)c] = h->user[(size_t)c].rx ? 1 : 0;
+    FMXCHK(flush_record_tap(h, h->rx_tap, true, rx::QUANT * meter::LANES, rx::RING, h->d_rx_state, h->d_rx_ring, h->d_rx_jobs));
     // (a channel's RDS path runs while its decoder is on and stands still otherwise -- block filters, phase delay line, decimator and slicer
     // keep what they hold, as the reference's processor's do: nothing restarts when a decoder is switched; run_piece counts per channel)
     if (nd.any_rds) { const int rc = ensure_rds(h); if (rc) return rc; }
     // (the RDS meter reads the path's own 24 kS/s ring and switches no decoder on: no part of CallNeeds, and nothing before a decoder runs)
-    if (!h->rdsm_alloc && nd.any_rds && std::any_of(h->user.begin(), h->user.end(), [](const ChanUser &u) { return u.rdsm; })) { const int rc = ensure_rds_meter(h); if (rc) return rc; }
-    if (h->rdsm_alloc) for (int c = 0; c < h->channels; c++) h->call_rdsm[(size_t)c] = h->user[(size_t)c].rdsm ? 1 : 0;
+    FMXCHK(flush_record_tap(h, h->rdsm_tap, nd.any_rds, rdsm::QUANT * rdsm::LANES, rdsm::RING, h->d_rdsm_state, h->d_rdsm_ring, h->d_rdsm_jobs));
     // (the spectrum meter reads the call's input and its own memory: no part of CallNeeds.  fmx_spectrum_setup's grid is taken over here, while no
     // stream's meter is on: indices, cursors and what the ring held start over)
-    if (h->spec_setup_dirty) {
-        h->spec_B = h->spec_B_user; h->spec_S = h->spec_S_user; h->spec_setup_dirty = false;
-        std::fill(h->spec_on_from.begin(), h->spec_on_from.end(), -1); std::fill(h->spec_tag.begin(), h->spec_tag.end(), -1);
-        std::fill(h->rd.spec.begin(), h->rd.spec.end(), 0);
-    }
-    if (!h->user_spec.empty()) {
-        if (std::any_of(h->user_spec.begin(), h->user_spec.end(), [](uint8_t on) { return on != 0; })) { const int rc = ensure_spectrum(h); if (rc) return rc; }
-        if (!h->call_spec.empty()) h->call_spec = h->user_spec;
-    }
+    if (h->spec_setup_dirty) { h->spec_B = h->spec_B_user; h->spec_S = h->spec_S_user; h->spec_setup_dirty = false; h->spec_tap.restart(); }
+    FMXCHK(flush_slot_tap(h, h->spec_tap, ensure_spectrum, false));      // (no `live`: run_piece looks at the slots allocated)
     // (the multiplex spectrum meter reads the rows a metered channel asks for above -- ChanNeeds::metered -- and its own memory.  fmx_mpx_spectrum_setup's
-    // grid is taken over here, while no channel's meter is on: indices, cursors and what the ring held start over)
-    if (h->mpx_setup_dirty) {
-        h->mpx_B = h->mpx_B_user; h->mpx_S = h->mpx_S_user; h->mpx_setup_dirty = false;
-        std::fill(h->mpx_on_from.begin(), h->mpx_on_from.end(), -1); std::fill(h->mpx_tag.begin(), h->mpx_tag.end(), -1);
-        std::fill(h->rd.mpx.begin(), h->rd.mpx.end(), 0);
-    }
-    if (!h->user_mpx.empty()) {
-        // (mpx_live: stage_mpx has something to do -- a meter is on, or was and its channel's first sample has not been cleared yet)
-        if (std::any_of(h->user_mpx.begin(), h->user_mpx.end(), [](uint8_t on) { return on != 0; })) { const int rc = ensure_mpx(h); if (rc) return rc; h->mpx_live = true; }
-        if (!h->call_mpx.empty()) h->call_mpx = h->user_mpx;
-    }
+    // grid is taken over here, while no channel's meter is on: indices, cursors and what the ring held start over.  live: stage_mpx has something to do --
+    // a meter is on, or was and its channel's first sample has not been cleared yet)
+    if (h->mpx_setup_dirty) { h->mpx_B = h->mpx_B_user; h->mpx_S = h->mpx_S_user; h->mpx_setup_dirty = false; h->mpx_tap.restart(); }
+    FMXCHK(flush_slot_tap(h, h->mpx_tap, ensure_mpx, true));
     // (the sub-carrier decoder reads the rows a decoding channel asks for above -- ChanNeeds::metered -- and its own memory.  fmx_sca_setup's values are
-    // taken over here, while no channel decodes: cursors and what the ring held start over.  sca_live: stage_sca has something to do -- a channel decodes,
+    // taken over here, while no channel decodes: cursors and what the ring held start over.  live: stage_sca has something to do -- a channel decodes,
     // or did and its first sample has not been cleared yet)
-    if (h->sca_setup_dirty) {
-        h->sca_cfg = h->sca_cfg_user; h->sca_setup_dirty = false; h->sca_taps_stale = true;
-        std::fill(h->sca_on_from.begin(), h->sca_on_from.end(), -1); std::fill(h->sca_tag.begin(), h->sca_tag.end(), -1);
-        std::fill(h->rd.sca.begin(), h->rd.sca.end(), 0);
-    }
-    if (!h->user_sca.empty()) {
-        if (std::any_of(h->user_sca.begin(), h->user_sca.end(), [](int32_t hz) { return hz != 0; })) { const int rc = ensure_sca(h); if (rc) return rc; h->sca_live = true; }
-        if (!h->call_sca.empty()) h->call_sca = h->user_sca;
-    }
+    if (h->sca_setup_dirty) { h->sca_cfg = h->sca_cfg_user; h->sca_setup_dirty = false; h->sca_taps_stale = true; h->sca_tap.restart(); }
+    FMXCHK(flush_slot_tap(h, h->sca_tap, ensure_sca, true));
     // (the monitoring feed reads the call's PCM behind everything that writes it, as the audio meter does, and its own memory: no part of CallNeeds.
-    // feed_live: stage_feed has something to do -- a channel feeds, or did and its first frame has not been cleared yet)
-    if (!h->user_feed.empty()) {
-        if (std::any_of(h->user_feed.begin(), h->user_feed.end(), [](int32_t mode) { return mode != 0; })) { const int rc = ensure_feed(h); if (rc) return rc; h->feed_live = true; }
-        if (!h->call_feed.empty()) h->call_feed = h->user_feed;
-    }
+    // live: stage_feed has something to do -- a channel feeds, or did and its first frame has not been cleared yet)
+    FMXCHK(flush_slot_tap(h, h->feed_tap, ensure_feed, true));
     if (nd.keep_taps && !h->w_diff_mem) {
         HIPCHK(hipDeviceSynchronize());
         FMXCHK(h->mem.alloc(h->w_diff_mem, (size_t)h->work_nj * h->pitch, true));
@@ -1156,17 +1053,17 @@ int stage_rds_meter(fmx_handle h, const CallGeom &G, hipStream_t s) {
         std::lock_guard<std::mutex> lk(h->mtx);      // (fmx_rds_meter_records reads the counters from any thread)
         for (int c = 0; c < h->channels; c++) {
             const int64_t a = h->rds_nc0[(size_t)c];
-            if (a >= 0 && h->call_rdsm[(size_t)c] && !rdsm::ring_holds(a / 8, (a + nj) / 8))
+            if (a >= 0 && h->rdsm_tap.call[(size_t)c] && !rdsm::ring_holds(a / 8, (a + nj) / 8))
                 return fail(FMX_E_TOO_LARGE, "the piece has more RDS samples than the path's 24 kS/s ring holds");
         }
         for (int c = 0; c < h->channels; c++) {
             const int64_t a = h->rds_nc0[(size_t)c];
-            const rdsm::Piece p = rdsm::piece(h->call_rdsm[(size_t)c] != 0, a >= 0, h->rdsm_on_from[(size_t)c], a < 0 ? 0 : a / 8, a < 0 ? 0 : (a + nj) / 8,
-                                              h->rdsm_produced[(size_t)c]);
-            h->rdsm_on_from[(size_t)c] = p.on_from;
+            RecordTap &T = h->rdsm_tap;      // (on_from is rdsm::piece's, the decoder-off case included: no begin here)
+            const rdsm::Piece p = rdsm::piece(T.call[(size_t)c] != 0, a >= 0, T.on_from[(size_t)c], a < 0 ? 0 : a / 8, a < 0 ? 0 : (a + nj) / 8, T.produced[(size_t)c]);
+            T.on_from[(size_t)c] = p.on_from;
             if (!p.job) continue;
             h->rdsm_jobs.push_back(RdsmJob{p.first, (a + nj) / 8, c, (int32_t)p.slot(0)});
-            h->rdsm_produced[(size_t)c] = p.new_produced;
+            T.produced[(size_t)c] = p.new_produced;
         }
     }
     const size_t n = h->rdsm_jobs.size();
@@ -1197,7 +1094,7 @@ int stage_rds(fmx_handle h, const CallGeom &G, hipStream_t s) {
         h->last_m0[(size_t)c] = a / 8; h->last_m1[(size_t)c] = (a + nj) / 8;
         h->rds_nc[(size_t)c] = a + nj;
     }
-    return h->rdsm_alloc ? stage_rds_meter(h, G, s) : FMX_OK;
+    return h->rdsm_tap.alloc ? stage_rds_meter(h, G, s) : FMX_OK;
 }
 
 // scan mode: the scanning channels' fm samples of the call behind their carries, every complete block of 1024 into the record ring (fmx_scan.hip), on the
@@ -1240,12 +1137,12 @@ int stage_meter(fmx_handle h, const CallGeom &G, hipStream_t s) {
     {
         std::lock_guard<std::mutex> lk(h->mtx);      // (fmx_mod_records reads the counters from any thread)
         for (int c = 0; c < h->channels; c++) {
-            if (!h->call_meter[(size_t)c]) { h->meter_on_from[(size_t)c] = -1; continue; }      // (off: the window in progress is dropped)
-            if (h->meter_on_from[(size_t)c] < 0) h->meter_on_from[(size_t)c] = G.J0;
-            const meter::Produce mp = meter::meter_produce(h->meter_on_from[(size_t)c], G.J0, nj, h->meter_produced[(size_t)c]);
+            RecordTap &T = h->mod_tap;
+            if (!T.begin((size_t)c, G.J0)) continue;      // (off: the window in progress is dropped)
+            const meter::Produce mp = meter::meter_produce(T.on_from[(size_t)c], G.J0, nj, T.produced[(size_t)c]);
             if (mp.first >= G.J1) continue;
             h->meter_jobs.push_back(MeterJob{c, (int32_t)(mp.first - G.J0), (int32_t)mp.slot(0), 0});
-            h->meter_produced[(size_t)c] = mp.new_produced;
+            T.produced[(size_t)c] = mp.new_produced;
         }
     }
     const size_t n = h->meter_jobs.size();
@@ -1271,13 +1168,11 @@ int stage_mpx(fmx_handle h, const CallGeom &G, hipStream_t s) {
     const int32_t S = h->mpx_S, B = h->mpx_B;
     const spec::Piece p = spec::piece(G.J0, nj, S, B);
     h->mpx_jobs.clear();
-    for (int c = 0; c < h->channels; c++) {
-        if (!h->call_mpx[(size_t)c]) { h->mpx_on_from[(size_t)c] = -1; continue; }      // (off: the record in progress is dropped)
-        if (h->mpx_on_from[(size_t)c] < 0) h->mpx_on_from[(size_t)c] = G.J0;
-        h->mpx_jobs.push_back(MpxJob{c, h->mpx_slot[(size_t)c], spec::first_block(h->mpx_on_from[(size_t)c], S)});
-    }
+    SlotTap &T = h->mpx_tap;
+    for (int c = 0; c < h->channels; c++)
+        if (T.begin((size_t)c, G.J0)) h->mpx_jobs.push_back(MpxJob{c, T.slot[(size_t)c], spec::first_block(T.on_from[(size_t)c], S)});      // (off: the record in progress is dropped)
     const int64_t n_jobs = (int64_t)h->mpx_jobs.size();
-    if (n_jobs == 0) { h->mpx_live = false; return FMX_OK; }      // (every meter is off and every first sample cleared: nothing to do until one is switched on)
+    if (n_jobs == 0) { T.live = false; return FMX_OK; }      // (every meter is off and every first sample cleared: nothing to do until one is switched on)
     if (h->mpx_c_B != B) {                    // (c follows B: fmx_mpx_spectrum_setup)
         std::vector<float> win(mpx::N);
         survey::make_window(win.data());
@@ -1300,7 +1195,7 @@ int stage_mpx(fmx_handle h, const CallGeom &G, hipStream_t s) {
     const int64_t r_end = p.record0 + p.records;
     for (const MpxJob &job : h->mpx_jobs)
         for (int64_t r = std::max(p.record0, r_end - mpx::RING); r < r_end; r++)
-            if (spec::delivered(r, B, job.first)) h->mpx_tag[(size_t)job.channel * mpx::RING + (size_t)(r & (mpx::RING - 1))] = r;
+            if (spec::delivered(r, B, job.first)) T.tag((size_t)job.channel, r, r & (mpx::RING - 1));
     return FMX_OK;
 }
 
@@ -1313,23 +1208,21 @@ int stage_sca(fmx_handle h, const CallGeom &G, hipStream_t s) {
     const int64_t nj = G.J1 - G.J0;
     if (nj > h->work_nj) return fail(FMX_E_TOO_LARGE, "the piece has more fm samples than stage B's rows hold");
     std::lock_guard<std::mutex> lk(h->mtx);
+    SlotTap &T = h->sca_tap;
     h->sca_jobs.clear();
     for (int c = 0; c < h->channels; c++) {
-        const int32_t centre = h->call_sca[(size_t)c];
-        if (!centre) { h->sca_on_from[(size_t)c] = -1; continue; }          // (off: the block in progress is dropped)
-        const int32_t slot = h->sca_slot[(size_t)c];
-        if (h->sca_slot_centre[(size_t)c] != centre) {                       // (another centre is another sub-carrier: it starts as a channel switched on does)
+        const int32_t centre = T.call[(size_t)c], slot = T.slot[(size_t)c];
+        if (centre && h->sca_slot_centre[(size_t)c] != centre) {                       // (another centre is another sub-carrier: it starts as a channel switched on does)
             std::vector<float2> taps = sca::mixed_taps(h->sca_g, centre, h->cfg.fmRate);
             taps.push_back(sca::rotation(centre, h->cfg.fmRate));
             // (pageable source: the copy is staged before the call returns)
             HIPCHK(hipMemcpyAsync(h->d_sca_taps + (size_t)slot * (sca::NG + 1), taps.data(), sizeof(float2) * taps.size(), hipMemcpyHostToDevice, s));
-            h->sca_slot_centre[(size_t)c] = centre; h->sca_on_from[(size_t)c] = -1;
+            h->sca_slot_centre[(size_t)c] = centre; T.restart_unit((size_t)c);
         }
-        if (h->sca_on_from[(size_t)c] < 0) h->sca_on_from[(size_t)c] = G.J0;
-        h->sca_jobs.push_back(ScaJob{c, slot, sca::first_block(h->sca_on_from[(size_t)c])});
+        if (T.begin((size_t)c, G.J0)) h->sca_jobs.push_back(ScaJob{c, slot, sca::first_block(T.on_from[(size_t)c])});      // (off: the block in progress is dropped)
     }
     const int64_t n_jobs = (int64_t)h->sca_jobs.size();
-    if (n_jobs == 0) { h->sca_live = false; return FMX_OK; }      // (no channel decodes and every first sample is cleared: nothing to do until one is switched on)
+    if (n_jobs == 0) { T.live = false; return FMX_OK; }      // (no channel decodes and every first sample is cleared: nothing to do until one is switched on)
     HIPCHK(hipMemcpyAsync(h->d_sca_jobs, h->sca_jobs.data(), sizeof(ScaJob) * (size_t)n_jobs, hipMemcpyHostToDevice, s));
     const int64_t bn = G.J0 / sca::BLOCK_FM, be = G.J1 / sca::BLOCK_FM;
     ScaArgs A{};
@@ -1340,7 +1233,7 @@ int stage_sca(fmx_handle h, const CallGeom &G, hipStream_t s) {
     launch_sca(A, s);
     HIPCHK(hipEventRecord(h->ev_sca, s)); h->ev_sca_set = true;
     for (const ScaJob &job : h->sca_jobs)
-        for (int64_t b = std::max(A.b_lo, job.first); b < be; b++) h->sca_tag[(size_t)job.channel * sca::RING + (size_t)(b % sca::RING)] = b;
+        for (int64_t b = std::max(A.b_lo, job.first); b < be; b++) T.tag((size_t)job.channel, b, b % sca::RING);
     return FMX_OK;
 }
 
@@ -1354,15 +1247,15 @@ int stage_rx(fmx_handle h, const CallGeom &G, hipStream_t sa) {
     {
         std::lock_guard<std::mutex> lk(h->mtx);      // (fmx_rx_records reads the counters from any thread)
         for (int c = 0; c < h->channels; c++)
-            if (h->call_rx[(size_t)c] && !rx::ring_holds(h->ring, h->h_front_sets[(size_t)h->params[(size_t)c].front_set].delay_fm, nj, h->twins))
+            if (h->rx_tap.call[(size_t)c] && !rx::ring_holds(h->ring, h->h_front_sets[(size_t)h->params[(size_t)c].front_set].delay_fm, nj, h->twins))
                 return fail(FMX_E_TOO_LARGE, "the piece has more fm samples than stage A's ring keeps behind the reception meter's look-back");
         for (int c = 0; c < h->channels; c++) {
-            if (!h->call_rx[(size_t)c]) { h->rx_on_from[(size_t)c] = -1; continue; }      // (off: the window in progress is dropped)
-            if (h->rx_on_from[(size_t)c] < 0) h->rx_on_from[(size_t)c] = G.J0;
-            const meter::Produce mp = meter::meter_produce(h->rx_on_from[(size_t)c], G.J0, nj, h->rx_produced[(size_t)c]);
+            RecordTap &T = h->rx_tap;
+            if (!T.begin((size_t)c, G.J0)) continue;      // (off: the window in progress is dropped)
+            const meter::Produce mp = meter::meter_produce(T.on_from[(size_t)c], G.J0, nj, T.produced[(size_t)c]);
             if (mp.first >= G.J1) continue;
             h->rx_jobs.push_back(RxJob{c, (int32_t)(mp.first - G.J0), (int32_t)mp.slot(0), 0});
-            h->rx_produced[(size_t)c] = mp.new_produced;
+            T.produced[(size_t)c] = mp.new_produced;
         }
     }
     const size_t n = h->rx_jobs.size();
@@ -1386,11 +1279,9 @@ int stage_spectrum(fmx_handle h, const CallGeom &G, const void *d_iq, hipStream_
     const int32_t S = h->spec_S, B = h->spec_B;
     const spec::Piece p = spec::piece(G.g0, G.n, S, B);
     h->spec_jobs.clear();
-    for (int st = 0; st < h->streams; st++) {
-        if (!h->call_spec[(size_t)st]) { h->spec_on_from[(size_t)st] = -1; continue; }      // (off: the record in progress is dropped)
-        if (h->spec_on_from[(size_t)st] < 0) h->spec_on_from[(size_t)st] = G.g0;
-        h->spec_jobs.push_back(SpecJob{st, h->spec_slot[(size_t)st], spec::first_block(h->spec_on_from[(size_t)st], S)});
-    }
+    SlotTap &T = h->spec_tap;
+    for (int st = 0; st < h->streams; st++)
+        if (T.begin((size_t)st, G.g0)) h->spec_jobs.push_back(SpecJob{st, T.slot[(size_t)st], spec::first_block(T.on_from[(size_t)st], S)});      // (off: the record in progress is dropped)
     const int64_t nj = (int64_t)h->spec_jobs.size();
     if (nj == 0) return FMX_OK;
     if (h->spec_c_B != B) {                   // (c follows B: fmx_spectrum_setup)
@@ -1416,7 +1307,7 @@ int stage_spectrum(fmx_handle h, const CallGeom &G, const void *d_iq, hipStream_
     const int64_t r_end = p.record0 + p.records;
     for (const SpecJob &job : h->spec_jobs)
         for (int64_t r = std::max(p.record0, r_end - spec::RING); r < r_end; r++)
-            if (spec::delivered(r, B, job.first)) h->spec_tag[(size_t)job.stream * spec::RING + (size_t)(r & (spec::RING - 1))] = r;
+            if (spec::delivered(r, B, job.first)) T.tag((size_t)job.stream, r, r & (spec::RING - 1));
     return FMX_OK;
 }
 
@@ -1436,11 +1327,11 @@ int stage_audio_meter(fmx_handle h, const CallGeom &G, const float2 *d_pcm, int6
     {
         std::lock_guard<std::mutex> lk(h->mtx);      // (fmx_audio_records reads the counters from any thread)
         for (int c = 0; c < h->channels; c++) {
-            if (!h->call_loud[(size_t)c]) { h->loud_on_from[(size_t)c] = -1; continue; }      // (off: the window in progress and the states are dropped)
-            if (h->loud_on_from[(size_t)c] < 0) h->loud_on_from[(size_t)c] = G.M0;
-            const loud::Produce ap = loud::audio_produce(h->loud_on_from[(size_t)c], G.M0, frames, h->loud_produced[(size_t)c]);
+            RecordTap &T = h->audio_tap;
+            if (!T.begin((size_t)c, G.M0)) continue;      // (off: the window in progress and the states are dropped)
+            const loud::Produce ap = loud::audio_produce(T.on_from[(size_t)c], G.M0, frames, T.produced[(size_t)c]);
             h->loud_jobs.push_back(LoudJob{c, ap.first == G.M0 ? 1 : 0, (int32_t)ap.slot(0), ap.reset ? 1 : 0});
-            h->loud_produced[(size_t)c] = ap.new_produced;
+            T.produced[(size_t)c] = ap.new_produced;
         }
     }
     const size_t n = h->loud_jobs.size();
@@ -1461,16 +1352,16 @@ int stage_audio_meter(fmx_handle h, const CallGeom &G, const float2 *d_pcm, int6
 // are formed.  The ring tags -- which block a slot holds -- change under mtx with the event the read-outs wait for.
 int stage_feed(fmx_handle h, const CallGeom &G, const float2 *d_pcm, int64_t frames, hipStream_t s) {
     std::lock_guard<std::mutex> lk(h->mtx);
+    SlotTap &T = h->feed_tap;
     h->feed_jobs.clear();
     for (int c = 0; c < h->channels; c++) {
-        const int32_t mode = h->call_feed[(size_t)c];
-        if (!mode) { h->feed_on_from[(size_t)c] = -1; h->feed_mode[(size_t)c] = 0; continue; }      // (off: the block in progress and the carry are dropped)
-        if (h->feed_mode[(size_t)c] != mode) { h->feed_mode[(size_t)c] = mode; h->feed_on_from[(size_t)c] = -1; }
-        if (h->feed_on_from[(size_t)c] < 0) h->feed_on_from[(size_t)c] = G.M0;
-        h->feed_jobs.push_back(FeedJob{c, h->feed_slot[(size_t)c], mode, 0, feed::first_block(h->feed_on_from[(size_t)c])});
+        const int32_t mode = T.call[(size_t)c];
+        if (mode && h->feed_mode[(size_t)c] != mode) T.restart_unit((size_t)c);
+        h->feed_mode[(size_t)c] = mode;
+        if (T.begin((size_t)c, G.M0)) h->feed_jobs.push_back(FeedJob{c, T.slot[(size_t)c], mode, 0, feed::first_block(T.on_from[(size_t)c])});      // (off: the block in progress and the carry are dropped)
     }
     const int64_t n_jobs = (int64_t)h->feed_jobs.size();
-    if (n_jobs == 0) { h->feed_live = false; return FMX_OK; }      // (no channel feeds and every first frame is cleared: nothing to do until one is switched on)
+    if (n_jobs == 0) { T.live = false; return FMX_OK; }      // (no channel feeds and every first frame is cleared: nothing to do until one is switched on)
     if (frames <= 0) return FMX_OK;
     if (h->ev_feed_rd_set) HIPCHK(hipStreamWaitEvent(s, h->ev_feed_rd, 0));      // (a fmx_feed_read_device still gathering on another stream reads the ring first)
     // (pageable source: the copy is staged before the call returns)
@@ -1483,7 +1374,7 @@ int stage_feed(fmx_handle h, const CallGeom &G, const float2 *d_pcm, int64_t fra
     launch_feed(A, s);
     HIPCHK(hipEventRecord(h->ev_feed, s)); h->ev_feed_set = true;
     for (const FeedJob &job : h->feed_jobs)
-        for (int64_t b = std::max(A.b_lo, job.first); b < be; b++) h->feed_tag[(size_t)job.channel * feed::RING + (size_t)feed::ring_slot(b)] = b;
+        for (int64_t b = std::max(A.b_lo, job.first); b < be; b++) T.tag((size_t)job.channel, b, feed::ring_slot(b));
     return FMX_OK;
 }
 
@@ -1556,8 +1447,8 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     if (capture && (rc = capture_samples(h, d_iq, a, G, sa))) return rc;
     if ((rc = stage_a(h, G, d_iq, s, sa))) return rc;
     if (!h->call_scan.empty() && G.J1 > G.J0 && (rc = stage_scan(h, G, sa))) return rc;
-    if (h->rx_alloc && G.J1 > G.J0 && (rc = stage_rx(h, G, sa))) return rc;
-    if (h->spec_cap > 0 && (rc = stage_spectrum(h, G, d_iq, s, sa))) return rc;
+    if (h->rx_tap.alloc && G.J1 > G.J0 && (rc = stage_rx(h, G, sa))) return rc;
+    if (h->spec_tap.cap > 0 && (rc = stage_spectrum(h, G, d_iq, s, sa))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[1], sa));
     G.stageb_form = h->stageb_form.load(); G.no_deemph = h->ola_mode ? 1 : 0;
     // a plain batch (no pre-pass, no RDS, no scope-tap rows: stage B as the whole kernel) runs stages B and C as two channel groups on two streams where it has
@@ -1569,14 +1460,14 @@ int run_piece(fmx_handle h, const CallArgs &a, const void *d_iq, int64_t n, floa
     h->last_second_group = second;
     if ((rc = stage_b(h, G, k, piped, second, s, sa))) return rc;
     if (rds_running && (rc = stage_rds(h, G, s))) return rc;
-    if (h->meter_alloc && G.J1 > G.J0 && (rc = stage_meter(h, G, s))) return rc;
-    if (h->mpx_live && G.J1 > G.J0 && (rc = stage_mpx(h, G, s))) return rc;
-    if (h->sca_live && G.J1 > G.J0 && (rc = stage_sca(h, G, s))) return rc;
+    if (h->mod_tap.alloc && G.J1 > G.J0 && (rc = stage_meter(h, G, s))) return rc;
+    if (h->mpx_tap.live && G.J1 > G.J0 && (rc = stage_mpx(h, G, s))) return rc;
+    if (h->sca_tap.live && G.J1 > G.J0 && (rc = stage_sca(h, G, s))) return rc;
     if (prof) HIPCHK(hipEventRecord(pr.e[2], s));
     if ((rc = stage_c(h, G, d_pcm, frames, second, s))) return rc;
     if (!h->call_scan.empty() && frames > 0 && (rc = stage_scan_mute(h, d_pcm, G.pcm_stride, frames, s))) return rc;
-    if (h->loud_alloc && frames > 0 && (rc = stage_audio_meter(h, G, d_pcm, frames, s))) return rc;
-    if (h->feed_live && (rc = stage_feed(h, G, d_pcm, frames, s))) return rc;
+    if (h->audio_tap.alloc && frames > 0 && (rc = stage_audio_meter(h, G, d_pcm, frames, s))) return rc;
+    if (h->feed_tap.live && (rc = stage_feed(h, G, d_pcm, frames, s))) return rc;
     if (prof) { HIPCHK(hipEventRecord(pr.e[3], s)); h->prof.push_back(pr); }
     FMX_LAUNCHED();
     HIPCHK(g_launch_err);
@@ -1703,6 +1594,9 @@ int init_channels(fmx_handle h, const fmx_config *cfg, int decim, const Conv2Des
     h->ola_mode = filter_form(0, h->channels).ola_mode;          // FMX_P_FILTER_RESTARTS = 0 (automatic)
     h->user.assign(h->channels, ChanUser());
     h->rd.init((size_t)h->channels);
+    for (RecordTap *t : {&h->mod_tap, &h->audio_tap, &h->rx_tap, &h->rdsm_tap}) t->init((size_t)h->channels);
+    h->spec_tap.init((size_t)h->streams);
+    for (SlotTap *t : {&h->mpx_tap, &h->sca_tap, &h->feed_tap}) t->init((size_t)h->channels);
     h->params.assign(h->channels, ChanParams());
     for (int c = 0; c < h->channels; c++) {
         ChanParams &p = h->params[c];
@@ -1887,6 +1781,12 @@ int alloc_channel_buffers(fmx_handle h, const Conv2Design &cv) {
     return FMX_OK;
 }
 
+
+// a switch of the units [u, u + 1), or of all `units` of them (u < 0); under mtx
+template <class T> void set_range(std::vector<T> &v, int32_t u, int32_t units, T value) {
+    const int u0 = u < 0 ? 0 : u, u1 = u < 0 ? units : u + 1;
+    for (int i = u0; i < u1; i++) v[(size_t)i] = value;
+}
 }  // namespace
 
 extern "C" {
@@ -2007,8 +1907,7 @@ int fmx_mod_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
     if (!h) return fail(FMX_E_INVALID, "null handle");
     if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
-    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
-    for (int c = c0; c < c1; c++) h->user[(size_t)c].meter = on != 0;
+    set_range<uint8_t>(h->mod_tap.user, channel, h->channels, on != 0);
     return FMX_OK;
 }
 
@@ -2018,8 +1917,7 @@ int fmx_audio_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
     if (h->cv_nt != 0 || h->cfg.audioRate != 48000)
         return fail(FMX_E_UNSUPPORTED, "the audio meter's K-weighting coefficients are those of 48000 frames/s: not on a handle with another audioRate");
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
-    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
-    for (int c = c0; c < c1; c++) h->user[(size_t)c].loud = on != 0;
+    set_range<uint8_t>(h->audio_tap.user, channel, h->channels, on != 0);
     return FMX_OK;
 }
 
@@ -2027,8 +1925,7 @@ int fmx_rx_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
     if (!h) return fail(FMX_E_INVALID, "null handle");
     if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
-    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
-    for (int c = c0; c < c1; c++) h->user[(size_t)c].rx = on != 0;
+    set_range<uint8_t>(h->rx_tap.user, channel, h->channels, on != 0);
     return FMX_OK;
 }
 
@@ -2036,8 +1933,7 @@ int fmx_rds_meter_enable(fmx_handle h, int32_t channel, int32_t on) {
     if (!h) return fail(FMX_E_INVALID, "null handle");
     if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes, and no decoder is switched)
-    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
-    for (int c = c0; c < c1; c++) h->user[(size_t)c].rdsm = on != 0;
+    set_range<uint8_t>(h->rdsm_tap.user, channel, h->channels, on != 0);
     return FMX_OK;
 }
 
@@ -2046,7 +1942,7 @@ int fmx_spectrum_setup(fmx_handle h, int32_t blocks_per_record, int32_t every) {
     if (blocks_per_record < 1 || blocks_per_record > spec::MAX_B) return fail(FMX_E_INVALID, "blocks_per_record must be in [1, 4096]");
     if (every < 1 || every > spec::MAX_S) return fail(FMX_E_INVALID, "every must be in [1, 4096]");
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes the grid over at the next call)
-    if (std::any_of(h->user_spec.begin(), h->user_spec.end(), [](uint8_t on) { return on != 0; }))
+    if (h->spec_tap.any_on())
         return fail(FMX_E_INVALID, "fmx_spectrum_setup: a stream's spectrum meter is on");
     h->spec_B_user = blocks_per_record; h->spec_S_user = every; h->spec_setup_dirty = true;
     return FMX_OK;
@@ -2056,9 +1952,7 @@ int fmx_spectrum_enable(fmx_handle h, int32_t stream, int32_t on) {
     if (!h) return fail(FMX_E_INVALID, "null handle");
     if (stream < -1 || stream >= h->streams) return fail(FMX_E_INVALID, "stream out of range");
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
-    if (h->user_spec.empty()) h->user_spec.assign((size_t)h->streams, 0);
-    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? h->streams : stream + 1;
-    for (int s = s0; s < s1; s++) h->user_spec[(size_t)s] = on != 0;
+    set_range<int32_t>(h->spec_tap.user, stream, h->streams, on != 0);
     return FMX_OK;
 }
 
@@ -2067,7 +1961,7 @@ int fmx_mpx_spectrum_setup(fmx_handle h, int32_t blocks_per_record, int32_t ever
     if (blocks_per_record < 1 || blocks_per_record > mpx::MAX_B) return fail(FMX_E_INVALID, "blocks_per_record must be in [1, 4096]");
     if (every < 1 || every > mpx::MAX_S) return fail(FMX_E_INVALID, "every must be in [1, 4096]");
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes the grid over at the next call)
-    if (std::any_of(h->user_mpx.begin(), h->user_mpx.end(), [](uint8_t on) { return on != 0; }))
+    if (h->mpx_tap.any_on())
         return fail(FMX_E_INVALID, "fmx_mpx_spectrum_setup: a channel's multiplex spectrum meter is on");
     h->mpx_B_user = blocks_per_record; h->mpx_S_user = every; h->mpx_setup_dirty = true;
     return FMX_OK;
@@ -2077,9 +1971,7 @@ int fmx_mpx_spectrum_enable(fmx_handle h, int32_t channel, int32_t on) {
     if (!h) return fail(FMX_E_INVALID, "null handle");
     if (channel < -1 || channel >= h->channels) return fail(FMX_E_INVALID, "channel out of range");
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
-    if (h->user_mpx.empty()) h->user_mpx.assign((size_t)h->channels, 0);
-    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
-    for (int c = c0; c < c1; c++) h->user_mpx[(size_t)c] = on != 0;
+    set_range<int32_t>(h->mpx_tap.user, channel, h->channels, on != 0);
     return FMX_OK;
 }
 
@@ -2088,7 +1980,7 @@ int fmx_sca_setup(fmx_handle h, const fmx_sca_config *cfg) {
     const fmx_sca_config want = cfg ? *cfg : sca::default_config();
     if (const char *why = sca::config_error(&want, h->cfg.fmRate)) return fail(FMX_E_INVALID, std::string("fmx_sca_setup: ") + why);
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes the values over at the next call)
-    if (std::any_of(h->user_sca.begin(), h->user_sca.end(), [](int32_t hz) { return hz != 0; }))
+    if (h->sca_tap.any_on())
         return fail(FMX_E_INVALID, "fmx_sca_setup: a channel's sub-carrier decoder is on");
     h->sca_cfg_user = want; h->sca_setup_dirty = true;
     return FMX_OK;
@@ -2103,9 +1995,7 @@ int fmx_sca_enable(fmx_handle h, int32_t channel, int32_t centre_hz) {
     if (const char *why = sca::centre_error(centre_hz, cfg.half_band_hz, h->cfg.fmRate))
         return fail(FMX_E_INVALID, "fmx_sca_enable: centre_hz " + std::to_string(centre_hz) + " with half_band_hz " + std::to_string(cfg.half_band_hz) + " at fmRate " +
                                        std::to_string(h->cfg.fmRate) + ": " + why);
-    if (h->user_sca.empty()) h->user_sca.assign((size_t)h->channels, 0);
-    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
-    for (int c = c0; c < c1; c++) h->user_sca[(size_t)c] = centre_hz;
+    set_range<int32_t>(h->sca_tap.user, channel, h->channels, centre_hz);
     return FMX_OK;
 }
 
@@ -2116,16 +2006,14 @@ int fmx_feed_enable(fmx_handle h, int32_t channel, int32_t mode) {
     if (h->cv_nt != 0 || h->cfg.audioRate != 48000)
         return fail(FMX_E_UNSUPPORTED, "the feed's filter and its divide by 3 are those of 48000 frames/s: not on a handle with another audioRate");
     std::lock_guard<std::mutex> lk(h->mtx);      // (flush_mailbox takes it at the next call; nothing on the device changes)
-    if (h->user_feed.empty()) h->user_feed.assign((size_t)h->channels, 0);
-    const int c0 = channel < 0 ? 0 : channel, c1 = channel < 0 ? h->channels : channel + 1;
-    for (int c = c0; c < c1; c++) h->user_feed[(size_t)c] = mode;
+    set_range<int32_t>(h->feed_tap.user, channel, h->channels, mode);
     return FMX_OK;
 }
 
 int64_t fmx_feed_allocated(fmx_handle h) {
     if (!h) return 0;
     std::lock_guard<std::mutex> lk(h->mtx);
-    return (int64_t)h->feed_cap * feed::BYTES_PER_CHANNEL;
+    return (int64_t)h->feed_tap.cap * feed::BYTES_PER_CHANNEL;
 }
 
 int64_t fmx_filter_change_due(fmx_handle h) {

@@ -16,6 +16,7 @@
 #include "fmx_mpx.h"
 #include "fmx_sca.h"
 #include "fmx_feed.h"
+#include "fmx_taps.h"
 
 #include <algorithm>
 #include <atomic>
@@ -76,6 +77,32 @@ struct DevMem {
     }
 };
 
+// A slotted array of a slot tap (fmx_taps.h) grows: `new_slots` x `per_slot` zeroed elements, the `old_slots` in use copied, the old array released (hipFree
+// waits for the copy), the new pointer stored.  The caller synchronises the device in front of a growth's first array and behind its last copy.
+template <class T> int grow_slots(DevMem &mem, T *&p, size_t old_slots, size_t new_slots, size_t per_slot) {
+    T *q = nullptr;
+    FMXCHK(mem.alloc(q, new_slots * per_slot, true));
+    if (old_slots > 0) HIPCHK(hipMemcpy(q, p, sizeof(T) * old_slots * per_slot, hipMemcpyDeviceToDevice));
+    mem.release(p);
+    p = q;
+    return FMX_OK;
+}
+
+// The staging of a gather read-out (fmx_mpx_spectrum_read, fmx_sca_read; under mtx): which ring items to gather, where the device gathers them, and the
+// pinned copy of that.  `src` is the host's list: a member, so that an asynchronous upload never reads a vector that has gone.
+struct GatherStage {
+    int32_t *d_src = nullptr; float *d_stage = nullptr, *h_stage = nullptr; int64_t cap = 0; std::vector<int32_t> src;
+    int ensure(DevMem &mem, int64_t batch, size_t floats_per_item) {
+        if (batch <= cap) return FMX_OK;
+        mem.release(d_src); mem.release(d_stage); mem.release(h_stage); cap = 0;
+        FMXCHK(mem.alloc(d_src, (size_t)batch));
+        FMXCHK(mem.alloc(d_stage, (size_t)batch * floats_per_item));
+        FMXCHK(mem.alloc_pinned(h_stage, (size_t)batch * floats_per_item));
+        cap = batch;
+        return FMX_OK;
+    }
+};
+
 inline int bytes_per_sample(int32_t fmt) { return fmt == FMX_IQ_F32 ? 8 : (fmt == FMX_IQ_S16 ? 4 : 2); }
 
 // per-channel user-level settings (what the fmProcessor setters store)
@@ -97,17 +124,14 @@ struct ChanUser {
     // scan mode (FMX_P_SCANNING, FMX_P_SCAN_THRESHOLD): startScanning / stopScanning, the constructor's thresHold (fm-processor.cpp:63,108,361-367)
     bool    scanning = false;
     int16_t scan_thr = 20;
-    bool    meter = false;       // the modulation meter (fmx_mod_meter_enable)
-    bool    loud = false;        // the programme audio meter (fmx_audio_meter_enable)
-    bool    rx = false;          // the reception meter (fmx_rx_meter_enable)
-    bool    rdsm = false;        // the RDS meter (fmx_rds_meter_enable)
 };
 
 struct ProfRec { hipEvent_t e[4]; int64_t in_samples, ch_samples; int n; };
 
-// Where every read-out of fmx_readout.hip stands, per channel: the number of the next item its ring's producer counts (ring_take, fmx_needs.h), the
-// reset requests of the two RDS decoder paths, and their group decoders.  The cursors and flags are sized by fmx_create (init); the decoders are large
-// and built by the first read-out that decodes.  ensure_rds_body starts `bits` over, ensure_scan `scan`.
+// Where the read-outs of the audio chain, the RDS path and scan mode stand, per channel: the number of the next item its ring's producer counts (ring_take,
+// fmx_needs.h), the reset requests of the two RDS decoder paths, and their group decoders.  The cursors and flags are sized by fmx_create (init); the
+// decoders are large and built by the first read-out that decodes.  ensure_rds_body starts `bits` over, ensure_scan `scan`.  The eight taps keep their
+// readers' cursors themselves (RecordTap::cursor, SlotTap::cursor: fmx_taps.h).
 // The count of a ring runs backwards only if its producer starts over, which no producer does today (fmx_rdssync.h).  Two readers of RdsState::nbits
 // provide for it all the same and start over themselves: fmx_rds_symbols (`symbols`) and fmx_rds_decode (`dec_bits`, with the decoder).  fmx_rds_bits
 // (`bits`) does not: it hands out nothing until the count has passed its cursor again.  The difference is kept as it was found.
@@ -119,19 +143,11 @@ struct Readers {
     std::vector<int64_t> dec_groups;         // fmx_rds_decode_all: groups of RdsSyncChan::groups
     std::vector<int64_t> groups;             // fmx_rds_groups: the same count
     std::vector<int64_t> scan;               // fmx_scan_results: blocks of fmx_handle_s::scan_blocks
-    std::vector<int64_t> mod;                // fmx_mod_records: records of fmx_handle_s::meter_produced
-    std::vector<int64_t> audio;              // fmx_audio_records: records of fmx_handle_s::loud_produced
-    std::vector<int64_t> rx;                 // fmx_rx_records: records of fmx_handle_s::rx_produced
-    std::vector<int64_t> rdsm;               // fmx_rds_meter_records: records of fmx_handle_s::rdsm_produced
-    std::vector<int64_t> spec;               // fmx_spectrum_read, per STREAM: the next record index it hands out (sized by the meter's first use)
-    std::vector<int64_t> mpx;                // fmx_mpx_spectrum_read, per channel: the next record index it hands out (sized by the meter's first use)
-    std::vector<int64_t> sca;                // fmx_sca_read, per channel: the next block it hands out (sized by the decoder's first use)
-    std::vector<int64_t> feed;               // fmx_feed_read / fmx_feed_read_device, per channel: the next block they hand out (sized by the feed's first use)
     std::vector<uint8_t> reset_dec, reset_dec_all;   // resetRds / triggerFrequencyChange asked for the group decoder's reset: fmx_rds_decode's, fmx_rds_decode_all's (under mtx)
     std::vector<RdsGroupDecoderHost> dec, dec_all;   // fmx_rds_decode's decoders (the synchroniser on the host), fmx_rds_decode_all's (on the GPU: rds_sync)
     void init(size_t channels) {
         peaks.assign(channels, 0); bits.assign(channels, 0); dec_bits.assign(channels, 0); symbols.assign(channels, 0);
-        dec_groups.assign(channels, 0); groups.assign(channels, 0); scan.assign(channels, 0); mod.assign(channels, 0); audio.assign(channels, 0); rx.assign(channels, 0); rdsm.assign(channels, 0);
+        dec_groups.assign(channels, 0); groups.assign(channels, 0); scan.assign(channels, 0);
         reset_dec.assign(channels, 0); reset_dec_all.assign(channels, 0);
     }
 };
@@ -206,96 +222,66 @@ struct fmx_handle_s {
     float2 *d_scan_W = nullptr, *d_scan_carry = nullptr, *d_scan_rec = nullptr; ScanJob *d_scan_jobs = nullptr; int32_t *d_scan_mute = nullptr;
     std::vector<ScanJob> scan_jobs;
     std::vector<int32_t> scan_fill; std::vector<int64_t> scan_blocks, scan_end; std::vector<int16_t> scan_rec_thr;
-    // the modulation meter (fmx_meter.hip, fmx_meter.h): the channels whose meter is on in the piece being made (flush_mailbox); per channel the fm sample
-    // since which its meter has been on in every piece (-1: off) and the records it has completed since fmx_create; the device keeps the lane accumulators
-    // of the window in progress and the record ring; allocated by the first call in which a meter is on
-    std::vector<uint8_t> call_meter;
-    bool meter_alloc = false;
-    float *d_meter_state = nullptr; fmx_mod_record *d_meter_ring = nullptr; MeterJob *d_meter_jobs = nullptr;
-    std::vector<MeterJob> meter_jobs;
-    std::vector<int64_t> meter_on_from, meter_produced;
-    // the programme audio meter (fmx_loud.hip, fmx_loud.h): the channels whose meter is on in the piece being made (flush_mailbox); per channel the PCM
-    // frame since which its meter has been on in every piece (-1: off) and the records it has completed since fmx_create; the device keeps each channel's
-    // 16 floats and the record ring; allocated by the first call in which a meter is on (ensure_audio_meter) -- a handle that never does has none of it
-    std::vector<uint8_t> call_loud;
-    bool loud_alloc = false;
-    float *d_loud_state = nullptr; fmx_audio_record *d_loud_ring = nullptr; LoudJob *d_loud_jobs = nullptr;
-    std::vector<LoudJob> loud_jobs;
-    std::vector<int64_t> loud_on_from, loud_produced;
-    // the reception meter (fmx_rx.hip, fmx_rx.h): the channels whose meter is on in the piece being made (flush_mailbox); per channel the fm sample since
-    // which its meter has been on in every piece (-1: off) and the records it has completed since fmx_create; the device keeps the lane accumulators of the
-    // window in progress and the record ring; allocated by the first call in which a meter is on (ensure_rx_meter) -- a handle that never does has none of it
-    std::vector<uint8_t> call_rx;
-    bool rx_alloc = false;
-    float *d_rx_state = nullptr; fmx_rx_record *d_rx_ring = nullptr; RxJob *d_rx_jobs = nullptr;
-    std::vector<RxJob> rx_jobs;
-    std::vector<int64_t> rx_on_from, rx_produced;
-    // the RDS meter (fmx_rdsm.hip, fmx_rdsm.h): the channels whose meter is on in the piece being made (flush_mailbox); per channel the RDS sample of its own
-    // count since which its meter has been on in every piece that produced one (-1: it has not) and the records it has completed since fmx_create; the
-    // device keeps the lane accumulators of the window in progress and the record ring; allocated by the first call in which a meter is on and a decoder
-    // runs (ensure_rds_meter) -- a handle that never does has none of it
-    std::vector<uint8_t> call_rdsm;
-    bool rdsm_alloc = false;
-    float *d_rdsm_state = nullptr; fmx_rds_meter_record *d_rdsm_ring = nullptr; RdsmJob *d_rdsm_jobs = nullptr;
-    std::vector<RdsmJob> rdsm_jobs;
-    std::vector<int64_t> rdsm_on_from, rdsm_produced;
-    // the spectrum meter (fmx_spec.hip, fmx_spec.h), per STREAM: the user's switch (under mtx), the streams whose meter is on in the piece being made
-    // (flush_mailbox), the input sample of the piece that switched it on (-1: off), its slot in the meter's device memory (-1: none yet; a stream keeps
-    // its slot) and per ring slot the record it holds (-1: none).  B and S in force, and what fmx_spectrum_setup asked for (taken over by flush_mailbox).
-    // The device keeps per slot the carry, sum and maximum, and the ring; memory grows with the streams switched on (ensure_spectrum) -- a handle that
-    // never switches the meter on has none of it
-    std::vector<uint8_t> user_spec, call_spec;
-    std::vector<int64_t> spec_on_from; std::vector<int32_t> spec_slot; std::vector<int64_t> spec_tag;
+    // The four record meters (RecordTap, fmx_taps.h: switches, on_from, produced and the reader's cursor, under mtx), each with its device side -- the
+    // accumulators of the window in progress, the record ring, the jobs -- and the jobs of the piece being made.  The device side is allocated by the first
+    // call in which a meter is on (ensure_record_tap): a handle that never switches a meter on has none of it.
+    // the modulation meter (fmx_meter.hip, fmx_meter.h): on_from and windows in fm samples
+    RecordTap mod_tap;
+    float *d_meter_state = nullptr; fmx_mod_record *d_meter_ring = nullptr; MeterJob *d_meter_jobs = nullptr; std::vector<MeterJob> meter_jobs;
+    // the programme audio meter (fmx_loud.hip, fmx_loud.h): in PCM frames; the device keeps each channel's 16 floats
+    RecordTap audio_tap;
+    float *d_loud_state = nullptr; fmx_audio_record *d_loud_ring = nullptr; LoudJob *d_loud_jobs = nullptr; std::vector<LoudJob> loud_jobs;
+    // the reception meter (fmx_rx.hip, fmx_rx.h): in fm samples
+    RecordTap rx_tap;
+    float *d_rx_state = nullptr; fmx_rx_record *d_rx_ring = nullptr; RxJob *d_rx_jobs = nullptr; std::vector<RxJob> rx_jobs;
+    // the RDS meter (fmx_rdsm.hip, fmx_rdsm.h): in RDS samples of the channel's own count, on_from that of the first piece that produced one (rdsm::piece);
+    // allocated by the first call in which a meter is on and a decoder runs
+    RecordTap rdsm_tap;
+    float *d_rdsm_state = nullptr; fmx_rds_meter_record *d_rdsm_ring = nullptr; RdsmJob *d_rdsm_jobs = nullptr; std::vector<RdsmJob> rdsm_jobs;
+    // The four slot taps (SlotTap, fmx_taps.h: the user's and the piece's values, slot, on_from, the reader's cursor, the ring tags, slots in use and
+    // allocated, live; under mtx), each with its slotted device arrays, the jobs of the piece being made, the event behind the last piece's kernels -- what
+    // its read-out waits for -- and whatever is its own.  The device arrays grow with the units switched on (grow_slots): a handle that never switches a
+    // tap on has none of its memory.
+    // the spectrum meter (fmx_spec.hip, fmx_spec.h), per STREAM, on_from in input samples: B and S in force and what fmx_spectrum_setup asked for (taken over
+    // by flush_mailbox); per slot the carry, sum and maximum, and the ring of records
+    SlotTap spec_tap;
     int32_t spec_B = 16, spec_S = 1, spec_B_user = 16, spec_S_user = 1; bool spec_setup_dirty = false;
-    int32_t spec_slots = 0, spec_cap = 0; int64_t spec_scratch = 0;      // slots in use, slots allocated, blocks of scratch allocated
+    int64_t spec_scratch = 0;                                           // blocks of scratch allocated
     float spec_c = 0.f, spec_c1 = 0.f; int32_t spec_c_B = 0;            // 1 / (B sum w^2) for B = spec_c_B, 1 / sum w^2
     float2 *d_spec_carry = nullptr, *d_spec_W = nullptr; float *d_spec_acc = nullptr, *d_spec_ring = nullptr, *d_spec_power = nullptr, *d_spec_win = nullptr;
     SpecJob *d_spec_jobs = nullptr; std::vector<SpecJob> spec_jobs;
-    hipEvent_t ev_spec = nullptr; bool ev_spec_set = false;             // behind the last piece's spectrum kernels: what fmx_spectrum_read waits for
-    // the multiplex spectrum meter (fmx_mpx.hip, fmx_mpx.h), per CHANNEL, kept as the spectrum meter keeps its streams: the user's switch (under mtx), the
-    // channels whose meter is on in the piece being made (flush_mailbox), the fm sample of the piece that switched it on (-1: off), its slot in the meter's
-    // device memory (-1: none yet; a channel keeps its slot) and per ring slot the record it holds (-1: none).  Per slot the device keeps the carry (16 KB),
-    // sum and maximum (16 KB) and the ring (64 KB); the window and the twiddles are d_spec_win / d_spec_W, shared with the spectrum meter
-    std::vector<uint8_t> user_mpx, call_mpx;
-    std::vector<int64_t> mpx_on_from; std::vector<int32_t> mpx_slot; std::vector<int64_t> mpx_tag;
+    hipEvent_t ev_spec = nullptr; bool ev_spec_set = false;
+    // the multiplex spectrum meter (fmx_mpx.hip, fmx_mpx.h), per CHANNEL, on_from in fm samples: per slot the carry (16 KB), sum and maximum (16 KB) and the
+    // ring (64 KB); the window and the twiddles are d_spec_win / d_spec_W, shared with the spectrum meter
+    SlotTap mpx_tap;
     int32_t mpx_B = mpx::DEFAULT_B, mpx_S = 1, mpx_B_user = mpx::DEFAULT_B, mpx_S_user = 1; bool mpx_setup_dirty = false;
-    int32_t mpx_slots = 0, mpx_cap = 0; int64_t mpx_scratch = 0;        // slots in use, slots allocated, blocks of scratch allocated
+    int64_t mpx_scratch = 0;                                            // blocks of scratch allocated
     float mpx_c = 0.f, mpx_c1 = 0.f; int32_t mpx_c_B = 0;              // 1 / (B sum w^2) for B = mpx_c_B, 1 / sum w^2
     float *d_mpx_carry = nullptr, *d_mpx_acc = nullptr, *d_mpx_ring = nullptr, *d_mpx_power = nullptr;
     MpxJob *d_mpx_jobs = nullptr; std::vector<MpxJob> mpx_jobs;
-    bool mpx_live = false;                                              // some channel's meter is on, or was in the last piece that looked (stage_mpx runs)
-    // the read-out's staging (fmx_mpx_spectrum_read, under mtx): which ring records to gather, where they are gathered, and the pinned copy of that
-    int32_t *d_mpx_src = nullptr; float *d_mpx_stage = nullptr, *h_mpx_stage = nullptr; int64_t mpx_stage_recs = 0; std::vector<int32_t> mpx_src;
-    hipEvent_t ev_mpx = nullptr; bool ev_mpx_set = false;               // behind the last piece's kernels: what fmx_mpx_spectrum_read waits for
-    // the sub-carrier decoder (fmx_sca.hip, fmx_sca.h), per CHANNEL, kept as the multiplex spectrum meter keeps its channels: the user's centre frequency
-    // (0: off; under mtx), the centres of the piece being made (flush_mailbox), the fm sample of the piece that switched the channel on (-1: off), its slot
-    // in the decoder's device memory (-1: none yet; a channel keeps its slot), the centre its slot's taps were made for, and per ring slot the block it holds
-    // (-1: none).  Per slot the device keeps the ring's audio (120 KB) and levels, the carry (10.25 KB) and the mixed taps with the rotation (1544 bytes)
-    std::vector<int32_t> user_sca, call_sca, sca_slot, sca_slot_centre;
-    std::vector<int64_t> sca_on_from, sca_tag;
+    GatherStage mpx_stage;                                              // fmx_mpx_spectrum_read's
+    hipEvent_t ev_mpx = nullptr; bool ev_mpx_set = false;
+    // the sub-carrier decoder (fmx_sca.hip, fmx_sca.h), per CHANNEL, the value a centre frequency, on_from in fm samples: the centre each channel's slot's
+    // taps were made for; per slot the ring's audio (120 KB) and levels, the carry (10.25 KB) and the mixed taps with the rotation (1544 bytes)
+    SlotTap sca_tap;
+    std::vector<int32_t> sca_slot_centre;
     fmx_sca_config sca_cfg = sca::default_config(), sca_cfg_user = sca::default_config(); bool sca_setup_dirty = false;
     bool sca_taps_stale = true;                                          // d_sca_a is not sca_cfg's (the setup changed, or nothing was uploaded yet)
-    int32_t sca_slots = 0, sca_cap = 0;
     std::vector<float> sca_g;                                            // the band filter of sca_cfg (the mixed taps are made from it per centre)
     float *d_sca_a = nullptr, *d_sca_carry = nullptr, *d_sca_audio = nullptr, *d_sca_level = nullptr; float2 *d_sca_taps = nullptr;
     ScaJob *d_sca_jobs = nullptr; std::vector<ScaJob> sca_jobs;
-    bool sca_live = false;                                               // some channel decodes, or did in the last piece that looked (stage_sca runs)
-    int32_t *d_sca_src = nullptr; float *d_sca_stage = nullptr, *h_sca_stage = nullptr; int64_t sca_stage_blocks = 0; std::vector<int32_t> sca_src;
-    hipEvent_t ev_sca = nullptr; bool ev_sca_set = false;                // behind the last piece's kernels: what fmx_sca_read waits for
-    // the monitoring feed (fmx_feed.hip, fmx_feed.h), per CHANNEL, kept as the sub-carrier decoder keeps its channels: the user's mode (0: off; under mtx),
-    // the modes of the piece being made (flush_mailbox), the mode the channel runs in, the frame of the piece that switched it on (-1: off), its slot in the
-    // feed's device memory (-1: none yet; a channel keeps its slot), and per ring slot the block it holds (-1: none).  Per slot the device keeps the ring's
+    GatherStage sca_stage;                                               // fmx_sca_read's
+    hipEvent_t ev_sca = nullptr; bool ev_sca_set = false;
+    // the monitoring feed (fmx_feed.hip, fmx_feed.h), per CHANNEL, the value a mode, on_from in PCM frames: the mode each channel runs in; per slot the ring's
     // audio (80 KB) and powers and the carry (2496 bytes); the taps are one array per handle
-    std::vector<int32_t> user_feed, call_feed, feed_slot, feed_mode;
-    std::vector<int64_t> feed_on_from, feed_tag;
-    int32_t feed_slots = 0, feed_cap = 0;
+    SlotTap feed_tap;
+    std::vector<int32_t> feed_mode;
     float *d_feed_h = nullptr, *d_feed_carry = nullptr, *d_feed_audio = nullptr, *d_feed_power = nullptr;
     FeedJob *d_feed_jobs = nullptr; std::vector<FeedJob> feed_jobs;
-    bool feed_live = false;                                              // some channel feeds, or did in the last piece that looked (stage_feed runs)
     // the read-outs' staging (under mtx): which ring blocks to gather and where to, where the host read-out gathers them, and the pinned copy of that
     int32_t *d_feed_src = nullptr; int64_t feed_src_cap = 0; std::vector<int32_t> feed_src, feed_dst;
     float *d_feed_stage = nullptr, *h_feed_stage = nullptr; int64_t feed_stage_blocks = 0;
-    hipEvent_t ev_feed = nullptr; bool ev_feed_set = false;              // behind the last piece's kernels: what the read-outs wait for
+    hipEvent_t ev_feed = nullptr; bool ev_feed_set = false;
     hipEvent_t ev_feed_rd = nullptr; bool ev_feed_rd_set = false;        // behind the last fmx_feed_read_device's gather: what the next use of d_feed_src, and the next piece's kernels, wait for
     std::atomic<int> stageb_form{0};     // FMX_P_STAGEB_FORM
     std::atomic<int> front_parts{0};     // FMX_P_FRONT_PARTS

@@ -2,7 +2,7 @@
 // and decoders, scan records, the modulation meter's, the audio meter's, the reception meter's and the RDS meter's records, the PLL counters, the facts about
 // the last call; the host-only RDS helpers, the host-only loudness figures (fmx_audio_loudness), reception figures (fmx_rx_quality_of) and RDS meter's
 // calibration and figures (fmx_rds_meter_cal, fmx_rds_meter_figures).  A per-channel read-out waits for the device, asks its ring's producer for the count, and takes [from, from + count) out of one copy of the ring (read_ring); where each reader stands is in the
-// handle's Readers (fmx_host.h).  The two batch RDS read-outs wait for the handle's last call only and copy every channel's ring at once (rds_batch_fetch).
+// handle's Readers (fmx_host.h), for the eight taps in the tap itself (RecordTap, SlotTap: fmx_taps.h).  The two batch RDS read-outs wait for the handle's last call only and copy every channel's ring at once (rds_batch_fetch).
 #include "fmx_host.h"
 #include "fmx_design.h"
 
@@ -45,6 +45,25 @@ template <class T, class F> int read_rings(const T *d_rings, int ring, int n, co
 // ... of one channel: visit (i, item)
 template <class T, class F> int read_ring(const T *d_ring, int ring, RingTake t, F &&visit) {
     return read_rings(d_ring, ring, 1, &t, [&](int, int64_t i, const T &item) { visit(i, item); });
+}
+
+// A record meter's read-out (RecordTap, fmx_taps.h): of the channels [first_channel, first_channel + n_channels) the records at the cursor, oldest first, at most
+// `cap` each, out of one copy of their rings; the cursors move behind what was handed out (a reader that fell behind: the gap shows in `index`)
+template <class R> int read_records(fmx_handle h, RecordTap fmx_handle_s::*tap, R *fmx_handle_s::*d_ring, int ring, int32_t first_channel, int32_t n_channels, R *out, int32_t cap,
+                                    int32_t *n_records) {
+    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || cap < 0 || (n_channels > 0 && (!n_records || (cap > 0 && !out))))
+        return fail(FMX_E_INVALID, "bad argument");
+    RecordTap &T = h->*tap;
+    for (int k = 0; k < n_channels; k++) n_records[k] = 0;
+    if (n_channels == 0 || !T.alloc) return FMX_OK;
+    FMXCHK(device_idle(h));
+    std::lock_guard<std::mutex> lk(h->mtx);
+    std::vector<RingTake> takes((size_t)n_channels);
+    for (int k = 0; k < n_channels; k++) takes[(size_t)k] = T.take((size_t)(first_channel + k), ring, cap);
+    FMXCHK(read_rings(h->*d_ring + (size_t)first_channel * (size_t)ring, ring, n_channels, takes.data(),
+                      [&](int k, int64_t i, const R &r) { out[(size_t)k * (size_t)cap + (size_t)i] = r; }));
+    for (int k = 0; k < n_channels; k++) { T.commit((size_t)(first_channel + k), takes[(size_t)k]); n_records[k] = (int32_t)takes[(size_t)k].count; }
+    return FMX_OK;
 }
 
 // fmx_pll_replays / fmx_pll_exact_segments: a counter of ChanState, of one channel or (channel < 0) summed over all
@@ -222,21 +241,7 @@ int fmx_scan_results(fmx_handle h, int32_t channel, fmx_scan_result *out, int32_
 }
 
 int fmx_mod_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_mod_record *out, int32_t capacity_per_channel, int32_t *n_records) {
-    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || capacity_per_channel < 0 ||
-        (n_channels > 0 && (!n_records || (capacity_per_channel > 0 && !out)))) return fail(FMX_E_INVALID, "bad argument");
-    for (int k = 0; k < n_channels; k++) n_records[k] = 0;
-    if (n_channels == 0 || !h->meter_alloc) return FMX_OK;
-    FMXCHK(device_idle(h));
-    std::lock_guard<std::mutex> lk(h->mtx);
-    std::vector<RingTake> takes((size_t)n_channels);
-    for (int k = 0; k < n_channels; k++) {
-        const size_t c = (size_t)(first_channel + k);
-        takes[(size_t)k] = ring_take(h->meter_produced[c], h->rd.mod[c], meter::RING, capacity_per_channel);      // (a reader that fell behind: the gap shows in `index`)
-    }
-    FMXCHK(read_rings(h->d_meter_ring + (size_t)first_channel * meter::RING, meter::RING, n_channels, takes.data(),
-                      [&](int k, int64_t i, const fmx_mod_record &r) { out[(size_t)k * (size_t)capacity_per_channel + (size_t)i] = r; }));
-    for (int k = 0; k < n_channels; k++) { h->rd.mod[(size_t)(first_channel + k)] = takes[(size_t)k].next(); n_records[k] = (int32_t)takes[(size_t)k].count; }
-    return FMX_OK;
+    return read_records(h, &fmx_handle_s::mod_tap, &fmx_handle_s::d_meter_ring, meter::RING, first_channel, n_channels, out, capacity_per_channel, n_records);
 }
 
 // Hz per unit of the demodulator output, in the reference's own float order: fm_Demodulator's constructor (fm-demodulator.cpp:58-64) makes K_FM of three
@@ -258,21 +263,7 @@ int fmx_mod_hz_per_unit(int32_t decoder, int32_t fmRate, double *hz) {
 }
 
 int fmx_audio_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_audio_record *out, int32_t capacity_per_channel, int32_t *n_records) {
-    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || capacity_per_channel < 0 ||
-        (n_channels > 0 && (!n_records || (capacity_per_channel > 0 && !out)))) return fail(FMX_E_INVALID, "bad argument");
-    for (int k = 0; k < n_channels; k++) n_records[k] = 0;
-    if (n_channels == 0 || !h->loud_alloc) return FMX_OK;
-    FMXCHK(device_idle(h));
-    std::lock_guard<std::mutex> lk(h->mtx);
-    std::vector<RingTake> takes((size_t)n_channels);
-    for (int k = 0; k < n_channels; k++) {
-        const size_t c = (size_t)(first_channel + k);
-        takes[(size_t)k] = ring_take(h->loud_produced[c], h->rd.audio[c], loud::RING, capacity_per_channel);      // (a reader that fell behind: the gap shows in `index`)
-    }
-    FMXCHK(read_rings(h->d_loud_ring + (size_t)first_channel * loud::RING, loud::RING, n_channels, takes.data(),
-                      [&](int k, int64_t i, const fmx_audio_record &r) { out[(size_t)k * (size_t)capacity_per_channel + (size_t)i] = r; }));
-    for (int k = 0; k < n_channels; k++) { h->rd.audio[(size_t)(first_channel + k)] = takes[(size_t)k].next(); n_records[k] = (int32_t)takes[(size_t)k].count; }
-    return FMX_OK;
+    return read_records(h, &fmx_handle_s::audio_tap, &fmx_handle_s::d_loud_ring, loud::RING, first_channel, n_channels, out, capacity_per_channel, n_records);
 }
 
 // BS.1770-4 over one channel's records (include/fmx.h): blocks of 4 consecutive records, the absolute gate at -70 LUFS, the relative gate 10 LU below the
@@ -320,21 +311,7 @@ int fmx_audio_loudness(const fmx_audio_record *recs, int32_t n, fmx_loudness *ou
 }
 
 int fmx_rx_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rx_record *out, int32_t capacity_per_channel, int32_t *n_records) {
-    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || capacity_per_channel < 0 ||
-        (n_channels > 0 && (!n_records || (capacity_per_channel > 0 && !out)))) return fail(FMX_E_INVALID, "bad argument");
-    for (int k = 0; k < n_channels; k++) n_records[k] = 0;
-    if (n_channels == 0 || !h->rx_alloc) return FMX_OK;
-    FMXCHK(device_idle(h));
-    std::lock_guard<std::mutex> lk(h->mtx);
-    std::vector<RingTake> takes((size_t)n_channels);
-    for (int k = 0; k < n_channels; k++) {
-        const size_t c = (size_t)(first_channel + k);
-        takes[(size_t)k] = ring_take(h->rx_produced[c], h->rd.rx[c], rx::RING, capacity_per_channel);      // (a reader that fell behind: the gap shows in `index`)
-    }
-    FMXCHK(read_rings(h->d_rx_ring + (size_t)first_channel * rx::RING, rx::RING, n_channels, takes.data(),
-                      [&](int k, int64_t i, const fmx_rx_record &r) { out[(size_t)k * (size_t)capacity_per_channel + (size_t)i] = r; }));
-    for (int k = 0; k < n_channels; k++) { h->rd.rx[(size_t)(first_channel + k)] = takes[(size_t)k].next(); n_records[k] = (int32_t)takes[(size_t)k].count; }
-    return FMX_OK;
+    return read_records(h, &fmx_handle_s::rx_tap, &fmx_handle_s::d_rx_ring, rx::RING, first_channel, n_channels, out, capacity_per_channel, n_records);
 }
 
 // the reception figures of one channel's records (include/fmx.h): level, the M2M4 carrier-to-noise estimate, the envelope's depth, the lag-1 offset
@@ -366,21 +343,7 @@ int fmx_rx_quality_of(const fmx_rx_record *recs, int32_t n, int32_t fmRate, fmx_
 }
 
 int fmx_rds_meter_records(fmx_handle h, int32_t first_channel, int32_t n_channels, fmx_rds_meter_record *out, int32_t capacity_per_channel, int32_t *n_records) {
-    if (!h || first_channel < 0 || n_channels < 0 || (int64_t)first_channel + n_channels > h->channels || capacity_per_channel < 0 ||
-        (n_channels > 0 && (!n_records || (capacity_per_channel > 0 && !out)))) return fail(FMX_E_INVALID, "bad argument");
-    for (int k = 0; k < n_channels; k++) n_records[k] = 0;
-    if (n_channels == 0 || !h->rdsm_alloc) return FMX_OK;
-    FMXCHK(device_idle(h));
-    std::lock_guard<std::mutex> lk(h->mtx);
-    std::vector<RingTake> takes((size_t)n_channels);
-    for (int k = 0; k < n_channels; k++) {
-        const size_t c = (size_t)(first_channel + k);
-        takes[(size_t)k] = ring_take(h->rdsm_produced[c], h->rd.rdsm[c], rdsm::RING, capacity_per_channel);      // (a reader that fell behind: the gap shows in `index`)
-    }
-    FMXCHK(read_rings(h->d_rdsm_ring + (size_t)first_channel * rdsm::RING, rdsm::RING, n_channels, takes.data(),
-                      [&](int k, int64_t i, const fmx_rds_meter_record &r) { out[(size_t)k * (size_t)capacity_per_channel + (size_t)i] = r; }));
-    for (int k = 0; k < n_channels; k++) { h->rd.rdsm[(size_t)(first_channel + k)] = takes[(size_t)k].next(); n_records[k] = (int32_t)takes[(size_t)k].count; }
-    return FMX_OK;
+    return read_records(h, &fmx_handle_s::rdsm_tap, &fmx_handle_s::d_rdsm_ring, rdsm::RING, first_channel, n_channels, out, capacity_per_channel, n_records);
 }
 
 // the calibration of a channel's RDS meter (include/fmx.h), from the taps the handle runs with: the 57 kHz band-pass (ensure_rds: only the real part of
@@ -470,26 +433,23 @@ int fmx_rds_meter_figures(const fmx_rds_meter_record *recs, int32_t n, const fmx
     return FMX_OK;
 }
 
-// the spectrum meter's records of one stream: which record a ring slot holds is the host's (fmx_handle_s::spec_tag); behind the handle's last call only
+// the spectrum meter's records of one stream: which record a ring slot holds is the host's (SlotTap::tags); behind the handle's last call only
 int fmx_spectrum_read(fmx_handle h, int32_t stream, fmx_spectrum_record *recs, float *mean, float *peak, int32_t capacity, int32_t *n_records) {
     if (!h || !n_records) return fail(FMX_E_INVALID, "null argument");
     *n_records = 0;
     if (stream < 0 || stream >= h->streams) return fail(FMX_E_INVALID, "stream out of range");
     if (capacity < 0 || (capacity > 0 && (!recs || !mean))) return fail(FMX_E_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(h->mtx);
-    if (h->spec_tag.empty() || capacity == 0) return FMX_OK;
-    int64_t have[spec::RING]; int n = 0;
-    for (int k = 0; k < spec::RING; k++) {
-        const int64_t r = h->spec_tag[(size_t)stream * spec::RING + (size_t)k];
-        if (r >= h->rd.spec[(size_t)stream]) have[n++] = r;      // (older ones were read, or overwritten: the gap shows in `index`)
-    }
-    std::sort(have, have + n);
-    n = std::min<int>(n, capacity);
+    SlotTap &T = h->spec_tap;
+    if (!T.started() || capacity == 0) return FMX_OK;
+    std::vector<int64_t> have;
+    T.pending((size_t)stream, capacity, have);      // (older ones were read, or overwritten: the gap shows in `index`)
+    const int n = (int)have.size();
     if (n == 0) return FMX_OK;
     HIPCHK(hipSetDevice(h->cfg.device));
     if (!h->rd_stream) HIPCHK(hipStreamCreateWithFlags(&h->rd_stream, hipStreamNonBlocking));
     if (h->ev_spec_set) HIPCHK(hipStreamWaitEvent(h->rd_stream, h->ev_spec, 0));
-    const float *ring = h->d_spec_ring + (size_t)h->spec_slot[(size_t)stream] * spec::RING * 2 * spec::N;
+    const float *ring = h->d_spec_ring + (size_t)T.slot[(size_t)stream] * spec::RING * 2 * spec::N;
     for (int i = 0; i < n; i++) {
         const int64_t r = have[i];
         recs[i] = fmx_spectrum_record{r, spec::record_end(r, h->spec_B, h->spec_S), h->spec_B, h->spec_S};
@@ -498,7 +458,7 @@ int fmx_spectrum_read(fmx_handle h, int32_t stream, fmx_spectrum_record *recs, f
         if (peak) HIPCHK(hipMemcpyAsync(peak + (size_t)i * spec::N, slot + spec::N, sizeof(float) * spec::N, hipMemcpyDeviceToHost, h->rd_stream));
     }
     HIPCHK(hipStreamSynchronize(h->rd_stream));
-    h->rd.spec[(size_t)stream] = have[n - 1] + 1;
+    T.commit((size_t)stream, have[(size_t)n - 1] + 1);
     *n_records = n;
     return FMX_OK;
 }
@@ -509,7 +469,7 @@ int fmx_spectrum_figures(const fmx_spectrum_find *cfg, const float *mean, const 
     return rc == FMX_OK ? FMX_OK : fail(rc, why);
 }
 
-// The multiplex spectrum meter's records of a range of channels.  Which record a ring slot holds is the host's (fmx_handle_s::mpx_tag).  The records of the
+// The multiplex spectrum meter's records of a range of channels.  Which record a ring slot holds is the host's (SlotTap::tags).  The records of the
 // whole range are gathered on the device into one staging array (mpx_gather_kernel) behind the handle's last call, and leave it in ONE copy to pinned
 // memory (a range of more than MPX_READ_BATCH records: one copy per 4096 records, 64 MB of staging at the most).  The cursors move only when every copy
 // has arrived: a read that fails loses nothing.
@@ -522,29 +482,25 @@ int fmx_mpx_spectrum_read(fmx_handle h, int32_t first_channel, int32_t n_channel
     const int32_t cap = capacity_per_channel;
     if (cap < 0 || (cap > 0 && (!recs || !mean))) return fail(FMX_E_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(h->mtx);
-    if (h->mpx_tag.empty() || cap == 0) return FMX_OK;
+    SlotTap &T = h->mpx_tap; GatherStage &S = h->mpx_stage;
+    if (!T.started() || cap == 0) return FMX_OK;
     // what the range has to hand out: per record its place in the ring and in the caller's arrays
-    h->mpx_src.clear();
+    S.src.clear();
     std::vector<size_t> dst;
-    std::vector<int64_t> next((size_t)n_channels, -1);
+    std::vector<int64_t> next((size_t)n_channels, -1), have;
     std::vector<int32_t> count((size_t)n_channels, 0);
     for (int q = 0; q < n_channels; q++) {
         const size_t ch = (size_t)(first_channel + q);
-        int64_t have[mpx::RING]; int n = 0;
-        for (int k = 0; k < mpx::RING; k++) {
-            const int64_t r = h->mpx_tag[ch * mpx::RING + (size_t)k];
-            if (r >= h->rd.mpx[ch]) have[n++] = r;      // (older ones were read, or overwritten: the gap shows in `index`)
-        }
-        std::sort(have, have + n);
-        n = std::min<int>(n, cap);
+        T.pending(ch, cap, have);      // (older ones were read, or overwritten: the gap shows in `index`)
+        const int n = (int)have.size();
         for (int i = 0; i < n; i++) {
-            const int64_t r = have[i];
+            const int64_t r = have[(size_t)i];
             const size_t at = (size_t)q * (size_t)cap + (size_t)i;
             recs[at] = fmx_mpx_record{r, spec::record_end(r, h->mpx_B, h->mpx_S), h->mpx_B, h->mpx_S};
-            h->mpx_src.push_back(h->mpx_slot[ch] * mpx::RING + (int32_t)(r & (mpx::RING - 1)));
+            S.src.push_back(T.slot[ch] * mpx::RING + (int32_t)(r & (mpx::RING - 1)));
             dst.push_back(at);
         }
-        if (n > 0) { next[(size_t)q] = have[n - 1] + 1; count[(size_t)q] = n; }
+        if (n > 0) { next[(size_t)q] = have[(size_t)n - 1] + 1; count[(size_t)q] = n; }
     }
     const int64_t total = (int64_t)dst.size();
     if (total == 0) return FMX_OK;
@@ -552,29 +508,23 @@ int fmx_mpx_spectrum_read(fmx_handle h, int32_t first_channel, int32_t n_channel
     if (!h->rd_stream) HIPCHK(hipStreamCreateWithFlags(&h->rd_stream, hipStreamNonBlocking));
     if (h->ev_mpx_set) HIPCHK(hipStreamWaitEvent(h->rd_stream, h->ev_mpx, 0));
     const int64_t batch = std::min(total, MPX_READ_BATCH);
-    if (batch > h->mpx_stage_recs) {
-        h->mem.release(h->d_mpx_src); h->mem.release(h->d_mpx_stage); h->mem.release(h->h_mpx_stage); h->mpx_stage_recs = 0;
-        FMXCHK(h->mem.alloc(h->d_mpx_src, (size_t)batch));
-        FMXCHK(h->mem.alloc(h->d_mpx_stage, (size_t)batch * 2 * mpx::BINS));
-        FMXCHK(h->mem.alloc_pinned(h->h_mpx_stage, (size_t)batch * 2 * mpx::BINS));
-        h->mpx_stage_recs = batch;
-    }
+    FMXCHK(S.ensure(h->mem, batch, 2 * mpx::BINS));
     g_launch_err = hipSuccess;
     for (int64_t o = 0; o < total; o += batch) {
         const int64_t m = std::min(batch, total - o);
-        HIPCHK(hipMemcpyAsync(h->d_mpx_src, h->mpx_src.data() + o, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, h->rd_stream));
-        launch_mpx_gather(h->d_mpx_ring, h->d_mpx_src, h->d_mpx_stage, (int)m, h->rd_stream);
+        HIPCHK(hipMemcpyAsync(S.d_src, S.src.data() + o, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, h->rd_stream));
+        launch_mpx_gather(h->d_mpx_ring, S.d_src, S.d_stage, (int)m, h->rd_stream);
         HIPCHK(g_launch_err);
-        HIPCHK(hipMemcpyAsync(h->h_mpx_stage, h->d_mpx_stage, sizeof(float) * (size_t)m * 2 * mpx::BINS, hipMemcpyDeviceToHost, h->rd_stream));
+        HIPCHK(hipMemcpyAsync(S.h_stage, S.d_stage, sizeof(float) * (size_t)m * 2 * mpx::BINS, hipMemcpyDeviceToHost, h->rd_stream));
         HIPCHK(hipStreamSynchronize(h->rd_stream));
         for (int64_t i = 0; i < m; i++) {
-            const float *from = h->h_mpx_stage + (size_t)i * 2 * mpx::BINS;
+            const float *from = S.h_stage + (size_t)i * 2 * mpx::BINS;
             std::memcpy(mean + dst[(size_t)(o + i)] * mpx::BINS, from, sizeof(float) * mpx::BINS);
             if (peak) std::memcpy(peak + dst[(size_t)(o + i)] * mpx::BINS, from + mpx::BINS, sizeof(float) * mpx::BINS);
         }
     }
     for (int q = 0; q < n_channels; q++)
-        if (count[(size_t)q] > 0) { h->rd.mpx[(size_t)(first_channel + q)] = next[(size_t)q]; n_records[q] = count[(size_t)q]; }
+        if (count[(size_t)q] > 0) { T.commit((size_t)(first_channel + q), next[(size_t)q]); n_records[q] = count[(size_t)q]; }
     return FMX_OK;
 }
 
@@ -584,7 +534,7 @@ int fmx_mpx_figures(const fmx_mpx_find *cfg, const float *mean, const float *pea
     return rc == FMX_OK ? FMX_OK : fail(rc, why);
 }
 
-// The sub-carrier decoder's blocks of a range of channels.  Which block a ring slot holds is the host's (fmx_handle_s::sca_tag).  Per channel the run of
+// The sub-carrier decoder's blocks of a range of channels.  Which block a ring slot holds is the host's (SlotTap::tags).  Per channel the run of
 // consecutive blocks from the oldest one not yet read; the runs of the whole range are gathered on the device into one staging array (sca_gather_kernel)
 // behind the handle's last call, and leave it in ONE copy to pinned memory (a range of more than SCA_READ_BATCH blocks: one copy per 65 536 blocks, 63 MB
 // of staging at the most).  The cursors move only when every copy has arrived: a read that fails loses nothing.
@@ -597,27 +547,21 @@ int fmx_sca_read(fmx_handle h, int32_t first_channel, int32_t n_channels, int64_
     const int32_t cap = capacity_blocks_per_channel;
     if (cap < 0 || (cap > 0 && !audio)) return fail(FMX_E_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(h->mtx);
-    if (h->sca_tag.empty() || cap == 0) return FMX_OK;
+    SlotTap &T = h->sca_tap; GatherStage &S = h->sca_stage;
+    if (!T.started() || cap == 0) return FMX_OK;
     constexpr int REC = sca::BLOCK_AUDIO + 1;
-    h->sca_src.clear();
+    S.src.clear();
     std::vector<size_t> dst;
     std::vector<int64_t> from((size_t)n_channels, -1);
     std::vector<int32_t> count((size_t)n_channels, 0);
     for (int q = 0; q < n_channels; q++) {
         const size_t ch = (size_t)(first_channel + q);
-        int64_t oldest = -1;
-        for (int k = 0; k < sca::RING; k++) {
-            const int64_t b = h->sca_tag[ch * sca::RING + (size_t)k];
-            if (b >= h->rd.sca[ch] && (oldest < 0 || b < oldest)) oldest = b;      // (older ones were read, or overwritten: the gap shows in first_block)
-        }
-        if (oldest < 0) continue;
-        int32_t n = 0;
-        while (n < cap && n < sca::RING && h->sca_tag[ch * sca::RING + (size_t)((oldest + n) % sca::RING)] == oldest + n) {      // (the run ends at a gap)
-            h->sca_src.push_back(h->sca_slot[ch] * sca::RING + (int32_t)((oldest + n) % sca::RING));
+        const SlotRun r = T.run(ch, cap);      // (older ones were read, or overwritten: the gap shows in first_block; the run ends at a gap)
+        for (int32_t n = 0; n < r.count; n++) {
+            S.src.push_back(T.slot[ch] * sca::RING + (int32_t)((r.from + n) % sca::RING));
             dst.push_back((size_t)q * (size_t)cap + (size_t)n);
-            n++;
         }
-        from[(size_t)q] = oldest; count[(size_t)q] = n;
+        from[(size_t)q] = r.from; count[(size_t)q] = r.count;
     }
     const int64_t total = (int64_t)dst.size();
     if (total == 0) return FMX_OK;
@@ -625,30 +569,24 @@ int fmx_sca_read(fmx_handle h, int32_t first_channel, int32_t n_channels, int64_
     if (!h->rd_stream) HIPCHK(hipStreamCreateWithFlags(&h->rd_stream, hipStreamNonBlocking));
     if (h->ev_sca_set) HIPCHK(hipStreamWaitEvent(h->rd_stream, h->ev_sca, 0));
     const int64_t batch = std::min(total, SCA_READ_BATCH);
-    if (batch > h->sca_stage_blocks) {
-        h->mem.release(h->d_sca_src); h->mem.release(h->d_sca_stage); h->mem.release(h->h_sca_stage); h->sca_stage_blocks = 0;
-        FMXCHK(h->mem.alloc(h->d_sca_src, (size_t)batch));
-        FMXCHK(h->mem.alloc(h->d_sca_stage, (size_t)batch * REC));
-        FMXCHK(h->mem.alloc_pinned(h->h_sca_stage, (size_t)batch * REC));
-        h->sca_stage_blocks = batch;
-    }
+    FMXCHK(S.ensure(h->mem, batch, REC));
     g_launch_err = hipSuccess;
     for (int64_t o = 0; o < total; o += batch) {
         const int64_t m = std::min(batch, total - o);
-        HIPCHK(hipMemcpyAsync(h->d_sca_src, h->sca_src.data() + o, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, h->rd_stream));
-        launch_sca_gather(h->d_sca_audio, h->d_sca_level, h->d_sca_src, h->d_sca_stage, (int)m, h->rd_stream);
+        HIPCHK(hipMemcpyAsync(S.d_src, S.src.data() + o, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, h->rd_stream));
+        launch_sca_gather(h->d_sca_audio, h->d_sca_level, S.d_src, S.d_stage, (int)m, h->rd_stream);
         HIPCHK(g_launch_err);
-        HIPCHK(hipMemcpyAsync(h->h_sca_stage, h->d_sca_stage, sizeof(float) * (size_t)m * REC, hipMemcpyDeviceToHost, h->rd_stream));
+        HIPCHK(hipMemcpyAsync(S.h_stage, S.d_stage, sizeof(float) * (size_t)m * REC, hipMemcpyDeviceToHost, h->rd_stream));
         HIPCHK(hipStreamSynchronize(h->rd_stream));
         for (int64_t i = 0; i < m; i++) {
-            const float *src = h->h_sca_stage + (size_t)i * REC;
+            const float *src = S.h_stage + (size_t)i * REC;
             std::memcpy(audio + dst[(size_t)(o + i)] * sca::BLOCK_AUDIO, src, sizeof(float) * sca::BLOCK_AUDIO);
             if (level) level[dst[(size_t)(o + i)]] = src[sca::BLOCK_AUDIO];
         }
     }
     for (int q = 0; q < n_channels; q++)
         if (count[(size_t)q] > 0) {
-            h->rd.sca[(size_t)(first_channel + q)] = from[(size_t)q] + count[(size_t)q];
+            T.commit((size_t)(first_channel + q), from[(size_t)q] + count[(size_t)q]);
             first_block[q] = from[(size_t)q]; n_blocks[q] = count[(size_t)q];
         }
     return FMX_OK;
@@ -675,7 +613,7 @@ int fmx_sca_info(int32_t fmRate, fmx_sca_info_t *out) {
     return FMX_OK;
 }
 
-// The monitoring feed's blocks of a range of channels, for both read-outs.  Which block a ring slot holds is the host's (fmx_handle_s::feed_tag).  Per
+// The monitoring feed's blocks of a range of channels, for both read-outs.  Which block a ring slot holds is the host's (SlotTap::tags).  Per
 // channel the run of consecutive blocks from the oldest one not yet read.  fmx_feed_read gathers the runs of the whole range on the device into one
 // staging array (feed_gather_kernel, which converts the format) behind the handle's last call, and they leave it in one copy of the audio and one of the
 // powers to pinned memory (a range of more than FEED_READ_BATCH blocks: a pair of copies per 65 536 blocks, 42 MB of staging at the most);
@@ -695,22 +633,16 @@ struct FeedRuns {
 void feed_runs(fmx_handle h, int32_t first_channel, int32_t n_channels, int32_t cap, FeedRuns &runs) {
     runs.from.assign((size_t)n_channels, -1); runs.count.assign((size_t)n_channels, 0);
     h->feed_src.clear(); h->feed_dst.clear();
-    if (h->feed_tag.empty() || cap == 0) return;
+    const SlotTap &T = h->feed_tap;
+    if (!T.started() || cap == 0) return;
     for (int q = 0; q < n_channels; q++) {
         const size_t ch = (size_t)(first_channel + q);
-        int64_t oldest = -1;
-        for (int k = 0; k < feed::RING; k++) {
-            const int64_t b = h->feed_tag[ch * feed::RING + (size_t)k];
-            if (b >= h->rd.feed[ch] && (oldest < 0 || b < oldest)) oldest = b;      // (older ones were read, or overwritten: the gap shows in first_block)
-        }
-        if (oldest < 0) continue;
-        int32_t n = 0;
-        while (n < cap && n < feed::RING && h->feed_tag[ch * feed::RING + (size_t)((oldest + n) % feed::RING)] == oldest + n) {      // (the run ends at a gap)
-            h->feed_src.push_back(h->feed_slot[ch] * feed::RING + (int32_t)((oldest + n) % feed::RING));
+        const SlotRun r = T.run(ch, cap);      // (older ones were read, or overwritten: the gap shows in first_block; the run ends at a gap)
+        for (int32_t n = 0; n < r.count; n++) {
+            h->feed_src.push_back(T.slot[ch] * feed::RING + (int32_t)((r.from + n) % feed::RING));
             h->feed_dst.push_back((int32_t)((int64_t)q * cap + n));
-            n++;
         }
-        runs.from[(size_t)q] = oldest; runs.count[(size_t)q] = n;
+        runs.from[(size_t)q] = r.from; runs.count[(size_t)q] = r.count;
     }
 }
 
@@ -743,7 +675,7 @@ int feed_index_arrays(fmx_handle h, int64_t n, hipStream_t s) {
 void feed_commit(fmx_handle h, int32_t first_channel, int32_t n_channels, const FeedRuns &runs, int64_t *first_block, int32_t *n_blocks) {
     for (int q = 0; q < n_channels; q++)
         if (runs.count[(size_t)q] > 0) {
-            h->rd.feed[(size_t)(first_channel + q)] = runs.from[(size_t)q] + runs.count[(size_t)q];
+            h->feed_tap.commit((size_t)(first_channel + q), runs.from[(size_t)q] + runs.count[(size_t)q]);
             first_block[q] = runs.from[(size_t)q]; n_blocks[q] = runs.count[(size_t)q];
         }
 }
